@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: 1024^2 SDXL images/sec (30 DDIM steps, one PNS candidate seed per GPU per step).
 
-  python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run)
 
 A "step" = one full 30-step denoise of one candidate per rank through the HIP hot path (UNet forward with
 the harmony-aware IP-Adapter processors + CFG + DDIM update), at BASELINE.json configs[1] (N=1) /
@@ -48,6 +48,8 @@ def parse():
                     "UNet batch per GPU (BASELINE.json configs[4] runs 4 per GPU); 1 = skip")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm; gloo only for "
                     "single-GPU testing of the multi-rank control path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned as DIR/<name>.npy in float32 (see dump_outputs); the same arguments give the same inputs")
     return ap.parse_args()
 
 
@@ -425,6 +427,36 @@ def pns_two_stage(eng, pipe, unet, cond, device, dtype, lat_shape, res, N=8, pre
                     "pns.run_pns(final_split_fn=...): measured no faster, DESIGN.md 7); the ceiling / tail share are for that one-seed-per-rank case"}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, out, score, world, rank):
+    """--dump-outputs DIR: what the last timed step returned on every rank, gathered in rank order -- latents.npy, the denoised
+    latents [world, 4, res / 8, res / 8] (DenoiseEngine.denoise), and pns_score.npy, the candidates' PNS scores [world]
+    (pns.default_scorer) -- in float32.  Latents beyond DUMP_CAP_BYTES keep a fixed, seeded sample of their flattened
+    elements instead (latents_sample.npy, with their flat indices as float64, exact below 2^53, in latents_sample_index.npy)."""
+    import numpy as np
+    import torch.distributed as dist
+    lat, sc = out.detach().float().contiguous(), score.detach().float().reshape(-1).contiguous()
+    if world > 1:
+        lats, scs = [torch.empty_like(lat) for _ in range(world)], [torch.empty_like(sc) for _ in range(world)]
+        dist.all_gather(lats, lat)
+        dist.all_gather(scs, sc)
+        lat, sc = torch.cat(lats), torch.cat(scs)
+    if rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    lat, sc = lat.cpu(), sc.cpu()
+    np.save(os.path.join(d, "pns_score.npy"), sc.numpy())
+    if lat.numel() * 4 <= DUMP_CAP_BYTES:
+        np.save(os.path.join(d, "latents.npy"), lat.numpy())
+    else:
+        n = DUMP_CAP_BYTES // 12                                     # 4-byte values + 8-byte indices
+        idx = torch.randperm(lat.numel(), generator=torch.Generator("cpu").manual_seed(0))[:n].sort().values
+        np.save(os.path.join(d, "latents_sample.npy"), lat.reshape(-1)[idx].numpy())
+        np.save(os.path.join(d, "latents_sample_index.npy"), idx.double().numpy())
+
+
 def _device_identity(device):
     """something that differs between two physical GPUs of one node and is equal for two ranks on the same one"""
     pr = torch.cuda.get_device_properties(device)
@@ -598,6 +630,8 @@ def main():
                                            "note": "the only collective after a PNS run's denoises besides the winner broadcast (pns.run_pns)"}
     dt = float(tmax.item())
     finite = bool(torch.isfinite(out).all().item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, scores[-1], world, rank)
 
     if rank == 0:
         # ---- roofline of the dominant kernel family, timed with HIP events on the launch stream ----

@@ -1,24 +1,14 @@
 """CPU: the on-disk formats either side of the path: accelerate checkpoint -> ip_adapter.bin
-regrouping (convert_bin.py) checked against the reference's OWN converter when /root/reference is present, and the
-.bin / .safetensors readers that feed IPAdapter.load_ip_adapter."""
-import importlib.util
+regrouping (convert_bin.py) checked against what the reference's OWN converter wrote for the same checkpoint
+(tests/golden/refpin_convert_bin.pt, oracle/gen_refpins.py), and the .bin / .safetensors readers that feed
+IPAdapter.load_ip_adapter."""
 import os
 
-import pytest
 import torch
 
 from imagharmony_amd import checkpoint as ck
-
-
-def _fake_training_checkpoint():
-    g = torch.Generator().manual_seed(0)
-    r = lambda *s: torch.randn(*s, generator=g)
-    return {"unet.conv_in.weight": r(8, 4, 3, 3),
-            "image_proj_model.proj.weight": r(16, 8), "image_proj_model.proj.bias": r(16),
-            "image_proj_model.norm.weight": r(4), "image_proj_model.norm.bias": r(4),
-            "adapter_modules.1.to_k_ip.weight": r(8, 6), "adapter_modules.1.to_v_ip.weight": r(8, 6),
-            "adapter_modules.3.to_k_ip.weight": r(8, 6), "adapter_modules.3.to_v_ip.weight": r(8, 6),
-            "composed_modules.fc1.weight": r(5, 3), "composed_modules.ln.bias": r(5)}
+from oracle.gen_refpins import fake_training_checkpoint as _fake_training_checkpoint
+from conftest import GOLDEN
 
 
 def test_regroup_and_roundtrip_both_formats(tmp_path):
@@ -52,16 +42,11 @@ def test_convert_tree_layout(tmp_path):
     assert os.path.exists(tmp_path / "run_a" / "checkpoint-200" / "ip_adapter.bin")
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/convert_bin.py"), reason="reference tree not present")
 def test_matches_reference_converter(tmp_path, capsys):
-    spec = importlib.util.spec_from_file_location("_ref_convert_bin", "/root/reference/convert_bin.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
     src = tmp_path / "pytorch_model.bin"
     torch.save(_fake_training_checkpoint(), src)
-    assert ref.convert_checkpoint_to_ip_adapter(str(src), str(tmp_path / "ref.bin"))
     assert ck.convert_checkpoint_to_ip_adapter(str(src), str(tmp_path / "ours.bin"))
-    a, b = torch.load(tmp_path / "ref.bin"), torch.load(tmp_path / "ours.bin")
+    a, b = torch.load(os.path.join(GOLDEN, "refpin_convert_bin.pt"))["out"], torch.load(tmp_path / "ours.bin")
     assert list(a) == list(b)
     for grp in a:
         assert list(a[grp]) == list(b[grp])

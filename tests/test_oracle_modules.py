@@ -1,17 +1,15 @@
 """CPU: the oracle restatement (oracle/modules.py) against the golden vectors minted from
-the reference's own modules (oracle/gen_golden.py), and -- when /root/reference is present --
-against the verbatim reference modules live."""
-import contextlib
-import io
+the reference's own modules (oracle/gen_golden.py, oracle/gen_refpins.py)."""
 import os
 
+import numpy as np
 import pytest
 import torch
 
 from oracle import modules as om
-from oracle import refshim
 from oracle.detfill import det_fill, det_randn
 from oracle.gen_golden import ATTN_CASES, HA_CFG, RES_PLUSXL, RES_TEST, attn_inputs, make_attn
+from oracle.gen_refpins import LEGACY_CASES, state_dict_modules, state_dict_outputs
 from conftest import GOLDEN, rel_rms
 
 TOL = 2e-6   # fp32 vs fp32, same math, different op order
@@ -98,43 +96,37 @@ def test_resampler_matches_reference_golden(name, cfg):
     assert rel_rms(y, g["out"]) < TOL
 
 
-@pytest.mark.refshim
-@pytest.mark.skipif(not refshim.available(), reason="/root/reference not present")
 def test_oracle_state_dicts_interchange_with_reference_live():
-    """Same parameter names/shapes as the verbatim reference modules, and identical outputs."""
-    ref = refshim.load()
-    with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
-        pairs = [
-            (ref.HarmonyAttention(**HA_CFG), om.HarmonyAttention(**HA_CFG)),
-            (ref.ImageProjModel(2048, 1280, 4), om.ImageProjModel(2048, 1280, 4)),
-            (ref.Resampler(**RES_TEST), om.Resampler(**RES_TEST)),
-            (ref.IPAttnProcessor2_0(640, 2048), om.IPAttnProcessor2_0(640, 2048)),
-        ]
-        for r, o in pairs:
-            rs, os_ = r.state_dict(), o.state_dict()
-            assert list(rs.keys()) == list(os_.keys())
-            assert all(rs[k].shape == os_[k].shape for k in rs)
-            o.load_state_dict(rs, strict=True)
-        text, img = det_randn((1, 77, 2048), 1), det_randn((1, 1280), 2)
-        assert rel_rms(pairs[0][1](text, img), pairs[0][0](text, img)) < TOL
-        x = det_randn((2, 257, 1280), 3)
-        assert rel_rms(pairs[2][1](x), pairs[2][0](x)) < TOL
+    """Same parameter names/shapes as the verbatim reference modules, and identical outputs with the same weights
+    (tests/golden/refpin_state_dicts.pt: the reference modules' state-dict layout, and their outputs filled by
+    det_fill, which derives every value from the parameter's name and shape alone)."""
+    g = torch.load(os.path.join(GOLDEN, "refpin_state_dicts.pt"))
+    mods = state_dict_modules(om)
+    with torch.no_grad():
+        for name, o in mods:
+            os_ = o.state_dict()
+            assert [k for k, _ in g["keys"][name]] == list(os_.keys()), name
+            assert all(tuple(os_[k].shape) == shape for k, shape in g["keys"][name]), name
+            o.load_state_dict({k: torch.zeros(shape) for k, shape in g["keys"][name]}, strict=True)
+        out = state_dict_outputs(mods)
+        assert rel_rms(out["ha_out"], g["ha_out"]) < TOL
+        assert rel_rms(out["res_out"], g["res_out"]) < TOL
 
 
-@pytest.mark.skipif(not refshim.available(), reason="/root/reference not present")
-@pytest.mark.parametrize("case", ["c1280_t4", "c128_t32"])
+@pytest.mark.parametrize("case", LEGACY_CASES)
 def test_reference_legacy_processors_equal_the_2_0_golden(case):
     """the reference's torch<2 processors (attention_processor.py:60-241, baddbmm + softmax + bmm) against the golden
     outputs of its 2_0 processors: same math -- which is why the legacy names alias the 2_0 classes here, as
-    ip_adapter.py:13-24 does upstream on torch >= 2.  Their attn_map is the true probability tensor (:221-222)."""
-    ref = refshim.load()
+    ip_adapter.py:13-24 does upstream on torch >= 2.  Their attn_map is the true probability tensor (:221-222).
+    The legacy outputs are stored in tests/golden/refpin_legacy_attn.npz as differences from the 2_0 outputs (oracle/gen_refpins.py)."""
     g = torch.load(os.path.join(GOLDEN, f"attn_{case}.pt"))
-    b, l, c, h, cd, nt, t, scale = ATTN_CASES[case]
-    hs, ehs = attn_inputs(case)
-    with torch.no_grad():
-        attn = make_attn(case, cross=True)
-        p = det_fill(ref.IPAttnProcessor(c, cd, scale=scale, num_tokens=t), 17, prefix="proc.")
-        y = p(attn, hs, encoder_hidden_states=ehs)
-        assert rel_rms(y, g["ip_skip0"]) < 1e-5
-        assert p.attn_map.shape[-1] == t and torch.allclose(p.attn_map.sum(-1), torch.ones_like(p.attn_map.sum(-1)), atol=1e-5)
-        assert rel_rms(ref.AttnProcessor()(make_attn(case, cross=False), hs), g["self"]) < 1e-5
+    with np.load(os.path.join(GOLDEN, "refpin_legacy_attn.npz")) as z:
+        ip = g["ip_skip0"] + torch.from_numpy(z[f"{case}.ip_minus_2_0"])
+        sa = g["self"] + torch.from_numpy(z[f"{case}.self_minus_2_0"])
+        attn_map = torch.from_numpy(z[f"{case}.attn_map"])
+    t = ATTN_CASES[case][6]
+    assert rel_rms(ip, g["ip_skip0"]) < 1e-5
+    assert attn_map.shape[-1] == t and torch.allclose(attn_map.sum(-1), torch.ones_like(attn_map.sum(-1)), atol=1e-5)
+    assert rel_rms(sa, g["self"]) < 1e-5
+    from imagharmony_amd import attention_processor as hap
+    assert hap.IPAttnProcessor is hap.IPAttnProcessor2_0 and hap.AttnProcessor is hap.AttnProcessor2_0
