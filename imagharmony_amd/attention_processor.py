@@ -191,33 +191,30 @@ class AttnProcessor2_0(nn.Module):
         return out
 
     def _emit_ragged(self, ctx, attn, x, B, L_, residual, ln):
-        """Token counts that are not a multiple of the 64-key tile (e.g. 1152x896 -> 36x28 = 1008 tokens at the
-        deepest level): every batch gets its own 64-padded slab of [Q|K] and V^T (dedicated zero-initialised
-        buffers, so the padded keys stay finite for ever; they are masked in the kernel), projections run per batch."""
+        """Token counts that are not a multiple of the 64-key tile (1152x896 -> 36x28 = 1008 tokens, 832x1216 -> 26x38 = 988 at the
+        deepest level): the rows of every batch are copied into its own Lp-row slab of a zero-initialised buffer (the padded rows are
+        never written, so they stay zero), [Q|K] and V^T are projected over all B*Lp rows -- the V^T store permutes keys in groups of
+        16 and only ever sees whole groups; the padded keys are exact zeros -- and the kernel masks the keys at or past L_."""
         if ln is not None:
             raise L.ImhError("ragged token counts are not supported together with the folded-LayerNorm path")
-        if L_ % 16:
-            raise L.ImhError(f"self-attention over {L_} tokens: the fused path needs a multiple of 16 "
-                             f"(the V^T layout permutes keys in groups of 16); use a resolution whose latent sides are even")
         C_ = x.shape[1]
         H = attn.heads
         Lp = _pad64(L_)
         wqk, wv, wo, bo = _packed_qk(attn, ctx), _w(attn.to_v, ctx), _w(attn.to_out[0], ctx), _b(attn.to_out[0], ctx)
-        qk = torch.zeros(B * Lp, 2 * C_, dtype=ctx.dtype, device=ctx.device)
-        vt = torch.zeros(C_, B * Lp, dtype=ctx.dtype, device=ctx.device)
-        ao = torch.zeros(B * Lp, C_, dtype=ctx.dtype, device=ctx.device)
-        if ctx.record:
-            ctx.keep.extend((qk, vt, ao))
-        for b in range(B):
-            xb = x[b * L_:(b + 1) * L_]
-            ctx.gemm(xb, wqk, out=qk[b * Lp:b * Lp + L_], descr="self.to_qk")
-            ctx.gemm(wv, xb, out=vt[:, b * Lp:b * Lp + L_], flags=L.GF_VT_PERM, descr="self.to_v^T")
+        xp = ctx.zero_slab(B * Lp, C_)
+        for b in range(B):          # (a concat with an empty second part: a row copy)
+            ctx.ew(L.EW_CONCAT, xp[b * Lp:b * Lp + L_], a=x[b * L_:(b + 1) * L_], b=x[b * L_:(b + 1) * L_], n=L_, i=(C_, 0, 0, 0, 0, 0),
+                   descr="self.pad_rows", nbytes=2.0 * L_ * C_ * x.element_size())
+        qk, vt = ctx.gemm_dual(dict(x=xp, w=wqk), dict(x=wv, w=xp, flags=L.GF_VT_PERM), cfg=(128, 64), descr="self.to_qk+v^T")
+        ao = ctx.new(B * Lp, C_)
         ctx.attention(qk[:, :C_], qk[:, C_:], vt, ao, B, H, Lp, L_, Lp, 2 * C_, 2 * C_, B * Lp, C_,
                       HEAD_DIM ** -0.5, descr="self.attn")
+        ctx.free(qk); ctx.free(vt)
         out = ctx.new(B * L_, C_)
         for b in range(B):
             ctx.gemm(ao[b * Lp:b * Lp + L_], wo, bias=bo, out=out[b * L_:(b + 1) * L_],
                      residual=None if residual is None else residual[b * L_:(b + 1) * L_], descr="self.to_out")
+        ctx.free(ao)
         return out
 
     # -- eager plugin protocol ------------------------------------------------------------

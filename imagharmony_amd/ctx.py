@@ -102,6 +102,7 @@ class Ctx:
         self.captured = False
         self._ops = []          # recorded (kind, ctypes args, cold tensors) for the weight-prefetch pass
         self._pf_done = False
+        self._zero_slabs = {}
 
     # ------------------------------------------------------------------ memory
     def new(self, *shape, dtype=None):
@@ -138,6 +139,14 @@ class Ctx:
         t = torch.zeros(*shape, dtype=dtype or self.dtype, device=self.device)
         if self.record:
             self.keep.append(t)
+        return t
+
+    def zero_slab(self, *shape):
+        """a zero-initialised buffer shared by every caller that asks for this shape: for ops that write only part of it and need the
+        rest to stay zero (the padded token rows of a ragged self-attention); its users run in stream order, like the pool's"""
+        t = self._zero_slabs.get(shape)
+        if t is None:
+            t = self._zero_slabs[shape] = self.zeros(*shape)
         return t
 
     def workspace(self, nbytes):
@@ -203,10 +212,13 @@ class Ctx:
     _HALO = (7128, 7564, 7328, 7428, 7256, 7356)   # LDS-halo conv3x3, stride 1 (7328 / 7428: weight rings; 7256 / 7356: 16 x 16 patch)
 
     @classmethod
-    def _variant_ok(cls, bm, sp, flags, conv, stride, ln_pre):
+    def _variant_ok(cls, bm, sp, flags, conv, stride, ln_pre, M=0, N=0, extras=False):
+        """extras: the launch has a bias, residual, row-add, second token source or transposed store (the epilogue inputs the
+        sixteen-wave tile has none of: gemm_w16_launch refuses them, and whole tiles only)"""
         plain = bm <= 128
         if bm in cls._W16:
-            return not conv and sp == 1 and bool(flags & L.GF_LN_ROW) and not flags & ~(L.GF_LN_ROW | L.GF_GEGLU) and bool(ln_pre)
+            return not conv and sp == 1 and bool(flags & L.GF_LN_ROW) and not flags & ~(L.GF_LN_ROW | L.GF_GEGLU) and bool(ln_pre) \
+                and not extras and M % 256 == 0 and N % 320 == 0
         if bm in cls._HALO:
             return bool(conv) and stride == 1 and not flags & (L.GF_LN_ROW | L.GF_LN_COL | L.GF_VT_PERM)
         if flags & (L.GF_VT_PERM | L.GF_LN_COL):
@@ -227,7 +239,7 @@ class Ctx:
             return 0
         return cells
 
-    def _config(self, M, N, K, conv, flags, stride=1, ln_pre=False, up=0):
+    def _config(self, M, N, K, conv, flags, stride=1, ln_pre=False, up=0, extras=False):
         """tile variant of a launch: the tuning table's entry for the shape if that variant implements the launch's flags
         (folded LayerNorm in either form, V^T permutation, conv stride), else the built-in heuristic -- in ONE place"""
         key = (M, N, K, int(conv))
@@ -237,7 +249,7 @@ class Ctx:
         # 64^2 ResBlock convs of UNet batch 8, which want the LDS-halo form that fuses their GroupNorm)
         cfg = (self.tuning.get(key + (1,)) if ln_pre else self.tuning.get(key + (2,)) if conv and stride == 2
                else self.tuning.get(key + (3,)) if conv and up else None) or self.tuning.get(key)
-        if cfg is not None and self._variant_ok(cfg[0], cfg[2], flags, conv, stride, ln_pre):
+        if cfg is not None and self._variant_ok(cfg[0], cfg[2], flags, conv, stride, ln_pre, M, N, extras):
             return tuple(cfg)
         bm, bn, sp = C.c_int(), C.c_int(), C.c_int()
         self.lib.imh_gemm_pick_config(M, N, K, C.byref(bm), C.byref(bn), C.byref(sp))
@@ -294,7 +306,8 @@ class Ctx:
             raise L.ImhError(f"{descr}: stats_out describes rows stored in the compute dtype; an fp32 output (GF_OUT_F32) has no such statistics")
         if stats_out and gn_out is not None:
             raise L.ImhError(f"{descr}: stats_out and gn_out are mutually exclusive (one consumer norm per output)")
-        bm, bn, sp = cfg or self._config(M, N, K, 0, flags, ln_pre=ln_stats is not None)
+        bm, bn, sp = cfg or self._config(M, N, K, 0, flags, ln_pre=ln_stats is not None, extras=any(
+            t is not None for t in (bias, residual, rowadd, x2, yt)))
         if x2 is not None and not (bm <= 128 or bm in self._WS):
             if cfg is not None:
                 raise L.ImhError(f"{descr}: variant {bm} does not read a two-source token operand")
@@ -510,7 +523,8 @@ class Ctx:
         es = q.element_size()
         fl = 4.0 * B * H * Lq * (Lk + Lk2) * 64
         by = es * (2 * B * Lq * H * 64 + 2 * B * (Lk + Lk2) * H * 64)
-        self._emit(L.OP_ATTN, a, descr=descr, flops=fl, nbytes=by, keep=(q, k, vt, out, k2, vt2, scale2_tab, step))
+        self._emit(L.OP_ATTN, a, descr=descr, flops=fl, nbytes=by, keep=(q, k, vt, out, k2, vt2, scale2_tab, step),
+                   shape=(B, H, Lq, Lk, Lk_pad), epi=dict(Lk2=Lk2, Lk2_pad=Lk2_pad, tab=scale2_tab is not None))
         return out
 
     def cross_attention(self, x, wq, k, vt, out, B, H, Lq, Lk, Lk_pad, ldk, ldvt, scale, ln=None,
@@ -547,7 +561,9 @@ class Ctx:
         fl = 2.0 * M * C_ * C_ + 4.0 * B * H * Lq * (Lk + Lk2) * 64
         by = es * (2 * M * C_ + C_ * C_ + 2 * B * (Lk + Lk2) * C_)
         self._emit(L.OP_XATTN, a, descr=descr, flops=fl, nbytes=by,
-                   keep=(x, wq, k, vt, out, k2, vt2, scale2_tab, step) + tuple((ln or ())[:2]) + keep_st)
+                   keep=(x, wq, k, vt, out, k2, vt2, scale2_tab, step) + tuple((ln or ())[:2]) + keep_st,
+                   shape=(B, H, Lq, Lk, Lk_pad), epi=dict(Lk2=Lk2, Lk2_pad=Lk2_pad, tab=scale2_tab is not None, ln=ln is not None,
+                                                          ln_slots=int(a.ln_slots) if ln is not None else 0))
         if own:
             self.free(keep_st[0])
         return out
@@ -740,7 +756,7 @@ class Ctx:
         a.rows, a.C, a.eps, a.dtype = rows, Cc, eps, self.dt
         es = x.element_size()
         self._emit(L.OP_LAYERNORM, a, descr=descr, flops=8.0 * x.numel(), nbytes=2.0 * es * x.numel(),
-                   keep=(x, out, gamma, beta))
+                   keep=(x, out, gamma, beta), shape=(rows, Cc))
         return out
 
     # ------------------------------------------------------------------ elementwise

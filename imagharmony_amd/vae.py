@@ -97,25 +97,36 @@ class VAEAttention(nn.Module):
     def emit(self, ctx, x):
         B, H, W, C_ = x.shape
         Lq = H * W
-        if Lq % 64:
-            raise L.ImhError(f"VAE attention: {H}x{W} tokens must be a multiple of 64")
+        # a token count that is not a multiple of 64 (a 100 x 100 latent): the PV GEMM runs over Lp keys (its K step is 64) from a
+        # probability matrix and a V^T whose padded keys are zero-filled and never written, so they contribute exact zeros; the scores
+        # GEMM runs over the Lq real keys, the softmax over Ls >= Lq columns (a multiple of 4) whose tail holds -inf scores (weight 0)
+        Lp, Ls = (Lq + 63) // 64 * 64, (Lq + 3) // 4 * 4
         n = _gn(ctx, self.group_norm, x, self.groups, False, "vae.attn.norm").view(B * Lq, C_)
         q = ctx.gemm(n, _w(self.to_q, ctx), bias=_b(self.to_q, ctx), descr="vae.attn.to_q")
         k = ctx.gemm(n, _w(self.to_k, ctx), bias=_b(self.to_k, ctx), descr="vae.attn.to_k")
         # V^T = Wv n^T (swapped operands) feeds the PV GEMM as its [N, K] operand; softmax rows sum to 1, so the
         # to_v bias is added once after PV instead of to every value row
-        vt = ctx.gemm(_w(self.to_v, ctx), n, descr="vae.attn.to_v^T")                       # [C, B*L]
+        if Lp == Lq:
+            vt = ctx.gemm(_w(self.to_v, ctx), n, descr="vae.attn.to_v^T")                   # [C, B*L]
+        else:
+            vt = ctx.zeros(C_, B * Lp)                                                      # [C, B*Lp], batch b's keys at b*Lp
+            for b in range(B):
+                ctx.gemm(_w(self.to_v, ctx), n[b * Lq:(b + 1) * Lq], out=vt[:, b * Lp:b * Lp + Lq], descr="vae.attn.to_v^T")
         ctx.free(n)
         o = ctx.new(B * Lq, C_)
-        sc = ctx.new(Lq, Lq, dtype=torch.float32)
-        pr = ctx.new(Lq, Lq)
+        if Ls == Lq:
+            sc = ctx.new(Lq, Lp, dtype=torch.float32)
+        else:
+            sc = ctx.zeros(Lq, Lp, dtype=torch.float32)
+            sc[:, Lq:Ls] = float("-inf")                                                    # plumbing: the softmax's padded columns
+        pr = ctx.new(Lq, Lp) if Lp == Lq else ctx.zeros(Lq, Lp)
         for b in range(B):
             qb, kb = q[b * Lq:(b + 1) * Lq], k[b * Lq:(b + 1) * Lq]
-            ctx.gemm(qb, kb, out=sc, flags=L.GF_OUT_F32, descr="vae.attn.scores")           # [L, L] fp32
-            ctx.ew(L.EW_SOFTMAX, pr, a=sc, i=(Lq, Lq, Lq, Lq, 0, 0), f=(C_ ** -0.5, 0.0, 0.0, 0.0),
-                   descr="vae.attn.softmax", nbytes=6.0 * Lq * Lq)
-            ctx.gemm(pr, vt[:, b * Lq:(b + 1) * Lq], out=o[b * Lq:(b + 1) * Lq], bias=_b(self.to_v, ctx), N=C_, K=Lq,
-                     ldw=B * Lq, descr="vae.attn.pv")
+            ctx.gemm(qb, kb, out=sc[:, :Lq], flags=L.GF_OUT_F32, descr="vae.attn.scores")   # [L, L] fp32
+            ctx.ew(L.EW_SOFTMAX, pr, a=sc, i=(Lq, Ls, Lp, Lp, 0, 0), f=(C_ ** -0.5, 0.0, 0.0, 0.0),
+                   descr="vae.attn.softmax", nbytes=6.0 * Lq * Ls)
+            ctx.gemm(pr, vt[:, b * Lp:(b + 1) * Lp], out=o[b * Lq:(b + 1) * Lq], bias=_b(self.to_v, ctx), N=C_, K=Lp,
+                     ldw=B * Lp, descr="vae.attn.pv")
         ctx.free(sc); ctx.free(pr); ctx.free(q); ctx.free(k); ctx.free(vt)
         out = ctx.gemm(o, _w(self.to_out[0], ctx), bias=_b(self.to_out[0], ctx), residual=x.view(B * Lq, C_),
                        descr="vae.attn.to_out")
@@ -263,19 +274,27 @@ def _res32(ctx, r, x):
 def _attn32(ctx, at, x):
     B, H, W, C_ = x.shape
     Lq = H * W
+    # a token count that is not a multiple of 16 (the PV GEMM's K step): the probabilities and V^T of the Lq real keys sit in zero-filled
+    # buffers of Lp keys whose padded columns are never written, so they contribute exact zeros
+    Lp = (Lq + 15) // 16 * 16
     n = _gn32(ctx, at.group_norm, x, at.groups, False, "vae32.attn.norm").view(B * Lq, C_)
     q = ctx.f32_gemm(n, _f32_lin_w(at.to_q), bias=_f32_vec(at.to_q), descr="vae32.attn.to_q")
     k = ctx.f32_gemm(n, _f32_lin_w(at.to_k), bias=_f32_vec(at.to_k), descr="vae32.attn.to_k")
     # V^T = Wv n^T (swapped operands) feeds the PV GEMM as its [N, K] operand; softmax rows sum to 1, so the to_v bias is added once after PV
-    vt = ctx.f32_gemm(_f32_lin_w(at.to_v), n, descr="vae32.attn.to_v^T")                      # [C, B*L]
+    if Lp == Lq:
+        vt = ctx.f32_gemm(_f32_lin_w(at.to_v), n, descr="vae32.attn.to_v^T")                  # [C, B*L]
+    else:
+        vt = ctx.zeros(C_, B * Lp, dtype=torch.float32)                                         # [C, B*Lp], batch b's keys at b*Lp
+        for b in range(B):
+            ctx.f32_gemm(_f32_lin_w(at.to_v), n[b * Lq:(b + 1) * Lq], out=vt[:, b * Lp:b * Lp + Lq], descr="vae32.attn.to_v^T")
     ctx.free(n)
     o = ctx.new(B * Lq, C_, dtype=torch.float32)
-    sc = ctx.new(Lq, Lq, dtype=torch.float32)
+    sc = ctx.new(Lq, Lq, dtype=torch.float32) if Lp == Lq else ctx.zeros(Lq, Lp, dtype=torch.float32)
     for b in range(B):
         qb, kb = q[b * Lq:(b + 1) * Lq], k[b * Lq:(b + 1) * Lq]
-        ctx.f32_gemm(qb, kb, out=sc, descr="vae32.attn.scores")
-        ctx.f32_softmax(sc, sc, C_ ** -0.5, descr="vae32.attn.softmax")                        # in place (a row is read before it is written)
-        ctx.f32_gemm(sc, vt[:, b * Lq:(b + 1) * Lq], out=o[b * Lq:(b + 1) * Lq], bias=_f32_vec(at.to_v), N=C_, K=Lq, ldw=B * Lq,
+        ctx.f32_gemm(qb, kb, out=sc[:, :Lq], descr="vae32.attn.scores")
+        ctx.f32_softmax(sc[:, :Lq], sc[:, :Lq], C_ ** -0.5, descr="vae32.attn.softmax")          # in place (a row is read before it is written)
+        ctx.f32_gemm(sc, vt[:, b * Lp:(b + 1) * Lp], out=o[b * Lq:(b + 1) * Lq], bias=_f32_vec(at.to_v), N=C_, K=Lp, ldw=B * Lp,
                      descr="vae32.attn.pv")
     ctx.free(sc); ctx.free(q); ctx.free(k); ctx.free(vt)
     out = ctx.f32_gemm(o, _f32_lin_w(at.to_out[0]), bias=_f32_vec(at.to_out[0]), residual=x.view(B * Lq, C_), descr="vae32.attn.to_out")

@@ -113,6 +113,22 @@ def test_fullsize_vae_decode_1024_reference_precision():
     assert rel < 4e-2, rel
 
 
+def test_fullsize_vae_decode_ragged_100x100():
+    """the full-size SDXL VAE on a 100x100 latent (800x800: 10000 tokens in the mid-block attention, not a multiple of 64): the native
+    bf16 decode and the fp32-precision decode of the same weights are finite and agree within the bf16-vs-fp32 bound of the 1024^2 test
+    (measured 1.24e-2)"""
+    from imagharmony_amd.vae import AutoencoderKL, decode_latents
+    vae = AutoencoderKL().init_random_(1).to(DEV, torch.float16)
+    lat = torch.randn(1, 4, 100, 100, generator=torch.Generator().manual_seed(0)).to(DEV) * 0.13025
+    a = decode_latents(vae, lat)
+    assert a.shape == (1, 3, 800, 800) and a.dtype == torch.float32 and torch.isfinite(a).all()
+    b = decode_latents(vae.to(torch.bfloat16), lat)
+    assert b.shape == a.shape and torch.isfinite(b).all()
+    rel = ((a - b).pow(2).mean().sqrt() / a.pow(2).mean().sqrt()).item()
+    print(f"full-size VAE 100x100: native bf16 vs fp32 rel-rms {rel:.3e}")
+    assert rel < 4e-2, rel
+
+
 @pytest.mark.parametrize("dtype,S,T,sched", [(torch.float16, 4, 16, "euler"), (torch.bfloat16, 4, 32, "ddim")])
 def test_fullsize_stacked_candidates_configs_3_and_4(dtype, S, T, sched):
     """BASELINE.json configs[3] (batch 4 per GPU, 16 Resampler tokens, fp16) and configs[4] (4 PNS candidates per GPU,

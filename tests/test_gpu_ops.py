@@ -286,21 +286,42 @@ def test_attention_self(L, dtype, mode, B, H, Lq):
         L.load().imh_debug_set(4, 0)
 
 
-def _attention_self_case(L, dtype, B, H, Lq):
+def _attention_self_case(L, dtype, B, H, Lq, Lk=None):
+    """Lk < Lq (= Lk_pad): only the first Lk keys of every batch are real; the padded keys and values hold large finite values
+    (not zeros), so a key the kernel fails to mask shows"""
+    Lk = Lk or Lq
     ctx = ctx_for(dtype)
     C_ = H * 64
     qk = rnd(B * Lq, 2 * C_, dtype=dtype, seed=1)
     v = rnd(B, Lq, C_, dtype=dtype, seed=2)
+    if Lk < Lq:
+        qk.view(B, Lq, 2 * C_)[:, Lk:, C_:] = 30.0
+        v[:, Lk:] = -100.0
     vt = make_vt(v, Lq)
     out = ctx.new(B * Lq, C_)
-    ctx.attention(qk[:, :C_], qk[:, C_:], vt, out, B, H, Lq, Lq, Lq, 2 * C_, 2 * C_, B * Lq, C_, 0.125)
-    ref = sdpa_ref(qk[:, :C_].reshape(B, Lq, C_), qk[:, C_:].reshape(B, Lq, C_), v, H)
-    assert_close(out.view(B, Lq, C_), ref, dtype, "self attention", k=6.0)
+    ctx.attention(qk[:, :C_], qk[:, C_:], vt, out, B, H, Lq, Lk, Lq, 2 * C_, 2 * C_, B * Lq, C_, 0.125)
+    ref = sdpa_ref(qk[:, :C_].reshape(B, Lq, C_), qk[:, C_:].reshape(B, Lq, C_)[:, :Lk], v[:, :Lk], H)
+    assert_close(out.view(B, Lq, C_), ref, dtype, f"self attention B={B} H={H} Lq={Lq} Lk={Lk}", k=6.0)
     first = out.clone()
     for _ in range(3):                                      # race screen of the rings / the key-split merge: bitwise repeatable
         out.zero_()
-        ctx.attention(qk[:, :C_], qk[:, C_:], vt, out, B, H, Lq, Lq, Lq, 2 * C_, 2 * C_, B * Lq, C_, 0.125)
+        ctx.attention(qk[:, :C_], qk[:, C_:], vt, out, B, H, Lq, Lk, Lq, 2 * C_, 2 * C_, B * Lq, C_, 0.125)
         assert torch.equal(out, first), "self attention not bitwise repeatable"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("mode", [0, 1, 2, 3] + ([5, 6] if experimental() else []))
+@pytest.mark.parametrize("B,H,Lk,Lk_pad", [(2, 20, 988, 1024), (2, 20, 1008, 1024), (1, 2, 63, 64), (2, 3, 1, 64), (1, 2, 100, 128),
+                                           (2, 10, 3952, 3968), (1, 1, 4031, 4096)])
+def test_attention_self_masked_keys(L, dtype, mode, B, H, Lk, Lk_pad):
+    """the ragged self-attention (AttnProcessor2_0._emit_ragged, the eager processor at any sequence length): keys at or past Lk inside
+    Lk_pad are masked, for key counts that are not a multiple of 16 (832x1216: 988 tokens at the deepest level) as well as of 64, in
+    every mode of test_attention_self (a key count that is not a multiple of 64 takes the in-order kernel in all of them)"""
+    assert L.load().imh_debug_set(4, mode) == 0
+    try:
+        _attention_self_case(L, dtype, B, H, Lk_pad, Lk)
+    finally:
+        L.load().imh_debug_set(4, 0)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

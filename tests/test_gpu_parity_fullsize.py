@@ -36,7 +36,8 @@ TOL_TRAJ30 = {torch.bfloat16: 3e-2, torch.float16: 4e-3}
 
 
 def _threads():
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
+    cap = int(os.environ.get("OMP_NUM_THREADS") or 16)       # a command may use 16 CPUs however many the machine shows
+    torch.set_num_threads(max(1, min(16, cap, os.cpu_count() or 1)))
 
 
 @pytest.fixture(scope="module")
@@ -300,29 +301,35 @@ def test_thirty_step_trajectory_reduced_width(dtype):
 # ------------------------------------------------------------------------------------------------------------
 # (b) every launch variant of the benchmarked forward
 # ------------------------------------------------------------------------------------------------------------
-def _forward_ops():
-    """distinct (shape, variant, epilogue) GEMM-family launches of the 1024^2 CFG-2 forward, from a dry recording"""
-    from imagharmony_amd.ctx import Ctx
-    from imagharmony_amd.ip_adapter import install_ip_processors
-    from imagharmony_amd.unet import UNet2DConditionModel, UNetConfig
-    with torch.device("meta"):
-        u = UNet2DConditionModel(UNetConfig())
-    u = u.to_empty(device="cpu").to(torch.bfloat16)
-    install_ip_processors(u, num_tokens=4, device="cpu", dtype=torch.bfloat16, init="empty")
-    ctx = Ctx("cpu", torch.bfloat16, record=True, dry=True)
-    st = u.prepare_conditioning(ctx, torch.zeros(2, 81, 2048), torch.zeros(2, 1280), torch.zeros(2, 6))
-    st.t_value = torch.zeros(2)
-    st.latents = torch.zeros(1, 4, 128, 128)
-    u.emit_forward(ctx, st, 1, 128, 128, cfg_dup=True)
-    seen, ops = set(), []
-    for (tag, kind, descr, fl, by_, shape, epi) in ctx.tags:
-        if kind != 0 or epi is None:
-            continue
-        key = (shape, tuple(sorted((k, str(v)) for k, v in epi.items())))
-        if key not in seen:
-            seen.add(key)
-            ops.append((descr, shape, epi))
-    return ops
+def _forward_ops(S=1, Hl=128, Wl=128):
+    """distinct (shape, variant, epilogue) GEMM-family launches of the CFG forward of S latents at Hl x Wl (default: the benchmarked
+    1024^2 forward), from a dry recording"""
+    return _distinct_launches([(S, Hl, Wl)])[0]
+
+
+def _distinct_launches(resolutions):
+    """the union over dry recordings of the forward at every (S, Hl, Wl) of `resolutions` of the distinct launches, deduplicated across
+    resolutions: GEMM-family (descr, shape, epi) as _forward_ops, self-attention (descr, (B, H, Lq, Lk, Lk_pad), epi), fused
+    cross-attention likewise, stand-alone LayerNorm (rows, C)"""
+    from forward_recordings import record_forward, sdxl_unet_meta
+    from imagharmony_amd import lib as L
+    u = sdxl_unet_meta()
+    seen, ops, attn, xattn, lns = set(), [], {}, {}, set()
+    for r in resolutions:
+        ctx = record_forward(u, *r)
+        for (tag, kind, descr, fl, by_, shape, epi) in ctx.tags:
+            if kind == L.OP_GEMM and epi is not None:
+                key = (shape, tuple(sorted((k, str(v)) for k, v in epi.items())))
+                if key not in seen:
+                    seen.add(key)
+                    ops.append((descr, shape, epi))
+            elif kind == L.OP_ATTN:
+                attn.setdefault((shape, str(epi)), (descr, shape, epi))
+            elif kind == L.OP_XATTN:
+                xattn.setdefault((shape, str(epi)), (descr, shape, epi))
+            elif kind == L.OP_LAYERNORM:
+                lns.add(shape)
+    return ops, list(attn.values()), list(xattn.values()), sorted(lns)
 
 
 _OPS = None
@@ -338,6 +345,12 @@ def _ops():
 def _rnd(shape, dtype, seed, scale=1.0):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return (torch.randn(*shape, generator=g) * scale).to(dtype).to(DEV)
+
+
+def _rnd_dev(shape, dtype, seed, scale=1.0):
+    """_rnd drawn on the device (the resolution sweep's ~420 launches per dtype: host-side draws of their operands would dominate)"""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return (torch.randn(*shape, generator=g, device=DEV) * scale).to(dtype)
 
 
 def _rand_norm(K):
@@ -356,6 +369,15 @@ def _close(y, ref, dtype, what, k=4.0):
     assert math.isfinite(err), f"{what}: non-finite"
     # same bound as tests/test_gpu_ops.py: a few output ulps of the result scale, 2 ulp rel-rms
     assert err <= k * EPS[dtype] * scale and rms <= 2 * EPS[dtype], f"{what}: max err {err:.3e} (scale {scale:.3e}) rel-rms {rms:.3e}"
+
+
+def _conv3x3_ref(xin, w4, stride):
+    """fp32 3x3 conv, padding 1, as im2col + matmul (F.conv2d would go through the vendor conv library, which builds and tunes kernels
+    for every new shape -- hundreds of geometries in the resolution sweep)"""
+    B, Cin, H, W = xin.shape
+    cols = F.unfold(xin, 3, padding=1, stride=stride)                              # [B, Cin * 9, Ho * Wo], (c, ky, kx) order
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return (w4.reshape(w4.shape[0], -1) @ cols).view(B, w4.shape[0], Ho, Wo)
 
 
 def _ref_epilogue(acc, epi, bias, residual, rowadd, L):
@@ -382,14 +404,23 @@ def _ref_epilogue(acc, epi, bias, residual, rowadd, L):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_every_gemm_and_conv_variant_of_the_benchmarked_forward(dtype):
-    from imagharmony_amd import lib as L
-    from imagharmony_amd.attention_processor import fold_ln
     from imagharmony_amd.ctx import Ctx
     ctx = Ctx(DEV, dtype)
-    ops = _ops()
+    n_checked, variants = _check_gemm_launches(ctx, dtype, _ops())
+    print(f"{dtype}: {n_checked} distinct launches checked; variants (bm, bn, splits, conv): {sorted(variants, key=str)}")
+    assert n_checked >= 35
+
+
+def _check_gemm_launches(ctx, dtype, ops, _rnd=_rnd):
+    """every GEMM-family launch of `ops` ((descr, shape, epi) as recorded) with its variant, epilogue and -- for convs -- its real
+    (B, H, W, Cin) geometry, against fp32 torch (_close) -> (launches checked, set of variants)"""
+    from imagharmony_amd import lib as L
+    from imagharmony_amd.attention_processor import fold_ln
     variants = set()
     n_checked = 0
-    for descr, shape, epi in ops:
+    for i, (descr, shape, epi) in enumerate(ops):
+        if i % 50 == 49:
+            print(f"  {i + 1} / {len(ops)} launches", flush=True)
         if "dual" in epi:
             (M1, N1, K1, f1), (M2, N2, K2, f2) = epi["dual"]
             x = _rnd((M1, K1), dtype, 1)
@@ -445,7 +476,7 @@ def test_every_gemm_and_conv_variant_of_the_benchmarked_forward(dtype):
             if up:
                 xin = F.interpolate(xin, scale_factor=2.0, mode="nearest")
             w4 = w.float().view(N, 3, 3, Cin).permute(0, 3, 1, 2)
-            acc = F.conv2d(xin, w4, stride=stride, padding=1).permute(0, 2, 3, 1).reshape(M, N)
+            acc = _conv3x3_ref(xin, w4, stride).permute(0, 2, 3, 1).reshape(M, N)
             ref = _ref_epilogue(acc, epi, bias, residual, rowadd, L)
             _close(y.view(M, N), ref, dtype, f"{descr} {shape} {epi}")
         else:
@@ -482,8 +513,88 @@ def test_every_gemm_and_conv_variant_of_the_benchmarked_forward(dtype):
         ctx.free(y)
         n_checked += 1
         del x, w
-    print(f"{dtype}: {n_checked} distinct launches checked; variants (bm, bn, splits, conv): {sorted(variants, key=str)}")
-    assert n_checked >= 35
+    return n_checked, variants
+
+
+_ALL = None
+
+
+def _all_launches():
+    global _ALL
+    if _ALL is None:
+        from forward_recordings import RESOLUTIONS
+        _ALL = _distinct_launches(RESOLUTIONS)
+    return _ALL
+
+
+_HALO = (7128, 7564, 7328, 7428, 7256, 7356)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_every_launch_of_the_forward_at_every_resolution(dtype):
+    """the union over the forwards at every resolution of tests/forward_recordings.py (1024^2; the 1152x896, 1344x768, 1536x640,
+    2048x512 and 832x1216 buckets both ways round; 1024^2 at 2 and 4 latents) of the distinct launches, each once: GEMM / conv / dual
+    launches as the benchmarked-forward sweep checks them (convs with their real (B, H, W) -- the tuned halo convs run at 64x256 and
+    256x64 too), self-attention with its real (B, heads, Lq, Lk, Lk_pad) -- the ragged deepest level masks the keys past 988 / 1008 of
+    1024 -- and the fused cross-attention against fp32 SDPA, the stand-alone LayerNorm of the unfused blocks against F.layer_norm"""
+    from conftest import ref_row_stats as rrs
+    from imagharmony_amd import lib as L
+    from imagharmony_amd.attention_processor import fold_ln
+    from imagharmony_amd.ctx import Ctx
+    from test_gpu_ops import _attention_self_case, _fused_cross_attention_case
+    ops, attn, xattn, lns = _all_launches()
+    halo_geoms = {shape[4][1:3] for _, shape, epi in ops if shape is not None and shape[3] and epi["cfg"][0] in _HALO}
+    assert halo_geoms & {(64, 256), (256, 64)}, halo_geoms          # a tuned halo conv at a geometry other than 128 x 128
+    assert {(988, 1024), (1008, 1024)} <= {(a[3], a[4]) for _, a, _ in attn}
+    assert any(d == "self.to_qk+v^T" and not e.get("ln_pre") and e["dual"][0][3] == 0 for d, _, e in ops)   # the ragged projections
+    assert lns, "no stand-alone LayerNorm launch recorded"
+    ctx = Ctx(DEV, dtype)
+    n_gemm, variants = _check_gemm_launches(ctx, dtype, ops, _rnd=_rnd_dev)
+    for descr, (B, H, Lq, Lk, Lk_pad), epi in attn:
+        assert Lq == Lk_pad and not epi["Lk2"]
+        _attention_self_case(L, dtype, B, H, Lq, Lk)
+    for descr, (B, H, Lq, Lk, Lk_pad), epi in xattn:
+        out = _fused_cross_attention_case(L, ctx, dtype, B, H, Lq, Lk, epi["Lk2"], 2 if epi["ln"] else 0, rrs, fold_ln)
+        ctx.free(out)
+    for rows, C_ in lns:
+        x = (_rnd((rows, C_), dtype, 9).float() * 1.5 + 2.0).to(dtype)
+        norm = _rand_norm(C_)
+        g, b = norm.weight.detach().to(DEV, dtype), norm.bias.detach().to(DEV, dtype)
+        y = ctx.layernorm(x, g, b, 1e-5)
+        _close(y, F.layer_norm(x.float(), (C_,), g.float(), b.float(), 1e-5), dtype, f"layernorm {rows} x {C_}")
+        ctx.free(y)
+    print(f"{dtype}: {n_gemm} distinct GEMM / conv / dual launches, {len(attn)} self-attention "
+          f"{sorted(a for _, a, _ in attn)}, {len(xattn)} fused cross-attention, {len(lns)} LayerNorm {lns} checked; "
+          f"variants (bm, bn, splits, conv): {sorted(variants, key=str)}; halo conv geometries {sorted(halo_geoms)}")
+    assert n_gemm >= 400
+
+
+# the official SDXL buckets the 1024^2 test does not reach: generic tiles, the stand-alone LayerNorm, the ragged self-attention (1152x896:
+# 1008 tokens at the deepest level; 832x1216: 988 and 3952 at levels 2 / 1)
+@pytest.mark.parametrize("Hl,Wl", [(112, 144), (104, 152)])
+def test_full_sdxl_forward_non_square_bucket_matches_cpu_oracle(sdxl_pair, Hl, Wl):
+    """as test_full_sdxl_forward_matches_cpu_oracle (same weights, conditioning and bound TOL_FWD), at a non-square latent; measured
+    bf16 1.15e-2 / fp16 1.41e-3 at 1152x896, bf16 1.33e-2 / fp16 1.67e-3 at 832x1216 (the 1024^2 forward: 1.15e-2 / 1.30e-3)"""
+    hu, ou = sdxl_pair
+    pe, ne, po, no = _cond()
+    ehs = torch.cat([ne, pe], 0)
+    text = torch.cat([no, po], 0)
+    ids = torch.tensor([[8 * Hl, 8 * Wl, 0, 0, 8 * Hl, 8 * Wl]] * 2, dtype=torch.float32)
+    x = torch.randn(1, 4, Hl, Wl, generator=torch.Generator("cpu").manual_seed(3)).repeat(2, 1, 1, 1)
+    t = torch.tensor(481.0)
+    with torch.no_grad():
+        ref = ou(x, t, ehs, added_cond_kwargs={"text_embeds": text, "time_ids": ids})[0]
+    assert torch.isfinite(ref).all()
+    for dtype in (torch.bfloat16, torch.float16):
+        u = hu if dtype == torch.bfloat16 else _as_fp16(hu)
+        y = u(x.to(DEV), t, ehs.to(DEV, dtype), added_cond_kwargs={"text_embeds": text.to(DEV, dtype), "time_ids": ids.to(DEV)})[0]
+        r = rel_rms(y.float().cpu(), ref)
+        print(f"full SDXL forward {8 * Hl}x{8 * Wl} {dtype}: rel-rms vs fp32 CPU oracle {r:.3e} (bound {TOL_FWD[dtype]:.1e})")
+        record_parity(f"unet_forward.cfg2_b2_t4_{Hl}x{Wl}.{str(dtype).split('.')[-1]}", r, TOL_FWD[dtype])
+        assert y.shape == (2, 4, Hl, Wl) and torch.isfinite(y).all() and r < TOL_FWD[dtype], f"{dtype}: rel-rms {r:.3e}"
+        if dtype == torch.float16:
+            del u
+            torch.cuda.empty_cache()
 
 
 def test_every_tuning_table_entry_vs_matmul():

@@ -64,10 +64,21 @@ def test_unet_forward_matches_oracle(dtype):
 
 def test_unet_recorded_plan_equals_eager():
     """the recorded plan / hipGraph replay computes exactly what the eager per-op path does"""
+    _recorded_plan_equals_eager(32, 32)
+
+
+def test_unet_recorded_plan_equals_eager_non_square_ragged():
+    """the same at 28x36: 14x18 = 252 and 7x9 = 63 tokens at levels 1 / 2 (ragged self-attention, stand-alone LayerNorm), whose
+    zero-padded row slab is shared by every ragged layer of the plan and must stay zero across a run, a capture and a replay"""
+    _recorded_plan_equals_eager(28, 36)
+
+
+def _recorded_plan_equals_eager(Hl, Wl):
     from imagharmony_amd.ctx import Ctx
     dtype = torch.bfloat16
     ou, hu, ocfg = build_pair(dtype)
     x, ehs, te, ids = inputs(ocfg)
+    x = det_randn((2, 4, Hl, Wl), 3)
     y_eager = hu(x.to(DEV), torch.tensor(321.0), ehs.to(DEV, dtype),
                  added_cond_kwargs={"text_embeds": te.to(DEV, dtype), "time_ids": ids.to(DEV)})[0]
     pre = Ctx(DEV, dtype)
@@ -75,16 +86,16 @@ def test_unet_recorded_plan_equals_eager():
     st.t_value = torch.full((2,), 321.0, device=DEV)
     st.latents = x.to(DEV).float().contiguous()
     rec = Ctx(DEV, dtype, record=True)
-    out = hu.emit_forward(rec, st, 2, 32, 32, cfg_dup=False)
+    out = hu.emit_forward(rec, st, 2, Hl, Wl, cfg_dup=False)
     rec.run()
     torch.cuda.synchronize()
-    y_plan = out.view(2, 32, 32, 4).permute(0, 3, 1, 2).clone()
+    y_plan = out.view(2, Hl, Wl, 4).permute(0, 3, 1, 2).clone()
     assert torch.equal(y_plan, y_eager)
     out.zero_()
     rec.capture()
     rec.replay()
     torch.cuda.synchronize()
-    assert torch.equal(out.view(2, 32, 32, 4).permute(0, 3, 1, 2), y_eager)
+    assert torch.equal(out.view(2, Hl, Wl, 4).permute(0, 3, 1, 2), y_eager)
 
 
 @pytest.mark.parametrize("dtype,B,T", [(torch.float16, 4, 16), (torch.bfloat16, 2, 32), (torch.bfloat16, 1, 4)])
@@ -119,3 +130,24 @@ def test_unet_forward_with_standalone_layernorm(dtype, monkeypatch):
     r1, r2, r12 = rel_rms(y_fold, ref), rel_rms(y_ln, ref), rel_rms(y_fold, y_ln)
     print(f"unet tiny {dtype}: folded-LN {r1:.3e}, stand-alone LN {r2:.3e}, between them {r12:.3e}")
     assert r1 < TOL[dtype] and r2 < TOL[dtype] and r12 < TOL[dtype]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("B", [1, 2])
+def test_unet_forward_non_square_ragged_token_counts(dtype, B):
+    """non-square latents whose token counts are ragged to 64 and to 16 at levels 1 / 2: 24x40 (240 / 60 tokens), 40x24, 28x36
+    (252 / 63), 36x28 -- the ragged self-attention with its zero-padded row slabs and the stand-alone LayerNorm -- against the oracle,
+    same bound as the square forward (measured bf16 1.40-1.44e-2, fp16 1.77-1.85e-3, as at 32x32)"""
+    ou, hu, ocfg = build_pair(dtype)
+    _, ehs, te, _ = inputs(ocfg, B=B)
+    for Hl, Wl in ((24, 40), (40, 24), (28, 36), (36, 28)):
+        x = det_randn((B, 4, Hl, Wl), 3)
+        ids = torch.tensor([[Hl * 8, Wl * 8, 0, 0, Hl * 8, Wl * 8]], dtype=torch.float32).repeat(B, 1)
+        with torch.no_grad():
+            ref = ou(x, torch.tensor(500.0), ehs, added_cond_kwargs={"text_embeds": te, "time_ids": ids})[0]
+        y = hu(x.to(DEV), torch.tensor(500.0), ehs.to(DEV, dtype),
+               added_cond_kwargs={"text_embeds": te.to(DEV, dtype), "time_ids": ids.to(DEV)})[0]
+        assert y.shape == ref.shape == (B, 4, Hl, Wl)
+        r = rel_rms(y.float().cpu(), ref)
+        print(f"unet tiny {dtype} B={B} {Hl}x{Wl}: rel-rms {r:.3e}")
+        assert torch.isfinite(y).all() and r < TOL[dtype], f"{Hl}x{Wl}: rel-rms {r:.3e}"

@@ -236,3 +236,47 @@ def test_pipeline_output_types_with_vae():
     with torch.no_grad():
         ref = oracle_post(oracle_decode(ov, lat.cpu()), "np")
     assert abs(arr - ref).mean() < 2e-2
+
+
+@pytest.mark.parametrize("shape", [(20, 20), (18, 18), (24, 40)])
+def test_vae_decode_ragged_token_counts_match_oracle(shape):
+    """mid-block attention over token counts that are not a multiple of 64 (20x20 = 400), of 16 (18x18 = 324) and a non-square 24x40
+    (960): the keys are padded to 64 (16-bit path) / 16 (fp32 path) in zero-filled probability and V^T buffers.  Untiled, against the
+    oracle with the bounds of the square tests: native bf16 3e-2 / fp16 8e-3, fp32 mode 1e-4 (measured 9.3-9.7e-3 / 1.2e-3 / 9e-6, as at
+    32x32)"""
+    from imagharmony_amd.vae import decode_latents
+    h, w = shape
+    lat = det_randn((2, 4, h, w), 11) * 0.13025 * 3.0
+    for dtype, tol in ((torch.bfloat16, 3e-2), (torch.float16, 8e-3)):
+        ov, hv = build_pair(dtype)
+        with torch.no_grad():
+            ref = oracle_decode(ov, lat)
+        img = decode_latents(hv, lat.to(DEV), precision="native")
+        assert img.shape == ref.shape == (2, 3, 8 * h, 8 * w) and torch.isfinite(img).all()
+        r = rel_rms(img.cpu(), ref)
+        print(f"vae tiny {dtype} native {h}x{w}: rel-rms {r:.3e}")
+        assert r < tol, (dtype, r)
+    ov, hv = _rounded_pair(torch.float16)
+    with torch.no_grad():
+        ref = oracle_decode(ov, lat)
+    img = decode_latents(hv, lat.to(DEV))
+    assert hv.precision_for() == "fp32" and img.shape == ref.shape and torch.isfinite(img).all()
+    r = rel_rms(img.cpu(), ref)
+    print(f"vae tiny fp32 mode {h}x{w}: rel-rms {r:.3e}")
+    assert r < 1e-4, r
+
+
+def test_vae_tiled_decode_with_ragged_edge_tiles_matches_oracle_tiled():
+    """a non-square 42x38 latent in tiles of 32 latent pixels, 24 apart: 32x32, 32x14 (448 tokens), 18x32 (576) and an 18x14 corner
+    (252 tokens: not a multiple of 16) -- native bf16 and fp32 mode against the oracle's tiled decode (measured 9.1e-3 / 8.4e-6)"""
+    from imagharmony_amd.vae import decode_latents
+    lat = det_randn((1, 4, 42, 38), 12) * 0.13025 * 3.0
+    for (ov, hv), tol in ((build_pair(torch.bfloat16), 3e-2), (_rounded_pair(torch.float16), 1e-4)):
+        ov.enable_tiling(); hv.enable_tiling()
+        with torch.no_grad():
+            ref = oracle_decode(ov, lat)
+        img = decode_latents(hv, lat.to(DEV))
+        assert img.shape == ref.shape == (1, 3, 336, 304) and torch.isfinite(img).all()
+        r = rel_rms(img.cpu(), ref)
+        print(f"vae tiny tiled 42x38 ({hv.precision_for()}): rel-rms {r:.3e}")
+        assert r < tol, r

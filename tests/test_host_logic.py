@@ -430,3 +430,133 @@ def test_inline_asm_vmem_stores_carry_their_hazard_nop():
             found += 1
             assert "s_nop" in m.group(1), f"{f}: inline-asm store without its hazard nop: {m.group(1)[:80]}"
     assert found >= 1
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the full-width forward at every accepted resolution (tests/forward_recordings.py), dry-recorded: what the GPU sweep checks
+# ------------------------------------------------------------------------------------------------------------
+_WS = (1464, 2464, 24128, 23256, 22128)
+_HALO = (7128, 7564, 7328, 7428, 7256, 7356)
+
+
+def _launcher_refusal(shape, epi):
+    """the argument checks of gemm_launch / gemm_w16_launch / gemm_pp_launch / conv_halo_launch (csrc) for one recorded launch, restated:
+    None when the launcher accepts it, else the reason"""
+    from imagharmony_amd import lib as L
+    M, N, K, conv, geom = shape
+    bm, bn, sp = epi["cfg"]
+    fl = epi["flags"]
+    ln = fl & (L.GF_LN_ROW | L.GF_LN_COL)
+    extras = epi["bias"] or epi["residual"] or epi["rowadd"] or epi.get("x2") or epi.get("yt")
+    if K % 64 or (conv and (geom[3] % 64 or K != 9 * geom[3])):
+        return "K / Cin not a multiple of 64"
+    if fl & L.GF_GEGLU and N % 16:
+        return "GEGLU with N % 16"
+    if ln and (sp > 1 or conv or (bm >= 256 and not (bm in _WS + (26256,) and fl & L.GF_LN_ROW))):
+        return "folded LayerNorm on a variant without it"
+    if epi.get("gn_in") is not None and not (conv and bm in _HALO):
+        return "fused GroupNorm front end off the LDS-halo conv"
+    if epi.get("x2") and (conv and bm not in _HALO or not conv and (not (bm <= 128 or bm in _WS) or fl & (ln | L.GF_VT_PERM))):
+        return "two-source operand on a variant without it"
+    if epi.get("yt"):
+        rows = 256 if bm == 23256 else 128 if bm in (24128, 22128) else 64
+        if bm not in _WS or not (bn == 160 or (bm, bn) == (23256, 128)) or fl != L.GF_LN_ROW or epi["residual"] or epi["rowadd"] \
+                or sp > 1 or M % rows or N % bn:
+            return "transposed V^T store"
+    if bm == 26256:
+        if conv or not fl & L.GF_LN_ROW or fl & ~(L.GF_LN_ROW | L.GF_GEGLU) or not epi["ln_pre"] or extras or sp > 1 \
+                or epi.get("stats_out") or epi.get("gn_out") or M % 256 or N % 320:
+            return "sixteen-wave tile"
+    elif bm in (8256, 9128, 9256):
+        if conv or sp > 1 or fl & (ln | L.GF_VT_PERM):
+            return "ping-pong tile"
+    elif bm in _HALO:
+        if not conv or geom[4] != 1 or sp > 1 or bn not in (320, 160, 80) or (bn == 80 and bm not in (7128, 7256)) \
+                or (bm in (7328, 7428, 7256, 7356) and bn == 320):
+            return "LDS-halo conv"
+    elif conv and bm in (8256, 9128, 9256, 26256):
+        return "Linear-only variant on a conv"
+    return None
+
+
+@pytest.fixture(scope="module")
+def sdxl_recordings():
+    from forward_recordings import RESOLUTIONS, record_forward, sdxl_unet_meta
+    u = sdxl_unet_meta()
+    return u, {r: record_forward(u, *r) for r in RESOLUTIONS}
+
+
+def test_full_width_forward_records_at_every_resolution(sdxl_recordings):
+    """every resolution of the GPU sweep records (832x1216 / 1216x832: 988 tokens at the deepest level, not a multiple of 16 -- the
+    ragged self-attention pads each batch's rows to a 64-row slab), with the launch families that make it differ from 1024^2"""
+    from imagharmony_amd import lib as L
+    _, recs = sdxl_recordings
+    for (S, Hl, Wl), ctx in recs.items():
+        kinds = {t[1] for t in ctx.tags}
+        assert L.OP_GEMM in kinds and L.OP_ATTN in kinds and L.OP_XATTN in kinds, (S, Hl, Wl)
+        attn = {t[5] for t in ctx.tags if t[1] == L.OP_ATTN}
+        deep = (2 * S, 20, (Hl // 4) * (Wl // 4))
+        assert any(a[:2] == deep[:2] and a[3] == deep[2] for a in attn), (S, Hl, Wl, attn)
+        ragged = deep[2] % 64 != 0
+        assert any(t[2] == "self.pad_rows" for t in ctx.tags) == ragged, (S, Hl, Wl)
+        assert any(t[1] == L.OP_LAYERNORM for t in ctx.tags) == ragged, (S, Hl, Wl)      # BasicTransformerBlock.fused needs L % 64 == 0
+        for a in attn:
+            B, H, Lq, Lk, Lk_pad = a
+            assert Lk <= Lk_pad == Lq and Lk_pad % 64 == 0 and Lk_pad - Lk < 64
+    assert {(a[3], a[4]) for a in (t[5] for t in recs[(1, 104, 152)].tags if t[1] == L.OP_ATTN)} >= {(988, 1024), (3952, 3968)}
+    assert {(a[3], a[4]) for a in (t[5] for t in recs[(1, 112, 144)].tags if t[1] == L.OP_ATTN)} >= {(1008, 1024)}
+    # 2048x512 shares (M, N, K) with 1024^2, so the tuned halo convs run there at another H x W
+    halo = {t[5][4][:3] for t in recs[(1, 64, 256)].tags if t[1] == L.OP_GEMM and t[5] is not None and t[5][3] and t[6]["cfg"][0] in _HALO}
+    assert (2, 64, 256) in halo, halo
+
+
+def test_unsupported_latent_is_refused_before_any_launch():
+    """sides that are not multiples of 4 (diffusers' forward_upsample_size interpolation is not implemented): an ImhError from the
+    emit_forward guard, with no launch of the forward recorded"""
+    from imagharmony_amd import lib as L
+    from imagharmony_amd.ctx import Ctx
+    from forward_recordings import sdxl_unet_meta
+    u = sdxl_unet_meta()
+    ctx = Ctx("cpu", torch.bfloat16, record=True, dry=True)
+    st = u.prepare_conditioning(ctx, torch.zeros(2, 81, 2048), torch.zeros(2, 1280), torch.zeros(2, 6))
+    st.t_value = torch.zeros(2)
+    st.latents = torch.zeros(1, 4, 34, 40)
+    n0 = len(ctx.tags)
+    with pytest.raises(L.ImhError, match="multiples of 4"):
+        u.emit_forward(ctx, st, 1, 34, 40, cfg_dup=True)
+    assert len(ctx.tags) == n0
+
+
+def test_every_recorded_launch_gets_a_variant_its_launcher_accepts(sdxl_recordings):
+    """the variant Ctx._config picked for every GEMM / conv launch of every recorded resolution is one the C launcher accepts with that
+    launch's epilogue (a tuning entry is keyed by shape only: another resolution or batch whose (M, N, K) coincides inherits it)"""
+    from imagharmony_amd import lib as L
+    _, recs = sdxl_recordings
+    n = 0
+    for r, ctx in recs.items():
+        for (tag, kind, descr, fl, by_, shape, epi) in ctx.tags:
+            if kind != L.OP_GEMM or shape is None:
+                continue
+            why = _launcher_refusal(shape, epi)
+            assert why is None, f"{r} {descr} {shape} {epi}: {why}"
+            n += 1
+    assert n > 5000
+
+
+def test_sixteen_wave_table_entry_falls_back_for_launches_it_cannot_run():
+    """Ctx._variant_ok: a 26256 x 320 table entry is used only for launches gemm_w16_launch accepts -- row-form folded LayerNorm with
+    handed-over statistics, no bias / residual / row-add, whole 256 x 320 tiles; any other launch of that (M, N, K) gets the heuristic"""
+    from imagharmony_amd import lib as L
+    from imagharmony_amd.ctx import Ctx
+    ctx = Ctx("cpu", torch.bfloat16, record=True, dry=True)
+    for (M, N, K), ok in (((2048, 10240, 1280), True), ((2000, 10240, 1280), False), ((2048, 10000, 1280), False)):
+        x, w = torch.zeros(M, K, dtype=torch.bfloat16), torch.zeros(N, K, dtype=torch.bfloat16)
+        st = (torch.zeros(M, 16, 2), 16)
+        ctx.tuning[(M, N, K, 0, 1)] = (26256, 320, 1)
+        ln = (torch.zeros(N), torch.zeros(N), 1e-5, st)
+        a = ctx.gemm(x, w, flags=L.GF_LN_ROW | L.GF_GEGLU, ln=ln, _args_only=True)[0]
+        assert (a.bm == 26256) == ok, (M, N, a.bm)
+        for kw in (dict(bias=torch.zeros(N, dtype=torch.bfloat16)), dict(residual=torch.zeros(M, N, dtype=torch.bfloat16))):
+            a = ctx.gemm(x, w, flags=L.GF_LN_ROW, ln=ln, _args_only=True, **kw)[0]
+            assert a.bm != 26256 and _launcher_refusal((M, N, K, 0, None), dict(
+                cfg=(a.bm, a.bn, a.splits), flags=L.GF_LN_ROW, bias="bias" in kw, residual="residual" in kw, rowadd=False, ln_pre=True)) is None
