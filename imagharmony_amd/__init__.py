@@ -10,8 +10,15 @@ __version__ = "0.1.0"
 __all__ = ["IPAdapter", "IPAdapterPlus", "IPAdapterPlusXL", "IPAdapterXL", "IPAdapterFull"]
 
 
+# the pipelines, lazily too: text-to-image (custom_pipelines.py) and image-to-image (diffusers' SDXL img2img call surface)
+_PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline")
+
+
 def __getattr__(name):
     if name in __all__:
         from . import ip_adapter
         return getattr(ip_adapter, name)
+    if name in _PIPELINES:
+        from . import pipeline
+        return getattr(pipeline, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

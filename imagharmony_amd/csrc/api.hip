@@ -50,7 +50,7 @@ static GemmParams to_gemm(const imh_gemm_args* a) {
     p.M = a->M; p.N = a->N; p.K = a->K;
     p.ldx = a->ldx; p.ldw = a->ldw; p.ldy = a->ldy; p.ldr = a->ldr; p.ldra = a->ldra > 0 ? a->ldra : a->N;
     p.rows_per_batch = a->rows_per_batch; p.splits = a->splits; p.flags = a->flags;
-    p.H = a->H; p.Wd = a->Wd; p.Cin = a->Cin; p.Ho = a->Ho; p.Wo = a->Wo; p.stride = a->stride; p.up = a->up;
+    p.H = a->H; p.Wd = a->Wd; p.Cin = a->Cin; p.Ho = a->Ho; p.Wo = a->Wo; p.stride = a->stride; p.up = a->up; p.pad_lo = a->pad == 1 ? 0 : 1;
     p.px = p.py = 1; p.tmx = p.tny = 0; p.xcd = a->xcd;
     p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes;
     p.early_res = g_ws_early;
@@ -94,12 +94,29 @@ static int do_gemm(const imh_gemm_args* a, hipStream_t s) {
     if (a->conv) {
         if (p.stride != 1 && p.stride != 2) { set_error("conv3x3: stride must be 1 or 2"); return IMH_ERR_ARG; }
         if (p.up != 0 && p.up != 1) { set_error("conv3x3: up must be 0 or 1"); return IMH_ERR_ARG; }
+        if (a->pad != 0 && a->pad != 1) { set_error("conv3x3: pad must be 0 or 1"); return IMH_ERR_ARG; }
+        if (a->pad == 1) {
+            // right / bottom padding (Downsample2D(padding=0)): stride 2 without upsampling, on the variants whose implicit-GEMM loaders
+            // take pad_lo -- the LDS-halo conv3x3 (stride 1 only), the ping-pong and the sixteen-wave Linear forms do not
+            if (p.stride != 2 || p.up || p.H < 2 || p.Wd < 2) {
+                set_error("conv3x3: pad mode 1 needs stride 2, up 0 and an input of at least 2 x 2 (stride=%d up=%d H=%d W=%d)", p.stride, p.up, p.H, p.Wd);
+                return IMH_ERR_ARG;
+            }
+            if (bm == 7128 || bm == 7564 || bm == 7328 || bm == 7428 || bm == 7256 || bm == 7356 || bm == 8256 || bm == 9128 || bm == 9256 ||
+                bm == 26256) {
+                set_error("conv3x3: pad mode 1 is not implemented by variant %d x %d", bm, bn);
+                return IMH_ERR_ARG;
+            }
+        }
         const int Hv = p.H << p.up, Wv = p.Wd << p.up;
-        if (p.Ho != (Hv + 2 - 3) / p.stride + 1 || p.Wo != (Wv + 2 - 3) / p.stride + 1) {
-            set_error("conv3x3: output size %dx%d inconsistent with input %dx%d up=%d stride=%d", p.Ho, p.Wo, p.H, p.Wd, p.up, p.stride);
+        const int span = a->pad == 1 ? 1 : 2;              // padded input minus the 3-tap window: (H + pad_total - 3)
+        if (p.Ho != (Hv + span - 3) / p.stride + 1 || p.Wo != (Wv + span - 3) / p.stride + 1 || p.Ho <= 0 || p.Wo <= 0) {
+            set_error("conv3x3: output size %dx%d inconsistent with input %dx%d up=%d stride=%d pad=%d", p.Ho, p.Wo, p.H, p.Wd, p.up, p.stride, a->pad);
             return IMH_ERR_SHAPE;
         }
         if (p.M % (p.Ho * p.Wo) != 0) { set_error("conv3x3: M must be B*Ho*Wo"); return IMH_ERR_SHAPE; }
+    } else if (a->pad) {
+        set_error("gemm: pad is a conv3x3 field (conv == 0)"); return IMH_ERR_ARG;
     }
     return gemm_launch(p, a->dtype, a->conv, bm, bn, s);
 }
@@ -292,6 +309,9 @@ int imh_f32(int op, const imh_f32_args* a, void* stream) {
     p.conv = a->conv; p.H = a->H; p.Wd = a->Wd; p.Cin = a->Cin; p.Ho = a->Ho; p.Wo = a->Wo; p.up = a->up;
     p.B = a->B; p.HW = a->HW; p.C = a->C; p.groups = a->groups; p.nblk = a->nblk; p.silu = a->silu;
     p.eps = a->eps; p.scale = a->scale;
+    if (a->pad != 0 && a->pad != 1) { set_error("imh_f32: pad must be 0 or 1"); return IMH_ERR_ARG; }
+    p.stride = a->stride > 0 ? a->stride : 1; p.pad_lo = a->pad == 1 ? 0 : 1;
+    p.add_a = a->add_a; p.add_b = a->add_b;
     return f32_launch(op, p, (hipStream_t)stream);
 }
 

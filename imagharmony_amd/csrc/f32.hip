@@ -2,7 +2,7 @@
 // upcasts the SDXL VAE to fp32 before decoding because it overflows in fp16 (:366-372, `needs_upcasting` / `upcast_vae`), so a decode
 // that is to be "like the reference" keeps fp32 activations, fp32 weights and fp32 arithmetic.  Everything here is fp32 in, fp32 out:
 //
-//   f32_gemm_kernel      Y[M, N] = X[M, K] W[N, K]^T (+ bias[n]) (+ residual[m, n]); conv == 1: 3x3 convolution, padding 1, stride 1,
+//   f32_gemm_kernel      Y[M, N] = X[M, K] W[N, K]^T (+ bias[n]) (+ residual[m, n]); conv == 1: 3x3 convolution, stride 1 | 2,
 //                        optional fused nearest x2 upsampling of the input, as an implicit GEMM over NHWC input (K = 9 Cin, weights
 //                        packed [Cout][ky][kx][Cin] like the 16-bit kernels').  v_mfma_f32_32x32x2_f32: exact fp32 products, one rounding
 //                        per accumulate (bitwise an fmaf chain, cdna_hip_programming.md 3), 64 FLOP / clk / SIMD = 1/16 of the bf16 rate --
@@ -13,6 +13,9 @@
 //   f32_gn_*             GroupNorm (+ SiLU) in three launches: per (sample, pixel block, group) shifted (sum, M2) -> per (sample, channel)
 //                        (scale, shift) merged in double in a fixed order (Chan) -> y = silu(x scale + shift).  No E[x^2] - mean^2.
 //   f32_softmax_kernel   row softmax of scale * a (the mid-block's single-head attention, materialised scores).
+//   f32_img2img_init_kernel  the img2img initial latents from the encoder's moments: posterior sample, scaling factor and the scheduler's
+//                        add_noise in one pass (imh.h IMH_F32_IMG2IMG_INIT).
+// The conv form also runs stride 2, with padding 1 on every side or on the right / bottom only (the VAE encoder's Downsample2D).
 // Roofline: f32_gemm is MFMA-bound at the fp32 matrix rate (157 TFLOP/s peak); the others are HBM-bound, once per image.
 #include "imh_common.h"
 #include "imh_kernels.h"
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void f32_gemm_kernel(const F32Params p) {
         for (int h = 0; h < 2; ++h) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (p.conv) {
-                const int iy = coy[h] + ky - 1, ix = cox[h] + kx - 1;
+                const int iy = coy[h] * p.stride + ky - p.pad_lo, ix = cox[h] * p.stride + kx - p.pad_lo;
                 if (xok[h] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv)
                     v = *(const f32x4*)(p.X + (((size_t)cb[h] * p.H + (iy >> p.up)) * p.Wd + (ix >> p.up)) * p.Cin + c0 + kq);
             } else if (xok[h]) {
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(256, 3) void f32_gemm_x3_kernel(const F32Params p) 
             const int tap = k0 / p.Cin;
             const int c0 = k0 - tap * p.Cin;
             const int ky = tap / 3, kx = tap - ky * 3;
-            const int iy = coy + ky - 1, ix = cox + kx - 1;
+            const int iy = coy * p.stride + ky - p.pad_lo, ix = cox * p.stride + kx - p.pad_lo;
             if (xok && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv)
                 xs = p.X + (((size_t)cb * p.H + (iy >> p.up)) * p.Wd + (ix >> p.up)) * p.Cin + c0 + kq;
         } else if (xok) {
@@ -401,14 +404,40 @@ __global__ __launch_bounds__(256) void f32_softmax_kernel(const F32Params p) {
     for (int i = threadIdx.x; i < p.N; i += 256) y[i] = __expf((a[i] - mx) * p.scale) * inv;
 }
 
+// diffusers DiagonalGaussianDistribution.sample + scaling_factor + scheduler.add_noise (StableDiffusionXLImg2ImgPipeline.prepare_latents),
+// fp32: one thread per latent element e of sample s, channel c, pixel q (NCHW [B, 4, HW]); the moments are NHWC [M, HW, 8]
+__global__ void f32_img2img_init_kernel(const F32Params p) {
+    const size_t total = (size_t)p.B * 4 * p.HW;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(e % p.HW);
+        const int c = (int)((e / p.HW) & 3);
+        const int s = (int)(e / ((size_t)4 * p.HW));
+        const float* mo = p.X + ((size_t)(s % p.M) * p.HW + q) * 8;
+        const float mean = mo[c];
+        const float logvar = fminf(fmaxf(mo[4 + c], -30.0f), 20.0f);
+        const float n1 = p.W[((size_t)(s % p.N) * 4 + c) * p.HW + q];
+        const float z = p.scale * (mean + expf(0.5f * logvar) * n1);
+        p.Y[e] = p.add_a * z + p.add_b * p.residual[e];
+    }
+}
+
 int f32_launch(int op, const F32Params& p, hipStream_t stream) {
     switch (op) {
     case 0: {                                            // GEMM / conv3x3
         if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.K % F_BK != 0) { set_error("f32 gemm: M, N > 0 and K %% 16 == 0 (M=%d N=%d K=%d)", p.M, p.N, p.K); return IMH_ERR_SHAPE; }
-        if (p.conv && (p.Cin % F_BK != 0 || p.K != 9 * p.Cin || p.Ho != (p.H << p.up) || p.Wo != (p.Wd << p.up) || p.M % (p.Ho * p.Wo) != 0)) {
-            set_error("f32 conv3x3: stride 1, Cin %% 16 == 0, K == 9 Cin, output = (upsampled) input size (Cin=%d K=%d H=%d W=%d up=%d Ho=%d Wo=%d M=%d)",
-                      p.Cin, p.K, p.H, p.Wd, p.up, p.Ho, p.Wo, p.M);
-            return IMH_ERR_SHAPE;
+        if (p.conv) {
+            // stride 1: padding 1 on every side, output = the (upsampled) input; stride 2 (no upsampling): padding 1 on every side,
+            // Ho = (H - 1) / 2 + 1, or right / bottom only (pad_lo 0, H >= 2), Ho = (H - 2) / 2 + 1
+            const bool s1 = p.stride == 1 && p.pad_lo == 1 && p.Ho == (p.H << p.up) && p.Wo == (p.Wd << p.up);
+            const int span = p.pad_lo ? 2 : 1;
+            const bool s2 = p.stride == 2 && !p.up && p.H >= 2 - p.pad_lo && p.Wd >= 2 - p.pad_lo &&
+                            p.Ho == (p.H + span - 3) / 2 + 1 && p.Wo == (p.Wd + span - 3) / 2 + 1;
+            if (p.Cin % F_BK != 0 || p.K != 9 * p.Cin || !(s1 || s2) || p.Ho <= 0 || p.Wo <= 0 || p.M % (p.Ho * p.Wo) != 0) {
+                set_error("f32 conv3x3: Cin %% 16 == 0, K == 9 Cin, stride 1 (pad 0, output = (upsampled) input size) or stride 2 (up 0, "
+                          "Ho = (H - 1) / 2 + 1 with pad 0, (H - 2) / 2 + 1 with pad 1) (Cin=%d K=%d H=%d W=%d up=%d stride=%d pad=%d Ho=%d Wo=%d M=%d)",
+                          p.Cin, p.K, p.H, p.Wd, p.up, p.stride, 1 - p.pad_lo, p.Ho, p.Wo, p.M);
+                return IMH_ERR_SHAPE;
+            }
         }
         if (!p.conv && (p.ldx & 3)) { set_error("f32 gemm: ldx must be a multiple of 4"); return IMH_ERR_SHAPE; }
         if (p.ldw & 3) { set_error("f32 gemm: ldw must be a multiple of 4"); return IMH_ERR_SHAPE; }
@@ -438,6 +467,17 @@ int f32_launch(int op, const F32Params& p, hipStream_t stream) {
         if (p.M <= 0 || p.N <= 0) { set_error("f32 softmax: empty"); return IMH_ERR_SHAPE; }
         hipLaunchKernelGGL(f32_softmax_kernel, dim3(p.M), dim3(256), 0, stream, p);
         return check_launch("f32_softmax_kernel");
+    case 5: {
+        if (!p.X || !p.W || !p.Y || !p.residual || p.B <= 0 || p.HW <= 0 || p.M <= 0 || p.N <= 0) {
+            set_error("f32 img2img init: X (moments), W (posterior noise), residual (noise), Y and B, HW, M, N > 0 (B=%d HW=%d M=%d N=%d)",
+                      p.B, p.HW, p.M, p.N);
+            return IMH_ERR_ARG;
+        }
+        const size_t total = (size_t)p.B * 4 * p.HW;
+        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+        hipLaunchKernelGGL(f32_img2img_init_kernel, dim3(blocks), dim3(256), 0, stream, p);
+        return check_launch("f32_img2img_init_kernel");
+    }
     default:
         set_error("imh_f32: unknown op %d", op);
         return IMH_ERR_ARG;

@@ -122,8 +122,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int bid, co
 #pragma unroll
             for (int i = 0; i < RX; ++i) {
                 const int c = stage_chunk_x(stage_row(i, wave, lane), lane);
-                const int iy = coy[i] * p.stride + ky - 1;
-                const int ix = cox[i] * p.stride + kx - 1;
+                const int iy = coy[i] * p.stride + ky - p.pad_lo;
+                const int ix = cox[i] * p.stride + kx - p.pad_lo;
                 const bool ok = cvalid[i] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
                 const size_t pix = ((size_t)cb[i] * p.H + (iy >> p.up)) * p.Wd + (ix >> p.up);
                 const unsigned char* src = ok

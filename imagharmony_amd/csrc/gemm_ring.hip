@@ -105,8 +105,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
 #pragma unroll
             for (int i = 0; i < RX; ++i) {
                 const int c = stage_chunk_x(i * RPR + srow, lane);
-                const int iy = coy[i] * p.stride + ky - 1;
-                const int ix = cox[i] * p.stride + kx - 1;
+                const int iy = coy[i] * p.stride + ky - p.pad_lo;
+                const int ix = cox[i] * p.stride + kx - p.pad_lo;
                 const bool ok = cvalid[i] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
                 const size_t pix = ((size_t)cb[i] * p.H + (iy >> p.up)) * p.Wd + (ix >> p.up);
                 const unsigned char* src = ok
@@ -285,8 +285,8 @@ __global__ __launch_bounds__(512, 2) void gemm_kg2_kernel(const GemmParams p) {
 #pragma unroll
             for (int i = 0; i < RX; ++i) {
                 const int c = stage_chunk_x(stage_row(i, wave, lane), lane);
-                const int iy = coy[i] * p.stride + ky - 1;
-                const int ix = cox[i] * p.stride + kx - 1;
+                const int iy = coy[i] * p.stride + ky - p.pad_lo;
+                const int ix = cox[i] * p.stride + kx - p.pad_lo;
                 const bool ok = cvalid[i] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
                 const size_t pix = ((size_t)cb[i] * p.H + (iy >> p.up)) * p.Wd + (ix >> p.up);
                 const unsigned char* src = ok
@@ -509,8 +509,8 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
                     const int r = (k * NL + pw) * 8 + (lane >> 3);
                     const int c = stage_chunk_x(r, lane);
                     const int Hv = p.H << p.up, Wv = p.Wd << p.up;
-                    const int iy = coy[k] * p.stride + ky - 1;
-                    const int ix = cox[k] * p.stride + kx - 1;
+                    const int iy = coy[k] * p.stride + ky - p.pad_lo;
+                    const int ix = cox[k] * p.stride + kx - p.pad_lo;
                     const bool ok = cvalid[k] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
                     const size_t pix = ((size_t)cb[k] * p.H + (iy >> p.up)) * p.Wd + (ix >> p.up);
                     const unsigned char* src = ok

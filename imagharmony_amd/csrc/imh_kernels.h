@@ -45,8 +45,9 @@ struct GemmParams {
     int rows_per_batch;
     int splits;
     int flags;
-    // implicit-GEMM conv3x3 (pad 1): input H x Wd (virtual size << up), output Ho x Wo
-    int H, Wd, Cin, Ho, Wo, stride, up;
+    // implicit-GEMM conv3x3: input H x Wd (virtual size << up), output Ho x Wo; input row oy * stride + ky - pad_lo (pad_lo = 1: one pixel
+    // on every side, imh_gemm_args.pad 0; pad_lo = 0: right / bottom only, pad 1 -- the VAE encoder's Downsample2D)
+    int H, Wd, Cin, Ho, Wo, stride, up, pad_lo;
     // XCD-aware tile placement (set by the launchers): the 8 XCDs form a px x py grid over the tile space
     int px, py, tmx, tny;
     int xcd;               // requested cell shape (imh_gemm_args.xcd): 0 = cost model, 2 .. 5 = (8,1) (4,2) (2,4) (1,8)
@@ -147,13 +148,15 @@ int layernorm_launch(const NormParams& p, int dtype, hipStream_t stream);
 
 // fp32 (reference-precision) kernels of the VAE decode tail (f32.hip).  op 0: GEMM / conv3x3 (X, W, Y, bias, residual; conv fields);
 // 1: GroupNorm statistics (X [B, HW, C] -> ws [B, nblk, groups, 2]); 2: table (ws, gamma, beta -> Y [B, C, 2]); 3: apply (X, ws = table -> Y);
-// 4: row softmax (X [M, ldx] -> Y [M, ldy], N columns, scale)
+// 4: row softmax (X [M, ldx] -> Y [M, ldy], N columns, scale); 5: img2img initial latents (imh.h IMH_F32_IMG2IMG_INIT)
 struct F32Params {
     const float* X; const float* W; float* Y; const float* bias; const float* residual; const float* gamma; const float* beta; float* ws;
     int M, N, K, ldx, ldw, ldy, ldr;
     int conv, H, Wd, Cin, Ho, Wo, up;
     int B, HW, C, groups, nblk, silu;
     float eps, scale;
+    int stride, pad_lo;          // conv: input row oy * stride + ky - pad_lo (as GemmParams)
+    float add_a, add_b;          // op 5 (img2img initial latents): the add-noise pair
 };
 int f32_launch(int op, const F32Params& p, hipStream_t stream);
 

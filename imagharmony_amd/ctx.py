@@ -212,10 +212,13 @@ class Ctx:
     _HALO = (7128, 7564, 7328, 7428, 7256, 7356)   # LDS-halo conv3x3, stride 1 (7328 / 7428: weight rings; 7256 / 7356: 16 x 16 patch)
 
     @classmethod
-    def _variant_ok(cls, bm, sp, flags, conv, stride, ln_pre, M=0, N=0, extras=False):
+    def _variant_ok(cls, bm, sp, flags, conv, stride, ln_pre, M=0, N=0, extras=False, pad=0):
         """extras: the launch has a bias, residual, row-add, second token source or transposed store (the epilogue inputs the
-        sixteen-wave tile has none of: gemm_w16_launch refuses them, and whole tiles only)"""
+        sixteen-wave tile has none of: gemm_w16_launch refuses them, and whole tiles only); pad: the conv padding mode
+        (imh_gemm_args.pad -- 1, right / bottom only, runs on every conv-capable variant except the LDS-halo kernels)"""
         plain = bm <= 128
+        if pad and (not conv or bm in cls._HALO + cls._PP + cls._W16):
+            return False
         if bm in cls._W16:
             return not conv and sp == 1 and bool(flags & L.GF_LN_ROW) and not flags & ~(L.GF_LN_ROW | L.GF_GEGLU) and bool(ln_pre) \
                 and not extras and M % 256 == 0 and N % 320 == 0
@@ -239,7 +242,7 @@ class Ctx:
             return 0
         return cells
 
-    def _config(self, M, N, K, conv, flags, stride=1, ln_pre=False, up=0, extras=False):
+    def _config(self, M, N, K, conv, flags, stride=1, ln_pre=False, up=0, extras=False, pad=0):
         """tile variant of a launch: the tuning table's entry for the shape if that variant implements the launch's flags
         (folded LayerNorm in either form, V^T permutation, conv stride), else the built-in heuristic -- in ONE place"""
         key = (M, N, K, int(conv))
@@ -249,7 +252,7 @@ class Ctx:
         # 64^2 ResBlock convs of UNet batch 8, which want the LDS-halo form that fuses their GroupNorm)
         cfg = (self.tuning.get(key + (1,)) if ln_pre else self.tuning.get(key + (2,)) if conv and stride == 2
                else self.tuning.get(key + (3,)) if conv and up else None) or self.tuning.get(key)
-        if cfg is not None and self._variant_ok(cfg[0], cfg[2], flags, conv, stride, ln_pre, M, N, extras):
+        if cfg is not None and self._variant_ok(cfg[0], cfg[2], flags, conv, stride, ln_pre, M, N, extras, pad):
             return tuple(cfg)
         bm, bn, sp = C.c_int(), C.c_int(), C.c_int()
         self.lib.imh_gemm_pick_config(M, N, K, C.byref(bm), C.byref(bn), C.byref(sp))
@@ -438,19 +441,23 @@ class Ctx:
         return lds <= 160 * 1024
 
     def conv3x3(self, x, w, bias=None, stride=1, up=0, residual=None, rowadd=None, ldra=0, out=None, cfg=None,
-                descr="conv3x3", gn_groups=0, gn=None, x2=None):
+                descr="conv3x3", gn_groups=0, gn=None, x2=None, pad=0):
         """x: NHWC [B, H, W, Cin]; w: packed [Cout, 9*Cin]; returns NHWC [B, Ho, Wo, Cout]; with gn_groups > 0 (the output is
         a GroupNorm input) -> (y, GnStats or None) as gemm(gn_out=...).
         gn = (table [B, Cin, 2] fp32 from gn_table(), silu) or (GnSpec, silu): the input's GroupNorm (+ SiLU) is applied inside the
         kernel's halo staging (diffusers ResnetBlock2D: norm -> nonlinearity -> conv in one launch) -- with a GnSpec the kernel also builds
         the table itself from the producers' partials (no table launch); x2: the input is the channel concat [x | x2].  Both need the
-        LDS-halo variant (conv_fuses_gn)."""
+        LDS-halo variant (conv_fuses_gn).
+        pad = 1: no padding on the top / left, one zero pixel on the right / bottom (diffusers Downsample2D(padding=0), the VAE
+        encoder's downsamplers; stride 2): Ho = (H - 2) // 2 + 1."""
         self._chk(x, descr + ".x"); self._chk(w, descr + ".w")
         B, H, W, C1 = x.shape
         Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
         Cout = w.shape[0]
         Hv, Wv = H << up, W << up
-        Ho, Wo = (Hv - 1) // stride + 1, (Wv - 1) // stride + 1
+        if pad and (stride != 2 or up or gn is not None or x2 is not None):
+            raise L.ImhError(f"{descr}: pad mode 1 is a plain stride-2 conv (no upsampling, fused GroupNorm or second source)")
+        Ho, Wo = ((Hv - 2) // 2 + 1, (Wv - 2) // 2 + 1) if pad else ((Hv - 1) // stride + 1, (Wv - 1) // stride + 1)
         M, N, K = B * Ho * Wo, Cout, 9 * Cin
         if not x.is_contiguous() or not w.is_contiguous() or w.shape[1] != K:
             raise L.ImhError(f"{descr}: x must be contiguous NHWC and w packed [Cout, 9*Cin]")
@@ -462,7 +469,7 @@ class Ctx:
             out = self.new(B, Ho, Wo, Cout)
         # (the table is keyed by (M, N, K): a stride-2 conv can share its key with a stride-1 conv of another resolution /
         # batch; the LDS-halo kernel is stride-1 only -> _config falls back to the heuristic tile for that one)
-        bm, bn, sp = cfg or self._config(M, N, K, 1, 0, stride=stride, up=up)
+        bm, bn, sp = cfg or self._config(M, N, K, 1, 0, stride=stride, up=up, pad=pad)
         if (gn is not None or x2 is not None) and not self.conv_fuses_gn(M, N, K, stride, up, cfg=(bm, bn, sp)):
             raise L.ImhError(f"{descr}: the fused GroupNorm front end / two-source input need the LDS-halo conv3x3 (variant {bm} x {bn}, "
                              f"stride {stride}, up {up}); apply the GroupNorm / concat as passes for this launch (Ctx.conv_fuses_gn)")
@@ -476,7 +483,7 @@ class Ctx:
         a.rows_per_batch = Ho * Wo
         a.splits, a.flags, a.dtype, a.conv, a.bm, a.bn = sp, 0, self.dt, 1, bm, bn
         a.xcd = self._xcd_for(N, 0, 1)
-        a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.stride, a.up = H, W, Cin, Ho, Wo, stride, up
+        a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.stride, a.up, a.pad = H, W, Cin, Ho, Wo, stride, up, pad
         if x2 is not None:
             a.X2, a.Cin1 = x2.data_ptr(), C1
         gn_keep = ()
@@ -503,7 +510,7 @@ class Ctx:
         self._emit(L.OP_GEMM, a, descr=descr, flops=2.0 * M * N * K,
                    nbytes=es * (B * H * W * Cin + N * K + M * N),
                    keep=(x, w, out, bias, rowadd, residual, x2) + ((gs.t,) if gs else ()) + gn_keep,
-                   shape=(M, N, K, 1, (B, H, W, Cin, stride, up)),
+                   shape=(M, N, K, 1, (B, H, W, Cin, stride, up) + ((pad,) if pad else ())),
                    epi=dict(flags=0, bias=bias is not None, residual=residual is not None, rowadd=rowadd is not None,
                             rows_per_batch=Ho * Wo, cfg=(bm, bn, sp), gn_out=(gs.nblk, Ho * Wo) if gs else None,
                             gn_in=None if gn is None else int(bool(gn[1])), x2=C1 if x2 is not None else 0))
@@ -593,13 +600,17 @@ class Ctx:
         self._f32(L.F32_GEMM, a, descr)
         return out
 
-    def f32_conv3x3(self, x, w, bias=None, residual=None, up=0, descr="f32.conv3x3"):
-        """x NHWC [B, H, W, Cin] fp32, w packed [Cout, 9 Cin] fp32 -> [B, H << up, W << up, Cout]; stride 1, padding 1, nearest x2 fused"""
+    def f32_conv3x3(self, x, w, bias=None, residual=None, up=0, stride=1, pad=0, descr="f32.conv3x3"):
+        """x NHWC [B, H, W, Cin] fp32, w packed [Cout, 9 Cin] fp32 -> [B, Ho, Wo, Cout]: stride 1 with padding 1 and optional nearest x2
+        (Ho = H << up), or stride 2 with padding 1 (Ho = (H - 1) // 2 + 1) or, pad = 1, right / bottom only (Ho = (H - 2) // 2 + 1)"""
         for t, n in ((x, "x"), (w, "w"), (bias, "bias"), (residual, "residual")):
             self._chk(t, f"{descr}.{n}", torch.float32)
         B, H, W, Cin = x.shape
         Cout = w.shape[0]
-        Ho, Wo = H << up, W << up
+        if stride == 1:
+            Ho, Wo = H << up, W << up
+        else:
+            Ho, Wo = ((H - 2) // 2 + 1, (W - 2) // 2 + 1) if pad else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
         if not x.is_contiguous() or not w.is_contiguous() or w.shape[1] != 9 * Cin:
             raise L.ImhError(f"{descr}: x must be contiguous NHWC and w packed [Cout, 9*Cin]")
         out = self.new(B, Ho, Wo, Cout, dtype=torch.float32)
@@ -607,8 +618,27 @@ class Ctx:
         a.X, a.W, a.Y, a.bias, a.residual = x.data_ptr(), w.data_ptr(), out.data_ptr(), self._p(bias), self._p(residual)
         a.M, a.N, a.K = B * Ho * Wo, Cout, 9 * Cin
         a.ldx, a.ldw, a.ldy, a.ldr = Cin, 9 * Cin, Cout, (residual.stride(-2) if residual is not None else 0)
-        a.conv, a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.up = 1, H, W, Cin, Ho, Wo, up
+        a.conv, a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.up, a.stride, a.pad = 1, H, W, Cin, Ho, Wo, up, stride, pad
         self._f32(L.F32_GEMM, a, descr)
+        return out
+
+    def img2img_init(self, out, moments, n1, n2, scaling, add_a, add_b, descr="img2img.init"):
+        """out [S, 4, h, w] fp32 = add_a * scaling * (mean + exp(0.5 clamp(logvar, -30, 20)) * n1) + add_b * n2 in one launch
+        (diffusers' posterior sample + scaling_factor + scheduler.add_noise); moments [M, h, w, 8] fp32 NHWC (the quant_conv output),
+        n1 [N, 4, h, w], n2 [S, 4, h, w]; sample s reads moments s % M and posterior noise s % N"""
+        for t, n in ((out, "out"), (moments, "moments"), (n1, "n1"), (n2, "n2")):
+            self._chk(t, f"{descr}.{n}", torch.float32)
+            if not t.is_contiguous():
+                raise L.ImhError(f"{descr}: {n} must be contiguous")
+        S, c4, h, w = out.shape
+        M, N = moments.shape[0], n1.shape[0]
+        if c4 != 4 or tuple(moments.shape[1:]) != (h, w, 8) or tuple(n1.shape[1:]) != (4, h, w) or tuple(n2.shape) != (S, 4, h, w):
+            raise L.ImhError(f"{descr}: shapes out {tuple(out.shape)} moments {tuple(moments.shape)} n1 {tuple(n1.shape)} n2 {tuple(n2.shape)}")
+        a = L.F32Args()
+        a.X, a.W, a.Y, a.residual = moments.data_ptr(), n1.data_ptr(), out.data_ptr(), n2.data_ptr()
+        a.B, a.HW, a.M, a.N = S, h * w, M, N
+        a.scale, a.add_a, a.add_b = float(scaling), float(add_a), float(add_b)
+        self._f32(L.F32_IMG2IMG_INIT, a, descr)
         return out
 
     def f32_groupnorm(self, x, gamma, beta, groups, eps, silu=False, descr="f32.groupnorm"):

@@ -39,6 +39,7 @@ class DenoiseEngine:
         self._plans = {}         # recorded plans by schedule key (two-stage PNS alternates a preview and a final schedule per image)
         self.max_cached_plans = int(os.environ.get("IMH_MAX_CACHED_PLANS", "3"))      # each pins ~2 GB of activation buffers at 1024^2
         self._sched_key = None
+        self.t_start = 0         # image-to-image: the first step of the schedule that runs (set_schedule)
 
     # -- conditioning (once per image / per PNS run; shared by every candidate seed) --
     @torch.no_grad()
@@ -88,8 +89,14 @@ class DenoiseEngine:
 
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
-                     denoising_end=None):
+                     denoising_end=None, t_start=0):
+        """t_start > 0 (image-to-image, diffusers get_timesteps): the loop runs timesteps[t_start:] -- the device step counter starts at
+        t_start, so the full schedule's tables, time-embedding rows and recorded plan serve; denoising_end then cuts the truncated list
+        and the IP-scale gating window counts it"""
         st, dev = self.st, self.device
+        t_start = int(t_start)
+        if not 0 <= t_start < int(num_inference_steps):
+            raise ValueError(f"t_start {t_start} outside the schedule of {num_inference_steps} steps")
         from .attention_processor import IPAttnProcessor2_0
         base = next((p.scale for p in self.unet.attn_processors.values() if isinstance(p, IPAttnProcessor2_0)), 1.0)
         # the key carries a fingerprint of the tables themselves (timesteps, coefficients, input scale, init sigma): a scheduler instance
@@ -101,7 +108,21 @@ class DenoiseEngine:
             v = tab.get(k)
             fp.update(b"-" if v is None else v.detach().to("cpu", torch.float64).contiguous().numpy().tobytes())
         fp.update(repr(float(tab["init_noise_sigma"])).encode())
-        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), fp.hexdigest())
+        n = num_inference_steps
+        if denoising_end is not None and isinstance(denoising_end, float) and 0 < denoising_end < 1:
+            # custom_pipelines.py:303-311: stop once t falls below the cut-off; the gating window below then counts
+            # the truncated list, as upstream does (image-to-image: the list from t_start on, as diffusers' img2img cuts it)
+            cutoff = int(round(1000 - denoising_end * 1000))
+            n = max(int((tab["timesteps"] >= cutoff).sum().item()), t_start)
+        m = n - t_start                                                      # steps that run: table rows t_start .. n - 1
+        # custom_pipelines.py:319-329 over the m steps that run, at rows t_start + i; the rows before t_start are never read (base
+        # there, so that a text-to-image and an image-to-image call with the same window share one gating table and plan)
+        gate = [float(base)] * t_start + [0.0 if (i / m < control_guidance_start) or ((i + 1) / m > control_guidance_end) else float(base)
+                                          for i in range(m)]
+        # the gating table is part of what the recorded plan reads: its fingerprint is part of the key
+        fp.update(torch.tensor(gate, dtype=torch.float32).numpy().tobytes())
+        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest())
+        self.t_start = t_start
         hit = self._plans.get(key)
         if hit is not None:
             # a schedule this engine has run under this conditioning: its tables, time-embedding rows and recorded plan are still there
@@ -113,17 +134,9 @@ class DenoiseEngine:
             self.plan_tail, self.np_full = hit.get("plan_tail"), hit.get("np_full")
             self._sched_key = key
             return
-        n = num_inference_steps
-        if denoising_end is not None and isinstance(denoising_end, float) and 0 < denoising_end < 1:
-            # custom_pipelines.py:303-311: stop once t falls below the cut-off; the gating window below then counts
-            # the truncated list, as upstream does
-            cutoff = int(round(1000 - denoising_end * 1000))
-            n = int((tab["timesteps"] >= cutoff).sum().item())
         st.t_table = tab["timesteps"].to(dev)
         st.coef_tab = tab["coef"].contiguous().to(dev)
         st.in_scale_tab = tab["in_scale"].to(dev) if tab["in_scale"] is not None else None
-        gate = [0.0 if (i / n < control_guidance_start) or ((i + 1) / n > control_guidance_end) else float(base)
-                for i in range(n)]                                           # custom_pipelines.py:319-329
         st.ip_scale_tab = torch.tensor(gate, dtype=torch.float32, device=dev)
         if st.step is None:
             st.step = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -139,7 +152,7 @@ class DenoiseEngine:
         e = DenoiseEngine(self.unet, self.device, self.dtype, self.use_graph)
         e._is_fork = True                        # never tunes: it may record while its parent is running on another stream
         for k in ("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
-                  "xcd_candidates", "xcd_cells"):
+                  "xcd_candidates", "xcd_cells", "t_start"):
             setattr(e, k, getattr(self, k))
         st = StepState()
         src = self.st
@@ -250,6 +263,8 @@ class DenoiseEngine:
         noise x the full denoise) is then `steps` batch-S forwards deep instead of batch-2S ones."""
         if getattr(self, "cfg_role", None) is None or not self.do_cfg:
             raise L.ImhError("denoise_cfg_split needs an engine whose conditioning was set with cfg_role = 0 / 1 and guidance > 1")
+        if self.t_start:
+            raise NotImplementedError("denoise_cfg_split runs whole schedules (t_start = 0)")
         if self.plan is None:
             self._record()
         st = self.st
@@ -263,20 +278,39 @@ class DenoiseEngine:
         return st.latents
 
     @torch.no_grad()
-    def denoise(self, latents, callback=None, callback_steps=1):
-        """latents: [S, 4, H/8, W/8] unit-variance noise (CPU or device).  Returns final fp32 latents
-        (output_type='latent' of custom_pipelines.py:365-379).  callback(i, t, latents) every ``callback_steps``
-        steps (:359-363) is the only thing that makes the host wait inside the loop."""
-        if getattr(self, "cfg_role", None) is not None and self.do_cfg:
-            raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
+    def prepare_img2img(self, moments, n1, n2, scaling, add_a, add_b):
+        """image-to-image initial latents (diffusers StableDiffusionXLImg2ImgPipeline.prepare_latents) written straight into the engine's
+        latent buffer by one fused fp32 launch: add_a * scaling * (mean + std * n1) + add_b * n2.  moments: the VAE's quant_conv output
+        NHWC [M, h, w, 8] fp32 (M images; sample s reads s % M), n1: posterior noise [N, 4, h, w] (sample s reads s % N), n2: the
+        add-noise noise [S, 4, h, w]; (add_a, add_b) = scheduler.add_noise_coefficients(t_start).  Then denoise(None)."""
         if self.plan is None:
             self._record()
         st = self.st
-        st.latents.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)     # prepare_latents :255-265
-        self.eager.ew(L.EW_STEP_SET, st.step, i=(0, 1, 0, 0, 0, 0), descr="step=0")
-        for i in range(self.steps):                                         # :325 -- no host work per step
+        dev = self.device
+        self.eager.img2img_init(st.latents, moments.to(dev, torch.float32).contiguous(), n1.to(dev, torch.float32).contiguous(),
+                                n2.to(dev, torch.float32).contiguous(), scaling, add_a, add_b)
+        return st.latents
+
+    @torch.no_grad()
+    def denoise(self, latents, callback=None, callback_steps=1):
+        """latents: [S, 4, H/8, W/8] unit-variance noise (CPU or device), or None: the latent buffer already holds the initial latents
+        (prepare_img2img).  Runs the steps t_start .. steps - 1 of the schedule (t_start = 0 unless set_schedule was given one).  Returns
+        final fp32 latents (output_type='latent' of custom_pipelines.py:365-379).  callback(i, t, latents) every ``callback_steps``
+        steps (:359-363; i counts the steps that run from 0) is the only thing that makes the host wait inside the loop."""
+        if getattr(self, "cfg_role", None) is not None and self.do_cfg:
+            raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
+        if self.plan is None:
+            if latents is None:
+                raise L.ImhError("denoise(None) needs the initial latents in place (prepare_img2img) under the current schedule")
+            self._record()
+        st = self.st
+        if latents is not None:
+            st.latents.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)     # prepare_latents :255-265
+        t0 = self.t_start
+        self.eager.ew(L.EW_STEP_SET, st.step, i=(t0, 1, 0, 0, 0, 0), descr="step=t_start")
+        for i in range(t0, self.steps):                                     # :325 -- no host work per step
             self.plan.replay()
-            if callback is not None and i % callback_steps == 0:
+            if callback is not None and (i - t0) % callback_steps == 0:
                 torch.cuda.current_stream(self.device).synchronize()
-                callback(i, st.t_table[i].item(), st.latents)
+                callback(i - t0, st.t_table[i].item(), st.latents)
         return st.latents

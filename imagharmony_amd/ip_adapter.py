@@ -252,8 +252,11 @@ class IPAdapterXL(IPAdapter):
         ``batch`` = preview candidates stacked per UNet forward on a rank; None (default) = as many as the rank holds, up
         to 4 (BASELINE.json configs[4] runs 4 per GPU): a stacked forward costs 1.27x less per candidate than one at a
         time on MI355X (bench.py ``stacked_candidates`` / ``pns_two_stage``); the final denoise is batch 1 either way.
-        Returns dict(images, best_seed, scores, latents)."""
+        Returns dict(images, best_seed, scores, latents).  Text-to-image only: an image-to-image pipeline raises NotImplementedError."""
         from . import pns
+        from .pipeline import StableDiffusionXLImg2ImgCustomPipeline
+        if isinstance(self.pipe, StableDiffusionXLImg2ImgCustomPipeline):
+            raise NotImplementedError("generate_pns runs text-to-image schedules; image-to-image PNS is not supported")
         self.set_scale(scale)
         pipe = self.pipe
         prompt = prompt if prompt is not None else "best quality, high quality"

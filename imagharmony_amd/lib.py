@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _EXP_PATH = os.path.join(_HERE, "..", "tools", "tmp_libs", "libimh_hip_experimental.so")
 LIB_PATH = os.environ.get("IMH_LIB_PATH") or (_EXP_PATH if os.environ.get("IMH_EXPERIMENTAL") == "1" else os.path.join(_HERE, "libimh_hip.so"))
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 IMH_DT_BF16, IMH_DT_F16 = 0, 1
 GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL = 1, 2, 4, 8, 16, 32, 64
 OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN = 0, 1, 2, 3, 4, 5, 6, 7
@@ -51,7 +51,8 @@ class GemmArgs(C.Structure):
                 ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32), ("ldra", _i32),
                 ("rows_per_batch", _i32), ("splits", _i32), ("flags", _i32),
                 ("H", _i32), ("Wd", _i32), ("Cin", _i32), ("Ho", _i32), ("Wo", _i32), ("stride", _i32), ("up", _i32),
-                ("dtype", _i32), ("conv", _i32), ("bm", _i32), ("bn", _i32), ("pf_ptr", _vp), ("pf_bytes", C.c_uint32), ("xcd", _i32)]
+                ("dtype", _i32), ("conv", _i32), ("bm", _i32), ("bn", _i32), ("pf_ptr", _vp), ("pf_bytes", C.c_uint32), ("xcd", _i32),
+                ("pad", _i32)]
 
 
 class AttnArgs(C.Structure):
@@ -99,10 +100,10 @@ class F32Args(C.Structure):
                 ("M", _i32), ("N", _i32), ("K", _i32), ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32),
                 ("conv", _i32), ("H", _i32), ("Wd", _i32), ("Cin", _i32), ("Ho", _i32), ("Wo", _i32), ("up", _i32),
                 ("B", _i32), ("HW", _i32), ("C", _i32), ("groups", _i32), ("nblk", _i32), ("silu", _i32),
-                ("eps", _f32), ("scale", _f32)]
+                ("eps", _f32), ("scale", _f32), ("stride", _i32), ("pad", _i32), ("add_a", _f32), ("add_b", _f32)]
 
 
-F32_GEMM, F32_GN_STATS, F32_GN_TABLE, F32_GN_APPLY, F32_SOFTMAX = range(5)
+F32_GEMM, F32_GN_STATS, F32_GN_TABLE, F32_GN_APPLY, F32_SOFTMAX, F32_IMG2IMG_INIT = range(6)
 
 # every symbol include/imh.h declares: (name, restype, argtypes)
 SYMBOLS = [

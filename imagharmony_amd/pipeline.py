@@ -11,7 +11,7 @@ import torch
 
 from .attention_processor import IPAttnProcessor
 from .denoise import DenoiseEngine
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, get_timesteps
 
 
 @dataclass
@@ -91,16 +91,7 @@ class StableDiffusionXLCustomPipeline:
         BEFORE denoising with a clear error (pass output_type="latent" for latents).  The default scheduler is
         DDIM (BASELINE.json's metric; IP-Adapter convention) -- stock SDXL ships EulerDiscrete: pass
         ``scheduler=EulerDiscreteScheduler()`` for that."""
-        if output_type != "latent" and self.vae is None and self.vae_decode is None:
-            raise NotImplementedError("output_type=%r needs a VAE: construct the pipeline with "
-                                      "vae=imagharmony_amd.vae.AutoencoderKL(...) or vae_decode=callable, or pass "
-                                      "output_type='latent'" % (output_type,))
-        if eta not in (0, 0.0):
-            raise NotImplementedError("eta != 0 (stochastic DDIM) is not supported: the device-resident step is the "
-                                      "deterministic x' = cx*x + ce*eps update (the reference runs eta = 0)")
-        for k in ("negative_original_size", "negative_target_size", "prompt_2", "negative_prompt_2", "cross_attention_kwargs"):
-            if kwargs.get(k) is not None:
-                raise NotImplementedError(f"{k} is not supported on this path (custom_pipelines.py:23-56 accepts it for diffusers' sake)")
+        self._refuse(output_type, eta, kwargs)
         height = height or self.default_sample_size * self.vae_scale_factor      # :189-190
         width = width or self.default_sample_size * self.vae_scale_factor
         if prompt_embeds is None:
@@ -118,6 +109,22 @@ class StableDiffusionXLCustomPipeline:
         if latents is None:
             latents = randn_latents((S, 4, height // 8, width // 8), generator)       # prepare_latents :255-265
         out = eng.denoise(latents, callback=callback, callback_steps=callback_steps).clone()
+        out = self._output(out, output_type)
+        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+
+    def _refuse(self, output_type, eta, kwargs):
+        if output_type != "latent" and self.vae is None and self.vae_decode is None:
+            raise NotImplementedError("output_type=%r needs a VAE: construct the pipeline with "
+                                      "vae=imagharmony_amd.vae.AutoencoderKL(...) or vae_decode=callable, or pass "
+                                      "output_type='latent'" % (output_type,))
+        if eta not in (0, 0.0):
+            raise NotImplementedError("eta != 0 (stochastic DDIM) is not supported: the device-resident step is the "
+                                      "deterministic x' = cx*x + ce*eps update (the reference runs eta = 0)")
+        for k in ("negative_original_size", "negative_target_size", "prompt_2", "negative_prompt_2", "cross_attention_kwargs"):
+            if kwargs.get(k) is not None:
+                raise NotImplementedError(f"{k} is not supported on this path (custom_pipelines.py:23-56 accepts it for diffusers' sake)")
+
+    def _output(self, out, output_type):
         if output_type != "latent":                                       # custom_pipelines.py:365-386
             if self.vae is not None:
                 from .vae import decode_latents, postprocess
@@ -127,4 +134,81 @@ class StableDiffusionXLCustomPipeline:
                 out = postprocess(image, output_type)
             else:
                 out = self.vae_decode(out)
+        return out
+
+
+class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
+    """SDXL image-to-image with diffusers' ``StableDiffusionXLImg2ImgPipeline`` call surface (0.30) for what this path supports: the
+    init image is encoded by the HIP VAE encoder (``vae=AutoencoderKL(..., with_encoder=True)``), noised to step t_start of the
+    schedule (get_timesteps) by one fused launch, and denoised from there by the device-resident loop.  ``IPAdapterXL(pipe, ...)
+    .generate(pil_image=..., image=init, strength=...)`` forwards image / strength here through its **kwargs, as the reference does.
+
+    Known difference: diffusers rounds the initial latents to the pipeline dtype (prepare_latents runs in prompt_embeds.dtype); this
+    loop keeps them in fp32, as the text-to-image path keeps its latents."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, strength: float = 0.3, num_inference_steps: int = 50, denoising_start=None,
+                 denoising_end: Optional[float] = None, guidance_scale: float = 5.0, negative_prompt=None,
+                 num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents=None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+                 callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, **kwargs):
+        """aesthetic_score / negative_aesthetic_score are accepted and unused: SDXL base has requires_aesthetics_score=False.
+        Refused: denoising_start (refiner hand-off), a 4-channel latent ``image``, ``latents=``, eta != 0 (NotImplementedError);
+        strength outside [0, 1] or a schedule that truncates to no step (ValueError)."""
+        if denoising_start is not None:
+            raise NotImplementedError("denoising_start (the refiner hand-off) is not supported on this path")
+        self._refuse(output_type, eta, kwargs)
+        if latents is not None:
+            raise NotImplementedError("latents= is not supported by the image-to-image path: the initial latents come from `image`")
+        if image is None:
+            raise ValueError("image-to-image needs `image` (PIL, a list of PIL images or a tensor [B, 3, H, W])")
+        if torch.is_tensor(image) and image.dim() >= 3 and image.shape[-3] == 4:
+            raise NotImplementedError("a 4-channel latent `image` is not supported: pass the image itself")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
+        from .vae import preprocess
+        img = preprocess(image)
+        if self.vae is None or not getattr(self.vae, "with_encoder", False):
+            raise NotImplementedError("image-to-image needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
+        height, width = img.shape[2], img.shape[3]
+        if prompt_embeds is None:
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
+                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
+        if pooled_prompt_embeds is None:
+            raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
+        S = prompt_embeds.shape[0]
+        B = img.shape[0]
+        if isinstance(generator, (list, tuple)) and len(generator) != S:
+            raise ValueError(f"got {len(generator)} generators for a batch of {S}")
+        if S < B or S % B:
+            raise ValueError(f"cannot duplicate an image batch of {B} to {S} samples")
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps)
+        _, t_start = get_timesteps(sch, num_inference_steps, strength)
+        eng = self.engine
+        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
+                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
+                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
+        eng.set_schedule(sch, num_inference_steps, control_guidance_start, control_guidance_end, denoising_end=denoising_end,
+                         t_start=t_start)
+        # prepare_latents: the posterior sample of every sample's image, then the add-noise noise, drawn in diffusers' order
+        h, w = height // 8, width // 8
+        vae = self.vae
+        if isinstance(generator, (list, tuple)):
+            # sample i encodes image[i % B] (the image batch repeated) and samples its posterior with generator[i]; the B distinct images
+            # are encoded once each, at batch 1 as diffusers encodes them, and read by index
+            moments = torch.cat([vae.encode_moments(img[j:j + 1]) for j in range(B)], 0)
+            n1 = randn_latents((S, 4, h, w), generator)
+        else:
+            moments = vae.encode_moments(img)
+            n1 = randn_latents((B, 4, h, w), generator)                     # one posterior draw per image, repeated S // B times
+        n2 = randn_latents((S, 4, h, w), generator)
+        a, b = sch.add_noise_coefficients(t_start)
+        eng.prepare_img2img(moments, n1, n2, vae.config.scaling_factor, a, b)
+        out = eng.denoise(None, callback=callback, callback_steps=callback_steps).clone()
+        out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)

@@ -42,6 +42,30 @@ class _Base:
         ts = self.timesteps.tolist()
         return ts.index(float(t) if isinstance(ts[0], float) else int(t))
 
+    def add_noise_coefficients(self, t_start):
+        """(a, b) of ``scheduler.add_noise(x, noise, timesteps[t_start]) == a * x + b * noise`` (image-to-image: the initial latents
+        start at step t_start of the schedule set by set_timesteps)"""
+        raise NotImplementedError
+
+    def add_noise(self, x, noise, t_start):
+        """host-side add_noise at step index t_start, in fp32 as diffusers computes it"""
+        a, b = self.add_noise_coefficients(t_start)
+        return x.float() * a + noise.float() * b
+
+
+def get_timesteps(scheduler, num_inference_steps, strength):
+    """diffusers 0.30 StableDiffusionXLImg2ImgPipeline.get_timesteps (denoising_start=None) -> (timesteps[t_start:], t_start), after
+    scheduler.set_timesteps(num_inference_steps): init = min(int(n * strength), n), t_start = max(n - init, 0).  A schedule that
+    truncates to no step raises ValueError, as diffusers' check does."""
+    if not 0.0 <= float(strength) <= 1.0:
+        raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
+    n = int(num_inference_steps)
+    init = min(int(n * strength), n)
+    t_start = max(n - init, 0)
+    if n - t_start < 1:
+        raise ValueError(f"strength {strength} with num_inference_steps {n} leaves no denoising step (num_inference_steps * strength < 1)")
+    return scheduler.timesteps[t_start * scheduler.order:], t_start
+
 
 class DDIMScheduler(_Base):
     """scaled_linear betas, clip_sample=False, set_alpha_to_one=False, steps_offset=1, leading spacing,
@@ -73,6 +97,11 @@ class DDIMScheduler(_Base):
             self._tab = dict(timesteps=self.timesteps.float(), in_scale=None, coef=coef.float(), init_noise_sigma=1.0)
         return self._tab
 
+    def add_noise_coefficients(self, t_start):
+        """diffusers DDIMScheduler.add_noise: (sqrt(abar_t), sqrt(1 - abar_t)) at t = timesteps[t_start], in fp32"""
+        ac = self.alphas_cumprod.float()[int(self.timesteps[t_start])]
+        return float(ac ** 0.5), float((1 - ac) ** 0.5)
+
 
 class EulerDiscreteScheduler(_Base):
     """leading spacing, steps_offset=1, linear sigma interpolation, epsilon prediction."""
@@ -102,3 +131,7 @@ class EulerDiscreteScheduler(_Base):
             self._tab = dict(timesteps=self.timesteps.float(), in_scale=(1.0 / (s[:-1] ** 2 + 1).sqrt()).float(),
                              coef=coef.float(), init_noise_sigma=self.init_noise_sigma)
         return self._tab
+
+    def add_noise_coefficients(self, t_start):
+        """diffusers EulerDiscreteScheduler.add_noise after set_begin_index(t_start): x + noise * sigmas[t_start] (fp32)"""
+        return 1.0, float(self.sigmas[t_start])

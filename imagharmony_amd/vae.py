@@ -3,7 +3,9 @@
 because the SDXL VAE overflows in fp16; test.py:73 turns tiling on) and ``image_processor.postprocess`` (:386).
 
 Same parameter names as diffusers' ``AutoencoderKL`` (``decoder.*``, ``post_quant_conv.*``; encoder keys are accepted
-and ignored), so a real SDXL VAE state dict drops in.  Two compute modes, chosen like the reference chooses
+and ignored -- or, with ``with_encoder=True``, held and loaded strictly), so a real SDXL VAE state dict drops in.  The encoder
+(``encode``, image-to-image) runs the same two compute modes on the same kernels; its downsamplers are the stride-2 conv3x3 with
+right / bottom padding (imh_gemm_args.pad = 1, diffusers ``Downsample2D(padding=0)``).  Two compute modes, chosen like the reference chooses
 (``needs_upcasting = vae.dtype == float16 and vae.config.force_upcast`` -> ``upcast_vae()``, custom_pipelines.py:366-372):
 
 * **fp32** (round 6; a float16 module with ``force_upcast``, or a float32 module): fp32 activations, fp32 weights (the stored
@@ -160,6 +162,34 @@ class UpDecoderBlock2D(nn.Module):
         return x
 
 
+class Downsample2D(nn.Module):
+    """diffusers Downsample2D(padding=0): conv3x3(F.pad(x, (0, 1, 0, 1)), stride 2) -- the pad is the conv's padding mode 1"""
+
+    def __init__(self, ch):
+        super().__init__()
+        self.conv = Conv2d(ch, ch, 3)
+
+    def emit(self, ctx, x):
+        out = ctx.conv3x3(x, self.conv.packed(ctx), bias=_b(self.conv, ctx), stride=2, pad=1, descr="vae.downsample")
+        ctx.free(x)
+        return out
+
+
+class DownEncoderBlock2D(nn.Module):
+    def __init__(self, cin, cout, n, groups, down):
+        super().__init__()
+        self.resnets = nn.ModuleList([ResnetBlock2D(cin if i == 0 else cout, cout, groups) for i in range(n)])
+        if down:
+            self.downsamplers = nn.ModuleList([Downsample2D(cout)])
+
+    def emit(self, ctx, x):
+        for r in self.resnets:
+            x = r.emit(ctx, x)
+        for d in getattr(self, "downsamplers", []):
+            x = d.emit(ctx, x)
+        return x
+
+
 class MidBlock(nn.Module):
     def __init__(self, ch, groups):
         super().__init__()
@@ -185,6 +215,49 @@ class Decoder(nn.Module):
             c = co
         self.conv_norm_out = Norm(ch[-1], 1e-6)
         self.conv_out = Conv2d(ch[-1], cfg.out_channels, 3)
+
+
+class Encoder(nn.Module):
+    """diffusers Encoder (down blocks, mid block, GroupNorm + SiLU, conv_out to the 2 x latent_channels moments), double_z"""
+
+    def __init__(self, cfg: VAEConfig):
+        super().__init__()
+        ch = cfg.block_out_channels
+        g = cfg.norm_num_groups
+        self.groups = g
+        self.conv_in = Conv2d(cfg.in_channels, ch[0], 3)
+        self.down_blocks = nn.ModuleList()
+        c = ch[0]
+        for i, co in enumerate(ch):
+            self.down_blocks.append(DownEncoderBlock2D(c, co, cfg.layers_per_block, g, down=i < len(ch) - 1))
+            c = co
+        self.mid_block = MidBlock(ch[-1], g)
+        self.conv_norm_out = Norm(ch[-1], 1e-6)
+        self.conv_out = Conv2d(ch[-1], 2 * cfg.latent_channels, 3)
+
+
+class DiagonalGaussianDistribution:
+    """diffusers DiagonalGaussianDistribution over the moments [B, 2 C, h, w] (fp32): logvar clamped to [-30, 20]"""
+
+    def __init__(self, parameters):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+
+    def sample(self, generator=None):
+        """diffusers: mean + std * randn_tensor(mean.shape, generator, dtype=fp32) -- drawn on the generator's device"""
+        from .pipeline import randn_latents
+        return self.mean + self.std * randn_latents(self.mean.shape, generator).to(self.parameters.device)
+
+    def mode(self):
+        return self.mean
+
+
+@dataclass
+class AutoencoderKLOutput:
+    latent_dist: DiagonalGaussianDistribution
 
 
 def _pad_conv_in(conv, ctx, cpad=64):
@@ -303,14 +376,20 @@ def _attn32(ctx, at, x):
 
 
 class AutoencoderKL(nn.Module):
-    """decode-only AutoencoderKL.  ``decode(z)`` returns the image tensor [B, 3, 8h, 8w] (fp32, roughly [-1, 1])."""
+    """AutoencoderKL.  ``decode(z)`` returns the image tensor [B, 3, 8h, 8w] (fp32, roughly [-1, 1]); with ``with_encoder=True``
+    ``encode(x)`` returns diffusers' ``AutoencoderKLOutput`` (``.latent_dist``) of an image tensor [B, 3, H, W] in [-1, 1]."""
 
-    def __init__(self, config: VAEConfig = None):
+    def __init__(self, config: VAEConfig = None, with_encoder=False):
         super().__init__()
         self.config = config or VAEConfig()
         c = self.config
+        # decoder first: init_random_(s) draws the decoder's weights identically with or without the encoder
         self.decoder = Decoder(c)
         self.post_quant_conv = Conv2d(c.latent_channels, c.latent_channels, 1)
+        self.with_encoder = bool(with_encoder)
+        if self.with_encoder:
+            self.encoder = Encoder(c)
+            self.quant_conv = Conv2d(2 * c.latent_channels, 2 * c.latent_channels, 1)
         self.use_tiling = False
         self.tile_sample_min_size = c.sample_size if c.sample_size < 512 else 512
         self.tile_latent_min_size = int(self.tile_sample_min_size / (2 ** (len(c.block_out_channels) - 1)))
@@ -318,13 +397,14 @@ class AutoencoderKL(nn.Module):
 
     # -- loading --
     def load_state_dict(self, sd, strict=True, **kw):
-        sd = {k: v for k, v in sd.items() if not (k.startswith("encoder.") or k.startswith("quant_conv."))}
+        if not self.with_encoder:
+            sd = {k: v for k, v in sd.items() if not (k.startswith("encoder.") or k.startswith("quant_conv."))}
         return super().load_state_dict(sd, strict=strict, **kw)
 
     @classmethod
-    def from_safetensors(cls, path, config: VAEConfig = None, device="cuda:0", dtype=torch.bfloat16):
+    def from_safetensors(cls, path, config: VAEConfig = None, device="cuda:0", dtype=torch.bfloat16, with_encoder=False):
         from safetensors.torch import load_file
-        m = cls(config)
+        m = cls(config, with_encoder=with_encoder)
         m.load_state_dict(load_file(path), strict=True)
         return m.to(device, dtype)
 
@@ -465,6 +545,169 @@ class AutoencoderKL(nn.Module):
         if self.use_tiling and (z.shape[-1] > self.tile_latent_min_size or z.shape[-2] > self.tile_latent_min_size):
             return self.tiled_decode(z, precision)
         return self._decode_tile(z, precision)
+
+
+    # -- encode (image-to-image) --
+    def _encoder(self):
+        if not self.with_encoder:
+            raise NotImplementedError("this AutoencoderKL holds no encoder: construct it with with_encoder=True (image-to-image)")
+        return self.encoder
+
+    def _encode_tile_f32(self, x):
+        """x: [B, 3, H, W] fp32 on the device -> moments NHWC [B, H/8', W/8', 2 C] fp32 (quant_conv(encoder(x))), every product in fp32"""
+        dev = x.device
+        ctx = Ctx(dev, torch.bfloat16)                                           # (pool / stream only: every tensor below is fp32)
+        e = self._encoder()
+        B, cin, H, W = x.shape
+        xp = torch.zeros(B, H, W, 16, dtype=torch.float32, device=dev)          # plumbing: NHWC, channels padded to the K step of 16
+        xp[..., :cin] = x.permute(0, 2, 3, 1)
+        h = ctx.f32_conv3x3(xp, _f32_conv_w(e.conv_in, cin_pad=16), bias=_f32_vec(e.conv_in), descr="vae32.enc.conv_in")
+        for blk in e.down_blocks:
+            for r in blk.resnets:
+                h = _res32(ctx, r, h)
+            for d in getattr(blk, "downsamplers", []):
+                y = ctx.f32_conv3x3(h, _f32_conv_w(d.conv), bias=_f32_vec(d.conv), stride=2, pad=1, descr="vae32.enc.downsample")
+                ctx.free(h)
+                h = y
+        h = _res32(ctx, e.mid_block.resnets[0], h)
+        h = _attn32(ctx, e.mid_block.attentions[0], h)
+        h = _res32(ctx, e.mid_block.resnets[1], h)
+        n = _gn32(ctx, e.conv_norm_out, h, e.groups, True, "vae32.enc.conv_norm_out")
+        ctx.free(h)
+        y = ctx.f32_conv3x3(n, _f32_conv_w(e.conv_out), bias=_f32_vec(e.conv_out), descr="vae32.enc.conv_out")      # [B, h, w, 2C]
+        ctx.free(n)
+        B, hh, ww, c2 = y.shape
+        yp = torch.zeros(B * hh * ww, 16, dtype=torch.float32, device=dev)      # plumbing: K padded to 16
+        yp[:, :c2] = y.view(-1, c2)
+        ctx.free(y)
+        qc = self.quant_conv
+
+        def build_q():
+            wq = torch.zeros(c2, 16, dtype=torch.float32, device=dev)
+            wq[:, :c2] = qc.weight.detach().float().view(c2, c2)
+            return wq
+        wq = _f32_cached(qc, "_imh_f32_w", build_q, qc.weight)
+        m = ctx.f32_gemm(yp, wq, bias=_f32_vec(qc), descr="vae32.enc.quant_conv")
+        return m.view(B, hh, ww, c2).clone()
+
+    def _encode_tile(self, x, precision="native"):
+        """x: [B, 3, H, W] fp32 on the device -> moments NHWC [B, h, w, 2 C] fp32"""
+        if precision == "fp32":
+            return self._encode_tile_f32(x)
+        dev, dt = x.device, self.dtype
+        if dt not in (torch.bfloat16, torch.float16):
+            raise L.ImhError("the native HIP VAE path computes in bf16 or fp16 (precision='fp32' runs any module in fp32)")
+        ctx = Ctx(dev, dt)
+        e = self._encoder()
+        B, cin, H, W = x.shape
+        xp = torch.zeros(B, H, W, 64, dtype=dt, device=dev)                     # plumbing: NHWC, channels padded to 64
+        xp[..., :cin] = x.permute(0, 2, 3, 1).to(dt)
+        h = ctx.conv3x3(xp, _pad_conv_in(e.conv_in, ctx), bias=_b(e.conv_in, ctx), descr="vae.enc.conv_in")
+        for blk in e.down_blocks:
+            h = blk.emit(ctx, h)
+        h = e.mid_block.emit(ctx, h)
+        n = _gn(ctx, e.conv_norm_out, h, e.groups, True, "vae.enc.conv_norm_out")
+        ctx.free(h)
+        y = ctx.conv3x3(n, e.conv_out.packed(ctx), bias=_b(e.conv_out, ctx), descr="vae.enc.conv_out")        # [B, h, w, 2C]
+        ctx.free(n)
+        B, hh, ww, c2 = y.shape
+        yp = torch.zeros(B * hh * ww, 64, dtype=dt, device=dev)                 # plumbing: K padded to 64
+        yp[:, :c2] = y.view(-1, c2)
+        ctx.free(y)
+        wq, bq = _pad_1x1(self.quant_conv, ctx)
+        m = torch.empty(B * hh * ww, 64, dtype=torch.float32, device=dev)
+        ctx.gemm(yp, wq, bias=bq, out=m, flags=L.GF_OUT_F32, descr="vae.enc.quant_conv")                        # fp32 moments
+        return m[:, :c2].reshape(B, hh, ww, c2)
+
+    def tiled_encode(self, x, precision="native"):
+        """diffusers 0.30 tiled_encode: tiles of tile_sample_min_size px at stride (1 - overlap) of that, encoder + quant_conv per tile,
+        in-place blend_v / blend_h over int(tile_latent_min_size * overlap) latent rows, crop to tile_latent_min_size - blend_extent.
+        Returns NCHW moments [B, 2 C, h, w].  The tiles of one shape are encoded as one batch, as tiled_decode does."""
+        overlap = int(self.tile_sample_min_size * (1 - self.tile_overlap_factor))
+        extent = int(self.tile_latent_min_size * self.tile_overlap_factor)
+        limit = self.tile_latent_min_size - extent
+        ii, jj = list(range(0, x.shape[2], overlap)), list(range(0, x.shape[3], overlap))
+        tiles = {(i, j): x[:, :, i:i + self.tile_sample_min_size, j:j + self.tile_sample_min_size] for i in ii for j in jj}
+        groups = {}
+        for key, t in tiles.items():
+            groups.setdefault(tuple(t.shape[2:]), []).append(key)
+        enc = {}
+        for keys in groups.values():
+            out = self._encode_tile(torch.cat([tiles[k] for k in keys], 0).contiguous(), precision).permute(0, 3, 1, 2)
+            for k, o in zip(keys, out.split(x.shape[0], 0)):
+                enc[k] = o
+        rows = [[enc[(i, j)] for j in jj] for i in ii]
+        out_rows = []
+        for i, row in enumerate(rows):
+            out = []
+            for j, t in enumerate(row):
+                if i > 0:
+                    t = self._blend(rows[i - 1][j], t, extent, 2)
+                if j > 0:
+                    t = self._blend(row[j - 1], t, extent, 3)
+                row[j] = t               # diffusers blends in place: later tiles see the blended neighbour
+                out.append(t[:, :, :limit, :limit])
+            out_rows.append(torch.cat(out, dim=3))
+        return torch.cat(out_rows, dim=2)
+
+    @torch.no_grad()
+    def encode_moments(self, x, precision=None):
+        """x: [B, 3, H, W] in [-1, 1], H and W multiples of 8 -> the moments quant_conv(encoder(x)) as NHWC [B, H/8, W/8, 2 C] fp32
+        (the layout the img2img initial-latents op reads).  Tiled like diffusers when use_tiling and a side exceeds tile_sample_min_size."""
+        precision = self.precision_for(precision)
+        self._encoder()
+        if x.dim() != 4 or x.shape[1] != self.config.in_channels or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"encode: expected an image [B, {self.config.in_channels}, H, W] with H and W multiples of 8, got {tuple(x.shape)}")
+        x = x.to(self.decoder.conv_in.weight.device, torch.float32)
+        if self.use_tiling and (x.shape[-1] > self.tile_sample_min_size or x.shape[-2] > self.tile_sample_min_size):
+            return self.tiled_encode(x, precision).permute(0, 2, 3, 1).contiguous()
+        return self._encode_tile(x, precision).contiguous()
+
+    @torch.no_grad()
+    def encode(self, x, precision=None):
+        """diffusers AutoencoderKL.encode: -> AutoencoderKLOutput(latent_dist=DiagonalGaussianDistribution(moments [B, 2 C, h, w] fp32)).
+        precision: as decode (the reference upcasts an fp16 VAE with force_upcast for encode too)"""
+        return AutoencoderKLOutput(DiagonalGaussianDistribution(self.encode_moments(x, precision).permute(0, 3, 1, 2).contiguous()))
+
+
+def preprocess(image):
+    """VaeImageProcessor.preprocess (do_resize, do_normalize, vae_scale_factor 8, resample 'lanczos') for the img2img input:
+    a PIL image, a list of them, or a float tensor [B, 3, H, W] / [3, H, W] -> fp32 [B, 3, H, W] in [-1, 1].  Sides that are not
+    multiples of 8 are resized DOWN to the next multiple (PIL: Lanczos; tensor: nearest, F.interpolate's default); PIL pixels /255;
+    then 2 x - 1 -- except for a tensor with min() < 0, which is taken as already in [-1, 1]."""
+    import numpy as np
+    try:
+        from PIL import Image
+    except ImportError:                                    # pragma: no cover - PIL ships with torchvision / diffusers installs
+        Image = None
+    if Image is not None and isinstance(image, Image.Image):
+        image = [image]
+    if isinstance(image, (list, tuple)):
+        if not image or Image is None or not all(isinstance(i, Image.Image) for i in image):
+            raise ValueError("preprocess: expected a PIL image, a list of PIL images or a tensor [B, 3, H, W]")
+        w, h = image[0].size
+        w, h = w - w % 8, h - h % 8
+        arrs = []
+        for im in image:
+            if im.mode != "RGB":
+                im = im.convert("RGB")
+            if im.size != (w, h):
+                im = im.resize((w, h), resample=Image.LANCZOS)
+            arrs.append(np.asarray(im).astype(np.float32) / 255.0)
+        x = torch.from_numpy(np.stack(arrs, 0)).permute(0, 3, 1, 2).contiguous()
+        return 2.0 * x - 1.0
+    if not torch.is_tensor(image):
+        raise ValueError(f"preprocess: unsupported image type {type(image).__name__}")
+    x = image.unsqueeze(0) if image.dim() == 3 else image
+    if x.dim() != 4:
+        raise ValueError(f"preprocess: expected [B, C, H, W], got {tuple(image.shape)}")
+    x = x.float()
+    h, w = x.shape[2] - x.shape[2] % 8, x.shape[3] - x.shape[3] % 8
+    if (h, w) != tuple(x.shape[2:]):
+        x = torch.nn.functional.interpolate(x, size=(h, w))
+    if x.min() < 0:
+        return x
+    return 2.0 * x - 1.0
 
 
 def decode_latents(vae: AutoencoderKL, latents, precision=None):

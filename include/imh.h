@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMH_ABI_VERSION 9
+#define IMH_ABI_VERSION 10
 
 enum imh_status {
     IMH_OK = 0,
@@ -64,8 +64,11 @@ enum imh_gemm_flags {
  *   proj_in/proj_out/FeedForward/TimestepEmbedding/time_emb_proj/conv_shortcut,
  *   Resampler / ImageProjModel / HarmonyAttention linears (resampler.py:13-20,45-47,101-103;
  *   ip_adapter.py:38; train.py:208,239).
- * conv == 1: 3x3 convolution, padding 1, stride 1|2, optional fused nearest x2 upsampling of the
+ * conv == 1: 3x3 convolution, stride 1|2, optional fused nearest x2 upsampling of the
  *   input (up = 1), as an implicit GEMM over NHWC input [B, H, Wd, Cin]; K = 9*Cin; M = B*Ho*Wo.
+ *   Padding by `pad` (ABI 10): 0 = one zero pixel on every side (Ho = (H - 1) / stride + 1); 1 = none on the top / left and
+ *   one on the right / bottom -- diffusers Downsample2D(padding=0), conv(F.pad(x, (0, 1, 0, 1)), stride 2): input row
+ *   2 oy + ky, zero beyond H - 1, Ho = (H - 2) / 2 + 1 (the VAE encoder's downsamplers); stride 2, up = 0 only.
  *   Replaces diffusers ResnetBlock2D.conv1/conv2, Downsample2D.conv, Upsample2D(+interpolate), conv_out.
  * K must be a multiple of 64; M and N are arbitrary (edge tiles read a zero page).
  * bm/bn/splits = 0 selects the built-in heuristic.  splits > 1 needs `partial`
@@ -165,6 +168,10 @@ typedef struct imh_gemm_args {
      * cells): 0 = the byte-count model picks the shape, 2 / 3 / 4 / 5 = 8 x 1 / 4 x 2 / 2 x 4 / 1 x 8 cells.  Placement only:
      * results are bit-identical.  Which shape is faster depends on the box, so the host measures. */
     int32_t xcd;
+    /* conv padding mode (ABI 10; see conv == 1 above): 0 = one pixel on every side (the zero-initialised default), 1 = right / bottom
+     * only (Downsample2D(padding=0)).  Mode 1 runs on the two-stage tiles, the rings and the wave-specialised variants; the LDS-halo
+     * conv3x3 (stride 1) refuses it with IMH_ERR_ARG. */
+    int32_t pad;
 } imh_gemm_args;
 
 int imh_gemm(const imh_gemm_args* a, void* stream);
@@ -357,15 +364,24 @@ int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
  * ip_adapter/custom_pipelines.py:365-377 upcasts the SDXL VAE to fp32 before `vae.decode` (it overflows in fp16): this entry keeps
  * fp32 activations, fp32 weights and fp32 arithmetic (v_mfma_f32_32x32x2_f32: exact products, fp32 accumulate).  All pointers fp32.
- *   IMH_F32_GEMM     Y[M, N] = X[M, K] W[N, K]^T (+ bias[n]) (+ residual[m, n]); K % 16 == 0.  conv == 1: 3x3, padding 1, stride 1,
- *                    optional nearest x2 upsampling of the input (up = 1), NHWC input [B, H, Wd, Cin], weights [Cout][ky][kx][Cin],
- *                    K = 9 Cin, Cin % 16 == 0, M = B Ho Wo.  Replaces diffusers AutoencoderKL's Conv2d / Linear / Upsample2D.
+ *   IMH_F32_GEMM     Y[M, N] = X[M, K] W[N, K]^T (+ bias[n]) (+ residual[m, n]); K % 16 == 0.  conv == 1: 3x3, stride 1 | 2 (0 = 1),
+ *                    padding mode `pad` as imh_gemm_args.pad (0: one pixel on every side; 1: right / bottom only, stride 2 -- the
+ *                    encoder's Downsample2D), optional nearest x2 upsampling of the input (up = 1, stride 1), NHWC input [B, H, Wd, Cin],
+ *                    weights [Cout][ky][kx][Cin], K = 9 Cin, Cin % 16 == 0, M = B Ho Wo.  Replaces diffusers AutoencoderKL's Conv2d /
+ *                    Linear / Upsample2D / Downsample2D.
  *   IMH_F32_GN_STATS X [B, HW, C] -> ws [B, nblk, groups, 2] = (mean, M2) per pixel block and group   (diffusers GroupNorm(32, eps 1e-6))
  *   IMH_F32_GN_TABLE ws, gamma, beta -> Y [B, C, 2] = (gamma rstd, beta - mean gamma rstd), merged in double in a fixed order
  *   IMH_F32_GN_APPLY Y = silu?(X scale + shift), ws = the table
  *   IMH_F32_SOFTMAX  Y[r, 0:N] = softmax(scale X[r, 0:N]), M rows (the mid-block attention's materialised scores)
+ *   IMH_F32_IMG2IMG_INIT  the initial latents of SDXL image-to-image (diffusers StableDiffusionXLImg2ImgPipeline.prepare_latents) in one
+ *                    pass: X = the quant_conv moments [M, HW, 8] NHWC (mean = channels 0-3, logvar = 4-7), W = posterior noise [N, 4, HW],
+ *                    residual = add-noise noise [B, 4, HW], Y = latents [B, 4, HW] (NCHW):
+ *                      z = scale (mean + exp(0.5 clamp(logvar, -30, 20)) n1),  Y = add_a z + add_b n2
+ *                    sample s reads moments s % M and posterior noise s % N (batch expansion by index: one encoded image feeds
+ *                    several samples); (add_a, add_b) = (sqrt(abar_t), sqrt(1 - abar_t)) for DDIM, (1, sigma_t) for Euler
  */
-enum imh_f32_op { IMH_F32_GEMM = 0, IMH_F32_GN_STATS = 1, IMH_F32_GN_TABLE = 2, IMH_F32_GN_APPLY = 3, IMH_F32_SOFTMAX = 4 };
+enum imh_f32_op { IMH_F32_GEMM = 0, IMH_F32_GN_STATS = 1, IMH_F32_GN_TABLE = 2, IMH_F32_GN_APPLY = 3, IMH_F32_SOFTMAX = 4,
+                  IMH_F32_IMG2IMG_INIT = 5 };
 
 typedef struct imh_f32_args {
     const float* X;
@@ -380,6 +396,8 @@ typedef struct imh_f32_args {
     int32_t conv, H, Wd, Cin, Ho, Wo, up;
     int32_t B, HW, C, groups, nblk, silu;
     float eps, scale;
+    int32_t stride, pad;     /* ABI 10: conv stride (0 = 1) and padding mode (as imh_gemm_args.pad) */
+    float add_a, add_b;      /* ABI 10: IMH_F32_IMG2IMG_INIT's add-noise pair */
 } imh_f32_args;
 
 int imh_f32(int op, const imh_f32_args* a, void* stream);

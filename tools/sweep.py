@@ -98,12 +98,14 @@ def sweep_shapes(rec, dtype, extra=None, base=None):
     report = []
     for (M, N, K, conv, geom), descr in shapes.items():
         x = w = None
+        pad = 0
         if conv:
-            B, H, W, Cin, stride, up = geom
+            B, H, W, Cin, stride, up, *rest = geom          # a seventh field: the conv padding mode (Ctx.conv3x3(pad=1)), recorded when non-zero
+            pad = rest[0] if rest else 0
             x = torch.randn(B, H, W, Cin, device=DEV).to(dtype)
             w = (torch.randn(N, K, device=DEV) * K ** -0.5).to(dtype)
-            call = lambda cfg, c=None: (c or ctx).conv3x3(x, w, stride=stride, up=up, cfg=cfg, out=out)
-            Ho, Wo = ((H << up) - 1) // stride + 1, ((W << up) - 1) // stride + 1
+            call = lambda cfg, c=None: (c or ctx).conv3x3(x, w, stride=stride, up=up, pad=pad, cfg=cfg, out=out)
+            Ho, Wo = ((H - 2) // 2 + 1, (W - 2) // 2 + 1) if pad else (((H << up) - 1) // stride + 1, ((W << up) - 1) // stride + 1)
             out = torch.empty(B, Ho, Wo, N, device=DEV, dtype=dtype)
         else:
             x = torch.randn(M, K, device=DEV).to(dtype)
@@ -128,7 +130,7 @@ def sweep_shapes(rec, dtype, extra=None, base=None):
             cands += [(7128, 320, 1), (7128, 160, 1), (7564, 320, 1), (7564, 160, 1), (7328, 160, 1), (7428, 160, 1), (7256, 160, 1), (7356, 160, 1)]           # LDS-halo conv kernel (stride 1 only)
         if extra:                      # incremental: the current table entry against the new variants only
             key = f"{M},{N},{K},{conv}"
-            cands = [tuple(base[key])] if base and key in base else [tuple(ctx._config(M, N, K, conv, 0))]
+            cands = [tuple(base[key])] if base and key in base else [tuple(ctx._config(M, N, K, conv, 0, pad=pad))]
             cands += [c for c in extra if c not in cands]
         from tools.gemm_bench import graph_time
         for cfg in cands:
@@ -138,7 +140,7 @@ def sweep_shapes(rec, dtype, extra=None, base=None):
                 print("  cfg failed", cfg, ex)
         res.sort()
         best_ms, best = res[0]
-        hb = ctx._config(M, N, K, conv, 0)
+        hb = ctx._config(M, N, K, conv, 0, pad=pad)
         h_ms = [r[0] for r in res if tuple(r[1]) == tuple(hb)]
         tf = 2.0 * M * N * K / best_ms / 1e9
         print(f"  {descr:18s} M={M:6d} N={N:6d} K={K:6d} conv={conv} best {best} {best_ms*1e3:8.1f} us {tf:7.1f} TF/s"
