@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: 1024^2 SDXL images/sec (30 DDIM steps, one PNS candidate seed per GPU per step).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 A "step" = one full 30-step denoise of one candidate per rank through the HIP hot path (UNet forward with
 the harmony-aware IP-Adapter processors + CFG + DDIM update), at BASELINE.json configs[1] (N=1) /
@@ -12,7 +12,11 @@ nothing per step (weak scaling); RCCL is used for the one-time weight / conditio
 final score gather only.  The K/V projections of the conditioning are computed once per PNS run (they are
 step- and seed-invariant), outside the timed region, as the one-time conditioning work they are.
 
-Rank 0 prints ONE JSON line with the metric plus
+Rank 0 prints ONE JSON line with the metric (`value`, `ms_per_step`) and the run's configuration.  A plain run does
+nothing else: it sets up, warms up, times the steps, writes --dump-outputs and prints.  With --full the line also carries
+every measurement that takes runs of its own (all of them outside `value`): the clock / power sampler during the timed
+steps, the timed collectives (N > 1), the per-kernel rooflines, the in-flight / stacked candidates, BASELINE.json
+configs[3] / configs[4], the box calibration, the two-stage PNS run, the VAE decode, the Resampler, and
   roofline     -- the dominant kernel family (MFMA GEMM / implicit-GEMM conv): algorithmic FLOPs of its
                   launches in one denoise step / their summed durations, measured here with HIP events on
                   the launch stream; peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md).
@@ -40,12 +44,14 @@ def parse():
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--denoise-steps", type=int, default=30)
     ap.add_argument("--ip-tokens", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-res", type=int, default=1024)
-    ap.add_argument("--in-flight", type=int, default=2, help="EXTRA measurement (never `value`): PNS candidates in flight per "
-                    "GPU, one HIP stream each, batch 1 each; 1 = skip")
-    ap.add_argument("--stacked", type=int, default=4, help="EXTRA measurement (never `value`): PNS candidates stacked into one "
-                    "UNet batch per GPU (BASELINE.json configs[4] runs 4 per GPU); 1 = skip")
+    ap.add_argument("--full", action="store_true", help="also run every measurement outside `value` (rooflines, extras, "
+                    "CPU baseline; see the module docstring) and add it to the line; a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-res", type=int, default=1024, help="--full: resolution of the CPU baseline")
+    ap.add_argument("--in-flight", type=int, default=2, help="EXTRA measurement of --full (never `value`): PNS candidates in "
+                    "flight per GPU, one HIP stream each, batch 1 each; 1 = skip")
+    ap.add_argument("--stacked", type=int, default=4, help="EXTRA measurements of --full (never `value`): PNS candidates stacked "
+                    "into one UNet batch per GPU (BASELINE.json configs[4] runs 4 per GPU); 1 = skip these and the other extras")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm; gloo only for "
                     "single-GPU testing of the multi-rank control path)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
@@ -523,16 +529,17 @@ def main():
     unet = build_unet(device, dtype, a.ip_tokens)
     collectives = None
     if world > 1:
-        # the one-time weight broadcast over xGMI (RCCL), timed: first call (communicator set-up + transfer), then once more warm --
-        # outside `value`, reported under config.distributed.collectives
+        # the one-time weight broadcast over xGMI (RCCL); --full times it: first call (communicator set-up + transfer), then once more
+        # warm -- outside `value`, reported under config.distributed.collectives
         w_bytes = sum(t.numel() * t.element_size() for t in list(unet.parameters()) + list(unet.buffers()))
         bt = []
-        for _ in range(2):
+        for _ in range(2 if a.full else 1):
             torch.cuda.synchronize(device); dist.barrier(); torch.cuda.synchronize(device)
             tb = time.perf_counter()
             n_coll = pns.broadcast_module_(unet, src=0)
             torch.cuda.synchronize(device); dist.barrier()
             bt.append(time.perf_counter() - tb)
+    if world > 1 and a.full:
         collectives = {"weight_broadcast": {"bytes": w_bytes, "GB": w_bytes / 1e9, "collectives": n_coll, "first_call_s": bt[0], "warm_s": bt[1],
                                             "warm_GB_per_s": w_bytes / 1e9 / bt[1],
                                             "note": "pns.broadcast_module_: the UNet replica of rank 0 to every rank as flat 512-MB buckets "
@@ -545,8 +552,9 @@ def main():
     eng = pipe.engine
     # per-image conditioning work (text / image-prompt K, V caches of the 70 cross-attention layers + the added-conditioning embedding:
     # attention_processor.py:410-411,432-433 hoisted out of the step loop) -- outside `value`, reported as conditioning_prepare_ms
+    # (--full: three calls, the later ones warm)
     cond_ms = []
-    for _ in range(3):
+    for _ in range(3 if a.full else 1):
         torch.cuda.synchronize(device)
         tc = time.perf_counter()
         eng.set_conditioning(pe, ne, po, no, a.res, a.res, guidance_scale=5.0)
@@ -605,7 +613,7 @@ def main():
     for i in range(a.warmup):
         eng.denoise(noises[i])
     barrier()
-    clk = ClockSampler() if rank == 0 else None              # host thread reading rocm-smi (sysfs): shader clock / power under load
+    clk = ClockSampler() if rank == 0 and a.full else None   # host thread reading rocm-smi (sysfs): shader clock / power under load
     t0 = time.perf_counter()
     for i in range(a.warmup, a.warmup + a.steps):
         out = eng.denoise(noises[i])
@@ -620,6 +628,7 @@ def main():
         dist.all_gather(alld, tmax)                          # per-rank wall time: the first real multi-GPU run diagnoses itself
         per_rank = [float(t.item()) / a.steps * 1e3 for t in alld]
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+    if world > 1 and a.full:
         allscores = [torch.empty_like(torch.cat(scores)) for _ in range(world)]
         dist.all_gather(allscores, torch.cat(scores))        # final gather of the candidate scores
         torch.cuda.synchronize(device)
@@ -634,8 +643,39 @@ def main():
         dump_outputs(a.dump_outputs, out, scores[-1], world, rank)
 
     if rank == 0:
-        # ---- roofline of the dominant kernel family, timed with HIP events on the launch stream ----
         rec = eng.plan
+        tot_fl = sum(t[3] for t in rec.tags)
+        images = a.steps * world
+        res = {
+            "metric": "1024^2 SDXL images/sec (30 DDIM steps, PNS N seeds)" if a.res == 1024 and a.denoise_steps == 30
+                      else f"{a.res}^2 SDXL images/sec ({a.denoise_steps} DDIM steps, PNS N seeds)",
+            "value": images / dt, "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": a.dtype, "data": "synthetic", "full": a.full,
+            "config": {"workload": f"SDXL UNet {a.res}x{a.res}, {a.denoise_steps} DDIM steps, CFG 5.0 (UNet batch 2), "
+                                   f"IP-Adapter scale 1.0, {a.ip_tokens} image tokens, 1 PNS candidate seed per GPU per step",
+                       "parallelism": f"candidates sharded x{world} (no per-step collective)", "outputs_finite": finite,
+                       "distributed": {"world_size_reported_by_backend": dist.get_world_size() if world > 1 else 1,
+                                       "backend": dist.get_backend() if world > 1 else None,
+                                       "per_rank_ms_per_step": per_rank,
+                                       "collectives": collectives,
+                                       "devices_visible": torch.cuda.device_count()},
+                       "conditioning_prepare_ms": {"first_call": cond_ms[0], "later_calls": cond_ms[1:],
+                                                   "note": "DenoiseEngine.set_conditioning: K / V caches of the 70 cross-attention layers (140 small GEMMs "
+                                                           "+ 20 for the image-prompt tokens), add_embedding; once per image / per PNS run, shared by every "
+                                                           "candidate seed; not in `value`"},
+                       "value_counts": "denoised latents per second (the reference's output_type='latent'); the VAE decode + "
+                                       "post-processing tail (custom_pipelines.py:365-386) is NOT in `value` -- its time is "
+                                       "reported under vae_decode (--full)",
+                       "ms_per_unet_forward": dt / a.steps / a.denoise_steps * 1e3,
+                       "xcd_cells": {"chosen": eng.xcd_cells, "ms_per_step_when_picked": getattr(eng, "xcd_times_ms", None),
+                                     "note": "XCD cell shape of the GEMM / conv tile grids, measured once when the plan is recorded "
+                                             "(DenoiseEngine._pick_xcd_cells, outside the timed region): 0 = byte-count model, "
+                                             "3 = 4 x 2, 2 = 8 x 1 cells over M x N; bit-identical results, box-dependent speed"},
+                       "tflop_per_unet_forward": tot_fl / 1e12},
+        }
+    if rank == 0 and a.full:
+        # ---- roofline of the dominant kernel family, timed with HIP events on the launch stream ----
         eng.eager.ew(L.EW_STEP_SET, eng.st.step, i=(0, 1, 0, 0, 0, 0), descr="step=0")
         ms = rec.time_ops()
         ms = [min(x, y) for x, y in zip(ms, rec.time_ops())]
@@ -645,7 +685,6 @@ def main():
         g_lds = sum(lds_operand_bytes(t[5], t[6]) for t in rec.tags if t[1] == L.OP_GEMM and t[5] is not None)
         g_lds_ms = sum(m for t, m in zip(rec.tags, ms) if t[1] == L.OP_GEMM and t[5] is not None)
         n_g = sum(1 for t in rec.tags if t[1] == L.OP_GEMM)
-        tot_fl = sum(t[3] for t in rec.tags)
         achieved = g_fl / (g_ms * 1e-3) / 1e12
         a_fl = sum(t[3] for t, m in zip(rec.tags, ms) if t[1] == L.OP_ATTN)
         a_ms = sum(m for t, m in zip(rec.tags, ms) if t[1] == L.OP_ATTN)
@@ -672,35 +711,8 @@ def main():
             traffic_src = f"profiles/{os.path.basename(pj)} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes of this command with --denoise-steps 4)"
         except (OSError, KeyError, ValueError, StopIteration):
             pass
-        images = a.steps * world
-        res = {
-            "metric": "1024^2 SDXL images/sec (30 DDIM steps, PNS N seeds)" if a.res == 1024 and a.denoise_steps == 30
-                      else f"{a.res}^2 SDXL images/sec ({a.denoise_steps} DDIM steps, PNS N seeds)",
-            "value": images / dt, "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"SDXL UNet {a.res}x{a.res}, {a.denoise_steps} DDIM steps, CFG 5.0 (UNet batch 2), "
-                                   f"IP-Adapter scale 1.0, {a.ip_tokens} image tokens, 1 PNS candidate seed per GPU per step",
-                       "parallelism": f"candidates sharded x{world} (no per-step collective)", "outputs_finite": finite,
-                       "distributed": {"world_size_reported_by_backend": dist.get_world_size() if world > 1 else 1,
-                                       "backend": dist.get_backend() if world > 1 else None,
-                                       "per_rank_ms_per_step": per_rank,
-                                       "collectives": collectives,
-                                       "devices_visible": torch.cuda.device_count()},
-                       "conditioning_prepare_ms": {"first_call": cond_ms[0], "later_calls": cond_ms[1:],
-                                                   "note": "DenoiseEngine.set_conditioning: K / V caches of the 70 cross-attention layers (140 small GEMMs "
-                                                           "+ 20 for the image-prompt tokens), add_embedding; once per image / per PNS run, shared by every "
-                                                           "candidate seed; not in `value`"},
-                       "value_counts": "denoised latents per second (the reference's output_type='latent'); the VAE decode + "
-                                       "post-processing tail (custom_pipelines.py:365-386) is NOT in `value` -- its time is "
-                                       "reported under vae_decode",
-                       "ms_per_unet_forward": dt / a.steps / a.denoise_steps * 1e3,
-                       "clocks_under_load": clocks,
-                       "xcd_cells": {"chosen": eng.xcd_cells, "ms_per_step_when_picked": getattr(eng, "xcd_times_ms", None),
-                                     "note": "XCD cell shape of the GEMM / conv tile grids, measured once when the plan is recorded "
-                                             "(DenoiseEngine._pick_xcd_cells, outside the timed region): 0 = byte-count model, "
-                                             "3 = 4 x 2, 2 = 8 x 1 cells over M x N; bit-identical results, box-dependent speed"},
-                       "tflop_per_unet_forward": tot_fl / 1e12},
+        res["config"]["clocks_under_load"] = clocks
+        res.update({
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": 2500.0, "unit": "TFLOP/s",
                          "frac": achieved / 2500.0,
                          "frac_at_sampled_clock": (achieved / (2500.0 * clocks["sclk_mhz"] / 2400.0)) if clocks else None,
@@ -726,7 +738,7 @@ def main():
                                         "operand tile bytes each workgroup stages (lds_operand_bytes).  Inside their K loops the one-workgroup-per-CU launches of "
                                         "the forward run AT this stream's rate for their bytes in flight -- 39 B/clk/CU = 90 GB/s with the 64 x 160 kernel's 84 KB "
                                         "(tools/micro/lds_port.hip, profiles/r05_lds_port_microbench.csv); the rest of a launch is ramp (DESIGN.md 3)"},
-        }
+        })
         if ip_us:
             kv_fl = 2.0 * 2 * 2 * (77 + a.ip_tokens) * 2048 * 1280          # text + ip K,V projections of one IP-active layer (CFG batch 2)
             per_call = sum(ip_fl) / len(ip_fl) + kv_fl / a.denoise_steps       # K/V counted once per image
@@ -843,9 +855,9 @@ def main():
                 res["resampler"] = {"error": f"{type(e).__name__}: {e}"}
         if world > 1:
             # the CPU baseline is a property of the box, timed on rank 0 of the N = 1 run only (it would steal host cores from N ranks'
-            # launch threads here); the field stays present so that every line carries it
+            # launch threads here); the field stays present so that every --full line carries it
             res["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": None, "kind": "port",
-                                   "sample": "see the N = 1 line of the same round (python bench.py --gpus 1): the fp32 CPU oracle, "
+                                   "sample": "see the N = 1 line of the same round (python bench.py --gpus 1 --full): the fp32 CPU oracle, "
                                              "1 warm-up + 2 timed 1024^2 CFG-2 UNet forwards x 30 steps"}
         if world == 1 and not a.no_cpu_baseline:
             try:
@@ -853,6 +865,7 @@ def main():
             except Exception as e:      # noqa: BLE001  -- the baseline is informational; never lose the GPU number
                 res["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": os.cpu_count(), "kind": "port",
                                        "sample": f"failed: {type(e).__name__}: {e}"}
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -13,8 +13,8 @@ python tools/vae_time.py > $out/r06_vae_decode_modes.txt 2>&1
 # ff.net.0 on 23256 x 160 (rounds 2-5) vs 26256 x 320 (round 6) in alternating PROCESSES (steady-state clocks, unlike forward_ab's short replays)
 OV='{"2048,10240,1280,0,1": [23256, 160, 1], "8192,5120,640,0,1": [23256, 160, 1]}'
 for i in 1 2; do
-  IMH_TUNING_OVERRIDE="$OV" python bench.py --steps 4 --warmup 2 --no-cpu-baseline --in-flight 1 --stacked 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ff.net.0 on 23256 x 160:', d['value'], 'images/sec', d['ms_per_step'], 'ms per denoise', d['config']['clocks_under_load'])"
-  python bench.py --steps 4 --warmup 2 --no-cpu-baseline --in-flight 1 --stacked 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ff.net.0 on 26256 x 320:', d['value'], 'images/sec', d['ms_per_step'], 'ms per denoise', d['config']['clocks_under_load'])"
+  IMH_TUNING_OVERRIDE="$OV" python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --in-flight 1 --stacked 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ff.net.0 on 23256 x 160:', d['value'], 'images/sec', d['ms_per_step'], 'ms per denoise', d['config']['clocks_under_load'])"
+  python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --in-flight 1 --stacked 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ff.net.0 on 26256 x 320:', d['value'], 'images/sec', d['ms_per_step'], 'ms per denoise', d['config']['clocks_under_load'])"
 done > $out/r06_bench_ab_geglu_w16.txt 2>&1
 python tools/forward_ab.py --rounds 4 --configs base,x1 --stacked 4 > $out/r06_forward_ab_xattn_wide_s4.json 2> $out/r06_forward_ab_xattn_wide_s4.log
 ls -la $out | grep r06_
