@@ -10,8 +10,8 @@ __version__ = "0.1.0"
 __all__ = ["IPAdapter", "IPAdapterPlus", "IPAdapterPlusXL", "IPAdapterXL", "IPAdapterFull"]
 
 
-# the pipelines, lazily too: text-to-image (custom_pipelines.py) and image-to-image (diffusers' SDXL img2img call surface)
-_PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline")
+# the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
+_PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline")
 
 
 def __getattr__(name):

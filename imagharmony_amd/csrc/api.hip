@@ -180,6 +180,7 @@ static int do_ew(int op, const imh_ew_args* a, hipStream_t s) {
     p.a = a->a; p.b = a->b; p.y = a->y; p.w = a->w; p.bias = a->bias; p.tab = a->tab; p.step = a->step; p.n = a->n;
     p.i0 = a->i0; p.i1 = a->i1; p.i2 = a->i2; p.i3 = a->i3; p.i4 = a->i4; p.i5 = a->i5;
     p.f0 = a->f0; p.f1 = a->f1; p.f2 = a->f2; p.f3 = a->f3;
+    p.x2 = a->x2; p.noise = a->noise; p.mask = a->mask; p.blend_tab = a->blend_tab;
     return ew_launch(op, p, a->dtype, s);
 }
 

@@ -2,11 +2,13 @@
 //   EW_TIMESTEP   diffusers Timesteps(dim, flip_sin_to_cos=True, shift 0)      
 //   EW_SILU       SiLU on the time embedding before time_emb_proj               (App. A ResnetBlock2D)
 //   EW_CONCAT     channel concat of NHWC tensors (up-block skip connections)    (App. A.6)
-//   EW_CONV_IN    conv_in 3x3 (4 -> C0) reading NCHW fp32 latents, fusing CFG duplication
-//                 (custom_pipelines.py:332) and scale_model_input (:334); writes NHWC
+//   EW_CONV_IN    conv_in 3x3 (4 | 9 -> C0) reading NCHW fp32 latents, fusing CFG duplication
+//                 (custom_pipelines.py:332) and scale_model_input (:334); writes NHWC; with 9 channels (the SDXL inpainting
+//                 UNet) the last five, [mask | masked-image latents], come from a second, step-invariant buffer
 //   EW_CFG_STEP   CFG combine (custom_pipelines.py:348-350) + linear scheduler update
 //                 x' = cx*x + ce*eps (DDIM eta=0 / Euler), noise pred read
-//                 NHWC, latents kept NCHW fp32 (custom_pipelines.py:357)
+//                 NHWC, latents kept NCHW fp32 (custom_pipelines.py:357); optionally followed in the same pass by the
+//                 masked blend of SDXL inpainting on a 4-channel UNet
 //   EW_CFG_RESCALE per-sample factor of rescale_noise_cfg (custom_pipelines.py:351-354; arXiv 2305.08891 3.4):
 //                 phi * std(eps_text) / std(eps_cfg) + (1 - phi), consumed by EW_CFG_STEP through `w`
 //   EW_SOFTMAX    row softmax of fp32 scores -> T probabilities (the VAE mid-block attention: one head of width
@@ -82,24 +84,30 @@ __global__ void concat_kernel(const EwParams p) {
     }
 }
 
-// conv_in: a = latents fp32 NCHW [S, 4, H, W]; w = weights T [C0][4][3][3]; bias T [C0];
+// conv_in: a = latents fp32 NCHW [S, 4, H, W]; w = weights T [C0][CIN][3][3]; bias T [C0];
 // y = NHWC T [Bout, H, W, C0] with Bout = i4 (batch b reads latent b % S: CFG duplication).
 // i0 = S, i1 = H, i2 = W, i3 = C0, f0 = input scale.  Eight threads per pixel, each 8 channels at a time.
-template <typename T>
-__global__ __launch_bounds__(256) void conv_in_kernel(const EwParams p) {
+// CIN = 9 (the SDXL inpainting UNet, diffusers StableDiffusionXLInpaintPipeline: cat([scaled latents, mask, masked_image_latents], 1)):
+// channels 4-8 come from x2, fp32 NCHW [S, 5, H, W], NOT scaled (scale_model_input is applied before the concat) and rounded to T like
+// the latents.  The weight tile stays fp32 in LDS, (81 + 1) * C0 * 4 B = 105 KB at C0 = 320 of the 160 KiB a workgroup may have -- one
+// workgroup per CU instead of three, so it has 512 threads (two waves per SIMD, 256 VGPRs each: the 81 taps stay in registers); 16-bit weights in LDS would add a conversion per
+// multiply-add to the inner loop of a VALU-bound kernel.  The CIN = 4 instantiation is the kernel as it was.
+template <typename T, int CIN>
+__global__ __launch_bounds__(CIN > 4 ? 512 : 256) void conv_in_kernel(const EwParams p) {
     typedef typename Vec<T>::v8 v8;
-    extern __shared__ float wl[];   // [36][C0] transposed weights, then [C0] bias
+    constexpr int KT = CIN * 9;
+    extern __shared__ float wl[];   // [KT][C0] transposed weights, then [C0] bias
     const int S = p.i0, H = p.i1, W = p.i2, C0 = p.i3, Bout = p.i4;
     const T* w = (const T*)p.w;
-    for (int co = threadIdx.x; co < C0; co += blockDim.x) {      // one output channel (36 contiguous taps) per thread
+    for (int co = threadIdx.x; co < C0; co += blockDim.x) {      // one output channel (KT contiguous taps) per thread
 #pragma unroll
-        for (int k = 0; k < 36; ++k) wl[k * C0 + co] = to_f32(w[co * 36 + k]);
+        for (int k = 0; k < KT; ++k) wl[k * C0 + co] = to_f32(w[co * KT + k]);
     }
-    for (int i = threadIdx.x; i < C0; i += blockDim.x) wl[36 * C0 + i] = p.bias ? to_f32(((const T*)p.bias)[i]) : 0.f;
+    for (int i = threadIdx.x; i < C0; i += blockDim.x) wl[KT * C0 + i] = p.bias ? to_f32(((const T*)p.bias)[i]) : 0.f;
     __syncthreads();
     const int cg = C0 >> 3;
     const float in_scale = p.tab ? p.tab[*p.step] : p.f0;
-    // 8 threads per pixel: each fetches the pixel's 36 taps once (all loads in flight together; the 8 copies hit
+    // 8 threads per pixel: each fetches the pixel's KT taps once (all loads in flight together; the 8 copies hit
     // L1), then produces the channel octets l8, l8+8, .. -- the 8 threads of a pixel store 128 contiguous bytes
     const long long total = (long long)Bout * H * W * 8;
     const float* lat = (const float*)p.a;
@@ -110,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const EwParams p) {
         const int y = (int)((pix / W) % H);
         const int b = (int)(pix / ((long long)W * H));
         const float* src = lat + (size_t)(b % S) * 4 * H * W;
-        float tap[36];
+        float tap[KT];
 #pragma unroll
         for (int ci = 0; ci < 4; ++ci)
 #pragma unroll
@@ -123,12 +131,26 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const EwParams p) {
                     // the model sees the latent rounded to the compute dtype (pipeline casts latents)
                     tap[ci * 9 + ky * 3 + kx] = to_f32(from_f32<T>(v));
                 }
+        if constexpr (CIN > 4) {
+            const float* src2 = p.x2 + (size_t)(b % S) * (CIN - 4) * H * W;
+#pragma unroll
+            for (int ci = 4; ci < CIN; ++ci)
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const int iy = y + ky - 1, ix = x + kx - 1;
+                        const bool in = iy >= 0 && iy < H && ix >= 0 && ix < W;
+                        const float v = in ? src2[((size_t)(ci - 4) * H + iy) * W + ix] : 0.f;
+                        tap[ci * 9 + ky * 3 + kx] = to_f32(from_f32<T>(v));
+                    }
+        }
         for (int c8 = l8; c8 < cg; c8 += 8) {
             float acc[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = wl[36 * C0 + c8 * 8 + e];
+            for (int e = 0; e < 8; ++e) acc[e] = wl[KT * C0 + c8 * 8 + e];
 #pragma unroll
-            for (int k = 0; k < 36; ++k) {
+            for (int k = 0; k < KT; ++k) {
                 const float* wr = wl + k * C0 + c8 * 8;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] += tap[k] * wr[e];
@@ -141,7 +163,11 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const EwParams p) {
     }
 }
 
-template <typename T>
+// BLEND (imh.h IMH_EW_CFG_STEP with `mask`): after the update, the masked blend of diffusers StableDiffusionXLInpaintPipeline.__call__
+// (num_channels_unet == 4): latents = (1 - m) * add_noise(z, n, timesteps[i + 1]) + m * latents, with add_noise's pair read from
+// blend_tab[*step] ((1, 0) in the last row that runs: the image latents themselves).  Same pass, same launch; a == NULL: the blend alone.
+// The plain instantiation is the kernel as it was.
+template <typename T, bool BLEND>
 __global__ void cfg_step_kernel(const EwParams p) {
     const int S = p.i0, HW = p.i1;
     const long long total = (long long)S * HW * 4;
@@ -149,21 +175,30 @@ __global__ void cfg_step_kernel(const EwParams p) {
     float* lat = (float*)p.y;
     const float cx = p.tab ? p.tab[*p.step * 2] : p.f0;
     const float ce = p.tab ? p.tab[*p.step * 2 + 1] : p.f1;
+    float ba = 0.f, bb = 0.f;
+    if constexpr (BLEND) { ba = p.blend_tab[*p.step * 2]; bb = p.blend_tab[*p.step * 2 + 1]; }
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int pix = (int)(i % HW);
         const int ch = (int)((i / HW) % 4);
         const int s = (int)(i / ((long long)HW * 4));
-        float eps;
-        if (p.i3) {
-            const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + ch]);
-            const float c = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + ch]);
-            eps = u + p.f2 * (c - u);
-        } else {
-            eps = to_f32(np_[((size_t)s * HW + pix) * 4 + ch]);
+        if (!BLEND || np_) {
+            float eps;
+            if (p.i3) {
+                const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + ch]);
+                const float c = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + ch]);
+                eps = u + p.f2 * (c - u);
+            } else {
+                eps = to_f32(np_[((size_t)s * HW + pix) * 4 + ch]);
+            }
+            if (p.w) eps *= ((const float*)p.w)[s];        // guidance_rescale factor of this sample (EW_CFG_RESCALE)
+            if (p.b) ((float*)p.b)[i] = eps;
+            lat[i] = cx * lat[i] + ce * eps;
         }
-        if (p.w) eps *= ((const float*)p.w)[s];        // guidance_rescale factor of this sample (EW_CFG_RESCALE)
-        if (p.b) ((float*)p.b)[i] = eps;
-        lat[i] = cx * lat[i] + ce * eps;
+        if constexpr (BLEND) {
+            const float m = p.mask[(size_t)(s % p.i4) * HW + pix];
+            const float pv = ba * p.x2[i] + bb * p.noise[i];
+            lat[i] = (1.0f - m) * pv + m * lat[i];
+        }
     }
 }
 
@@ -311,14 +346,35 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
             break;
         case EW_CONV_IN: {
             if (p.i3 & 7) { set_error("conv_in: C0 must be a multiple of 8"); return IMH_ERR_SHAPE; }
-            const size_t lds = (size_t)(37 * p.i3) * sizeof(float);
             const long long work = (long long)p.i4 * p.i1 * p.i2 * 8;
+            if (p.i5 == 9) {
+                // the 9-channel form (imh.h): (81 + 1) * C0 floats of LDS, above the 64 KB default from C0 = 200 on, within a workgroup's
+                // 160 KiB up to C0 = 496; one persistent 512-thread workgroup per CU there, three while three fit
+                static DynLdsOnce once;          // (per T: ew_typed is a template)
+                const size_t lds = (size_t)(82 * p.i3) * sizeof(float);
+                if (!p.x2 || p.i0 <= 0) { set_error("conv_in: 9 input channels need the second source x2 [S, 5, H, W]"); return IMH_ERR_ARG; }
+                if (lds > 160 * 1024) { set_error("conv_in: C0 = %d needs %zu bytes of LDS at 9 input channels (160 KiB per workgroup)", p.i3, lds); return IMH_ERR_SHAPE; }
+                if (lds > 64 * 1024) once.ensure((const void*)conv_in_kernel<T, 9>, 160 * 1024);
+                hipLaunchKernelGGL((conv_in_kernel<T, 9>), dim3(std::min(grid_for(work, 512), lds > 53 * 1024 ? 256 : 768)), dim3(512), lds, stream, p);
+                break;
+            }
+            if (p.i5 != 0 && p.i5 != 4) { set_error("conv_in: %d input channels (4 or 9)", p.i5); return IMH_ERR_ARG; }
+            const size_t lds = (size_t)(37 * p.i3) * sizeof(float);
             // persistent workgroups (3 per CU by LDS): the 46 KB weight transpose is paid 768 times, not once per 1024 outputs
-            hipLaunchKernelGGL((conv_in_kernel<T>), dim3(std::min(grid_for(work, 256), 768)), dim3(256), lds, stream, p);
+            hipLaunchKernelGGL((conv_in_kernel<T, 4>), dim3(std::min(grid_for(work, 256), 768)), dim3(256), lds, stream, p);
             break;
         }
         case EW_CFG_STEP:
-            hipLaunchKernelGGL((cfg_step_kernel<T>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+            if (p.mask) {
+                if (!p.x2 || !p.noise || !p.blend_tab || !p.step || p.i4 < 1) {
+                    set_error("cfg_step: the masked blend needs x2 (image latents), noise, blend_tab, step and i4 = mask batch >= 1");
+                    return IMH_ERR_ARG;
+                }
+                hipLaunchKernelGGL((cfg_step_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+                break;
+            }
+            if (!p.a) { set_error("cfg_step: null noise prediction"); return IMH_ERR_ARG; }
+            hipLaunchKernelGGL((cfg_step_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
             break;
         case EW_CFG_RESCALE:
             if (p.i0 <= 0 || p.i1 <= 0) { set_error("cfg_rescale: empty problem"); return IMH_ERR_SHAPE; }

@@ -171,6 +171,10 @@ struct EwParams {
     long long n;
     int i0, i1, i2, i3, i4, i5;
     float f0, f1, f2, f3;
+    const float* x2;         // conv_in: channels 4-8 (step-invariant); cfg_step blend: image latents
+    const float* noise;      // cfg_step blend: add-noise noise
+    const float* mask;       // cfg_step blend: latent mask (selects the blend)
+    const float* blend_tab;  // cfg_step blend: (a, b) rows indexed by *step
 };
 int ew_launch(int op, const EwParams& p, int dtype, hipStream_t stream);
 

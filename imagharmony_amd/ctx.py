@@ -791,15 +791,22 @@ class Ctx:
 
     # ------------------------------------------------------------------ elementwise
     def ew(self, op, y, a=None, b=None, w=None, bias=None, tab=None, step=None, n=0, i=(0, 0, 0, 0, 0, 0),
-           f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0):
+           f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0, x2=None, noise=None, mask=None, blend_tab=None):
+        """x2 / noise / mask / blend_tab (fp32, imh.h ABI 11): conv_in's second source, the masked blend behind the CFG step"""
         e = L.EwArgs()
         e.a, e.b, e.y, e.w, e.bias = self._p(a), self._p(b), y.data_ptr(), self._p(w), self._p(bias)
         e.tab, e.step = self._p(tab), self._p(step)
+        for t, nm in ((x2, "x2"), (noise, "noise"), (mask, "mask"), (blend_tab, "blend_tab")):
+            if t is not None:
+                self._chk(t, f"{descr}.{nm}", torch.float32)
+                if not t.is_contiguous():
+                    raise L.ImhError(f"{descr}: {nm} must be contiguous")
+        e.x2, e.noise, e.mask, e.blend_tab = self._p(x2), self._p(noise), self._p(mask), self._p(blend_tab)
         e.n = n
         e.i0, e.i1, e.i2, e.i3, e.i4, e.i5 = i
         e.f0, e.f1, e.f2, e.f3 = f
         e.dtype = self.dt
-        self._emit(L.OP_EW, e, ew_op=op, descr=descr, nbytes=nbytes, keep=(a, b, y, w, bias, tab, step))
+        self._emit(L.OP_EW, e, ew_op=op, descr=descr, nbytes=nbytes, keep=(a, b, y, w, bias, tab, step, x2, noise, mask, blend_tab))
         return y
 
     def silu(self, x, descr="silu"):

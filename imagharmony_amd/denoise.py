@@ -4,7 +4,10 @@ One denoise step = [UNet forward on the CFG-duplicated latent] + [CFG combine + 
 [step counter += 1], recorded ONCE into a C++ plan and captured into a hipGraph; the 30-step loop is
 30 graph replays with no host work in between: timesteps, scheduler coefficients, the Euler input
 scale and the per-step IP-scale gate (control_guidance_start/end, custom_pipelines.py:326-329) are
-device tables indexed by a device-resident step counter.
+device tables indexed by a device-resident step counter.  Inpainting (diffusers StableDiffusionXLInpaintPipeline) keeps that shape: the
+masked blend upstream applies on the host after every scheduler.step is part of the recorded step (it rides in the CFG + scheduler
+launch and reads its add_noise pair from one more table), and a 9-channel UNet reads [mask | masked-image latents] from a
+step-invariant buffer inside conv_in.
 """
 import hashlib
 import os
@@ -40,6 +43,7 @@ class DenoiseEngine:
         self.max_cached_plans = int(os.environ.get("IMH_MAX_CACHED_PLANS", "3"))      # each pins ~2 GB of activation buffers at 1024^2
         self._sched_key = None
         self.t_start = 0         # image-to-image: the first step of the schedule that runs (set_schedule)
+        self.inpaint = None      # None | "blend" (4-channel UNet: masked blend in the step) | "concat" (9-channel UNet: conv_in reads the mask)
 
     # -- conditioning (once per image / per PNS run; shared by every candidate seed) --
     @torch.no_grad()
@@ -82,15 +86,23 @@ class DenoiseEngine:
         old = self.st
         self.st = st
         if old is not None:                      # keep per-run tables
-            for k in ("latents", "t_table", "step", "in_scale_tab", "ip_scale_tab", "coef_tab"):
+            for k in ("latents", "t_table", "step", "in_scale_tab", "ip_scale_tab", "coef_tab", "blend_tab") + self._INPAINT_BUFFERS:
                 setattr(st, k, getattr(old, k, None))
         self.plan = None                         # conditioning buffers changed -> re-record
         return st
 
+    # inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
+    _INPAINT_BUFFERS = ("inp_z", "inp_noise", "inp_mask", "conv_in_extra")
+
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
-                     denoising_end=None, t_start=0):
-        """t_start > 0 (image-to-image, diffusers get_timesteps): the loop runs timesteps[t_start:] -- the device step counter starts at
+                     denoising_end=None, t_start=0, inpaint=False):
+        """inpaint: the schedule of an inpainting call (prepare_inpaint).  On a 4-channel UNet every step then ends with upstream's masked
+        blend, latents = (1 - m) * add_noise(z, n, timesteps[i + 1]) + m * latents, whose add_noise pair comes from blend_tab: row r holds
+        scheduler.add_noise_coefficients(r + 1), the last row that runs (1, 0) -- the image latents themselves.  On a 9-channel UNet there is
+        no blend; conv_in reads the mask and the masked-image latents.  Either way the plan differs from the text-to-image one under the
+        same schedule, so the mode is part of the plan key.
+        t_start > 0 (image-to-image, diffusers get_timesteps): the loop runs timesteps[t_start:] -- the device step counter starts at
         t_start, so the full schedule's tables, time-embedding rows and recorded plan serve; denoising_end then cuts the truncated list
         and the IP-scale gating window counts it"""
         st, dev = self.st, self.device
@@ -121,13 +133,17 @@ class DenoiseEngine:
                                           for i in range(m)]
         # the gating table is part of what the recorded plan reads: its fingerprint is part of the key
         fp.update(torch.tensor(gate, dtype=torch.float32).numpy().tobytes())
-        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest())
+        mode = None
+        if inpaint:
+            mode = "concat" if self.unet.config.in_channels == 9 else "blend"
+        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), mode)
         self.t_start = t_start
+        self.inpaint = mode
         hit = self._plans.get(key)
         if hit is not None:
             # a schedule this engine has run under this conditioning: its tables, time-embedding rows and recorded plan are still there
             # (the plan's launches point at them), so a preview / final alternation re-records nothing
-            for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table"):
+            for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab"):
                 setattr(st, k, hit["st"][k])
             self.steps, self.init_noise_sigma = hit["steps"], hit["init_noise_sigma"]
             self.plan, self.noise_pred, self._temb_ctx = hit["plan"], hit["noise_pred"], hit["temb_ctx"]
@@ -138,12 +154,22 @@ class DenoiseEngine:
         st.coef_tab = tab["coef"].contiguous().to(dev)
         st.in_scale_tab = tab["in_scale"].to(dev) if tab["in_scale"] is not None else None
         st.ip_scale_tab = torch.tensor(gate, dtype=torch.float32, device=dev)
+        st.blend_tab = self.blend_table(scheduler, num_inference_steps, n).to(dev) if mode == "blend" else None
         if st.step is None:
             st.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.steps = n
         self.init_noise_sigma = float(tab["init_noise_sigma"])
         self.plan = None                         # table pointers changed
         self._sched_key = key
+
+    @staticmethod
+    def blend_table(scheduler, num_inference_steps, n):
+        """fp32 [num_inference_steps, 2]: row r = scheduler.add_noise_coefficients(r + 1) -- upstream's add_noise(image_latents, noise,
+        timesteps[i + 1]) after step i (DDIM: alphas_cumprod[t]; Euler after set_begin_index and one step: sigmas[step_index]) -- and
+        (1, 0) from row n - 1 on: after the last step that runs (n as set_schedule counts it under denoising_end) the unmasked region
+        is the image latents themselves.  The scheduler's timesteps must be set."""
+        rows = [scheduler.add_noise_coefficients(r + 1) if r < n - 1 else (1.0, 0.0) for r in range(int(num_inference_steps))]
+        return torch.tensor(rows, dtype=torch.float32)
 
     def fork(self):
         """A second engine on the SAME weights and the SAME conditioning (K/V caches, aug_emb) with its own latents,
@@ -152,12 +178,13 @@ class DenoiseEngine:
         e = DenoiseEngine(self.unet, self.device, self.dtype, self.use_graph)
         e._is_fork = True                        # never tunes: it may record while its parent is running on another stream
         for k in ("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
-                  "xcd_candidates", "xcd_cells", "t_start"):
+                  "xcd_candidates", "xcd_cells", "t_start", "inpaint"):
             setattr(e, k, getattr(self, k))
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
         st.t_table, st.coef_tab, st.in_scale_tab, st.ip_scale_tab = src.t_table, src.coef_tab, src.in_scale_tab, src.ip_scale_tab
+        st.blend_tab = getattr(src, "blend_tab", None)               # (the mask, image latents and noise are the fork's own: _record)
         st.step = torch.zeros(1, dtype=torch.int32, device=self.device)
         e.st = st
         return e
@@ -166,10 +193,18 @@ class DenoiseEngine:
         st = self.st
         if st.latents is None or tuple(st.latents.shape) != (self.S, 4, self.H, self.W):
             st.latents = torch.zeros(self.S, 4, self.H, self.W, dtype=torch.float32, device=self.device)
+        split = self.do_cfg and getattr(self, "cfg_role", None) is not None
+        if self.inpaint and split:
+            raise NotImplementedError("inpainting runs on an engine that holds both halves of the CFG pair (cfg_role = None)")
+        if self.unet.config.in_channels == 9 and self.inpaint != "concat":
+            raise L.ImhError("a UNet with in_channels = 9 runs inpainting schedules only (set_schedule(..., inpaint=True), prepare_inpaint)")
+        want = {"blend": (("inp_z", 4), ("inp_noise", 4), ("inp_mask", 1)), "concat": (("conv_in_extra", 5),)}.get(self.inpaint, ())
+        for k, c in want:
+            if getattr(st, k, None) is None or tuple(getattr(st, k).shape) != (self.S, c, self.H, self.W):
+                setattr(st, k, torch.zeros(self.S, c, self.H, self.W, dtype=torch.float32, device=self.device))
         # the time-embedding rows of every step of this schedule under this conditioning: once here, not five launches per step
         self._temb_ctx = Ctx(self.device, self.dtype)          # (its pool owns the table for the life of the plan)
         self.unet.precompute_temb(self._temb_ctx, st, st.t_table)
-        split = self.do_cfg and getattr(self, "cfg_role", None) is not None
         if not split and self.use_graph and len(self.xcd_candidates) > 1 and self.xcd_cells is None:
             pk = (self.device.index or 0, self.S, self.H, self.W, str(self.dtype), bool(self.do_cfg))
             if pk not in _XCD_PICK and not self._is_fork:
@@ -207,8 +242,14 @@ class DenoiseEngine:
             fac = rec.new(self.S, dtype=torch.float32)
             rec.ew(L.EW_CFG_RESCALE, fac, a=out, i=(self.S, self.H * self.W, 0, 0, 0, 0),
                    f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
-        rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
-               i=(self.S, self.H * self.W, 0, int(self.do_cfg), 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
+        if self.inpaint == "blend":
+            # ... and upstream's masked blend in the same launch (imh.h IMH_EW_CFG_STEP): no extra launch, no extra pass over the latents
+            rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
+                   i=(self.S, self.H * self.W, 0, int(self.do_cfg), self.S, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step+blend",
+                   x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab)
+        else:
+            rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
+                   i=(self.S, self.H * self.W, 0, int(self.do_cfg), 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
         rec.ew(L.EW_STEP_SET, st.step, i=(0, 0, 0, 0, 0, 0), descr="step++")
         if self.use_graph:
             rec.capture()
@@ -221,7 +262,7 @@ class DenoiseEngine:
             return
         st = self.st
         self._plans[self._sched_key] = dict(
-            st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table")},
+            st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab")},
             steps=self.steps, init_noise_sigma=self.init_noise_sigma, plan=self.plan, noise_pred=self.noise_pred,
             temb_ctx=self._temb_ctx, plan_tail=getattr(self, "plan_tail", None), np_full=getattr(self, "np_full", None))
         while len(self._plans) > self.max_cached_plans:              # (each plan keeps ~2 GB of activation buffers alive at 1024^2)
@@ -263,8 +304,8 @@ class DenoiseEngine:
         noise x the full denoise) is then `steps` batch-S forwards deep instead of batch-2S ones."""
         if getattr(self, "cfg_role", None) is None or not self.do_cfg:
             raise L.ImhError("denoise_cfg_split needs an engine whose conditioning was set with cfg_role = 0 / 1 and guidance > 1")
-        if self.t_start:
-            raise NotImplementedError("denoise_cfg_split runs whole schedules (t_start = 0)")
+        if self.t_start or self.inpaint:
+            raise NotImplementedError("denoise_cfg_split runs whole text-to-image schedules (t_start = 0, no inpainting)")
         if self.plan is None:
             self._record()
         st = self.st
@@ -292,6 +333,44 @@ class DenoiseEngine:
         return st.latents
 
     @torch.no_grad()
+    def prepare_inpaint(self, moments, n1, n2, scaling, add_a, add_b, mask, strength_max=False, masked_moments=None, n3=None):
+        """inpainting state and initial latents (diffusers StableDiffusionXLInpaintPipeline.prepare_latents / prepare_mask_latents), copied
+        into the buffers the recorded plan points at; under set_schedule(..., inpaint=True).  moments / n1 / n2 / scaling as
+        prepare_img2img; mask: the latent mask [M, 1, h, w] of zeros and ones (1 = repaint; sample s reads mask s % M).
+        Initial latents: add_noise(z, n2, t_start) = add_a * z + add_b * n2, or with strength_max (upstream's is_strength_max, strength
+        == 1) n2 * init_noise_sigma.  4-channel UNet: the image latents z (the init op with (a, b) = (1, 0)), n2 and the mask feed the
+        blend of every step.  9-channel UNet: masked_moments / n3 = the encoder moments and posterior noise of the masked image; conv_in
+        reads [mask | scaling * posterior sample] at every step (moments / n1 may be None with strength_max: nothing reads z).
+        Then denoise(None)."""
+        if not self.inpaint:
+            raise L.ImhError("prepare_inpaint needs an inpainting schedule: set_schedule(..., inpaint=True)")
+        if self.plan is None:
+            self._record()
+        st, dev = self.st, self.device
+        f32 = lambda t: t.to(dev, torch.float32).contiguous()
+        S, H, W = self.S, self.H, self.W
+        if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, H, W) or S % mask.shape[0]:
+            raise L.ImhError(f"prepare_inpaint: latent mask {tuple(mask.shape)} for {S} samples of {H} x {W}")
+        mask = f32(mask).repeat(S // mask.shape[0], 1, 1, 1)
+        n2 = f32(n2)
+        if strength_max:
+            st.latents.copy_(n2 * self.init_noise_sigma)
+        else:
+            self.eager.img2img_init(st.latents, f32(moments), f32(n1), n2, scaling, add_a, add_b)
+        if self.inpaint == "blend":
+            self.eager.img2img_init(st.inp_z, f32(moments), f32(n1), n2, scaling, 1.0, 0.0, descr="inpaint.z")
+            st.inp_noise.copy_(n2)
+            st.inp_mask.copy_(mask)
+        else:
+            if masked_moments is None or n3 is None:
+                raise L.ImhError("prepare_inpaint: a 9-channel UNet needs the masked image's moments and posterior noise")
+            mz = torch.empty(S, 4, H, W, dtype=torch.float32, device=dev)
+            self.eager.img2img_init(mz, f32(masked_moments), f32(n3), n2, scaling, 1.0, 0.0, descr="inpaint.masked_z")
+            st.conv_in_extra[:, :1].copy_(mask)
+            st.conv_in_extra[:, 1:].copy_(mz)
+        return st.latents
+
+    @torch.no_grad()
     def denoise(self, latents, callback=None, callback_steps=1):
         """latents: [S, 4, H/8, W/8] unit-variance noise (CPU or device), or None: the latent buffer already holds the initial latents
         (prepare_img2img).  Runs the steps t_start .. steps - 1 of the schedule (t_start = 0 unless set_schedule was given one).  Returns
@@ -299,9 +378,11 @@ class DenoiseEngine:
         steps (:359-363; i counts the steps that run from 0) is the only thing that makes the host wait inside the loop."""
         if getattr(self, "cfg_role", None) is not None and self.do_cfg:
             raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
+        if self.inpaint and latents is not None:
+            raise L.ImhError("an inpainting schedule starts from prepare_inpaint: denoise(None)")
         if self.plan is None:
             if latents is None:
-                raise L.ImhError("denoise(None) needs the initial latents in place (prepare_img2img) under the current schedule")
+                raise L.ImhError("denoise(None) needs the initial latents in place (prepare_img2img / prepare_inpaint) under the current schedule")
             self._record()
         st = self.st
         if latents is not None:

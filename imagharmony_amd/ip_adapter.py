@@ -252,11 +252,11 @@ class IPAdapterXL(IPAdapter):
         ``batch`` = preview candidates stacked per UNet forward on a rank; None (default) = as many as the rank holds, up
         to 4 (BASELINE.json configs[4] runs 4 per GPU): a stacked forward costs 1.27x less per candidate than one at a
         time on MI355X (bench.py ``stacked_candidates`` / ``pns_two_stage``); the final denoise is batch 1 either way.
-        Returns dict(images, best_seed, scores, latents).  Text-to-image only: an image-to-image pipeline raises NotImplementedError."""
+        Returns dict(images, best_seed, scores, latents).  Text-to-image only: an image-to-image or inpainting pipeline raises NotImplementedError."""
         from . import pns
-        from .pipeline import StableDiffusionXLImg2ImgCustomPipeline
-        if isinstance(self.pipe, StableDiffusionXLImg2ImgCustomPipeline):
-            raise NotImplementedError("generate_pns runs text-to-image schedules; image-to-image PNS is not supported")
+        from .pipeline import StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline
+        if isinstance(self.pipe, (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline)):
+            raise NotImplementedError("generate_pns runs text-to-image schedules; image-to-image and inpainting PNS are not supported")
         self.set_scale(scale)
         pipe = self.pipe
         prompt = prompt if prompt is not None else "best quality, high quality"

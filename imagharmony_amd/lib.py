@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _EXP_PATH = os.path.join(_HERE, "..", "tools", "tmp_libs", "libimh_hip_experimental.so")
 LIB_PATH = os.environ.get("IMH_LIB_PATH") or (_EXP_PATH if os.environ.get("IMH_EXPERIMENTAL") == "1" else os.path.join(_HERE, "libimh_hip.so"))
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 IMH_DT_BF16, IMH_DT_F16 = 0, 1
 GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL = 1, 2, 4, 8, 16, 32, 64
 OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN = 0, 1, 2, 3, 4, 5, 6, 7
@@ -92,7 +92,8 @@ class EwArgs(C.Structure):
     _fields_ = [("a", _vp), ("b", _vp), ("y", _vp), ("w", _vp), ("bias", _vp), ("tab", _vp), ("step", _vp),
                 ("n", C.c_int64),
                 ("i0", _i32), ("i1", _i32), ("i2", _i32), ("i3", _i32), ("i4", _i32), ("i5", _i32),
-                ("f0", _f32), ("f1", _f32), ("f2", _f32), ("f3", _f32), ("dtype", _i32)]
+                ("f0", _f32), ("f1", _f32), ("f2", _f32), ("f3", _f32), ("dtype", _i32),
+                ("x2", _vp), ("noise", _vp), ("mask", _vp), ("blend_tab", _vp)]
 
 
 class F32Args(C.Structure):

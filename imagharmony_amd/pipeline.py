@@ -212,3 +212,117 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
         out = eng.denoise(None, callback=callback, callback_steps=callback_steps).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+
+
+class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
+    """SDXL inpainting with diffusers' ``StableDiffusionXLInpaintPipeline`` call surface (0.30) for what this path supports: the edit is
+    confined to ``mask_image`` (white = repaint).  The mode follows ``unet.config.in_channels`` as upstream's ``num_channels_unet``:
+
+    * 4 (SDXL base): after every step the region outside the mask is replaced by the init image's latents, noised to the next
+      timestep (``__call__``: ``latents = (1 - init_mask) * init_latents_proper + init_mask * latents``) -- here inside the recorded
+      step, in the CFG + scheduler launch, so the loop stays graph replays with no host work;
+    * 9 (the published SDXL inpainting UNet): conv_in reads ``cat([scale_model_input(latents), mask, masked_image_latents], 1)``; no
+      blend.
+
+    The image and (9 channels) the masked image are encoded by the HIP VAE encoder (``vae=AutoencoderKL(..., with_encoder=True)``).
+    Draws from ``generator`` (one, or a list with one per sample), in upstream's order: the posterior noise of ``image``
+    (prepare_latents), the add-noise noise, then -- 9 channels only -- the posterior noise of ``masked_image`` (prepare_mask_latents).
+    Upstream also encodes the masked image and makes the third draw for a 4-channel UNet, where nothing reads the result: this path
+    skips both.  With a 9-channel UNet at ``strength == 1.0`` nothing reads the image latents either: the encoder pass is skipped, the
+    first draw is still made so that the order above holds in every mode.  ``IPAdapterXL(pipe, ...).generate(pil_image=..., image=init,
+    mask_image=mask, strength=...)`` reaches this class through its **kwargs.
+
+    Not supported: soft masks (``mask_processor.blur``), ``padding_mask_crop`` / ``apply_overlay``, the refiner hand-off.  Known
+    difference, as for image-to-image: the latents stay fp32 where diffusers rounds them to the pipeline dtype."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, mask_image=None, masked_image_latents=None, height=None, width=None,
+                 padding_mask_crop=None, strength: float = 0.9999, num_inference_steps: int = 50, denoising_start=None,
+                 denoising_end: Optional[float] = None, guidance_scale: float = 7.5, negative_prompt=None,
+                 num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents=None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+                 callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, **kwargs):
+        """height / width default to the preprocessed image's size (anything else is refused: resize the image first).
+        aesthetic_score / negative_aesthetic_score are accepted and unused, as for image-to-image.
+        Refused before any GPU work -- NotImplementedError: padding_mask_crop, masked_image_latents=, a 4-channel latent ``image``,
+        latents=, denoising_start, eta != 0; ValueError: no image, no mask_image, a mask that cannot be brought to the image's size and
+        batch, strength outside [0, 1] or a schedule that truncates to no step."""
+        if denoising_start is not None:
+            raise NotImplementedError("denoising_start (the refiner hand-off) is not supported on this path")
+        if padding_mask_crop is not None:
+            raise NotImplementedError("padding_mask_crop (crop, inpaint, overlay) is not supported on this path")
+        if masked_image_latents is not None:
+            raise NotImplementedError("masked_image_latents= is not supported: the masked image is encoded from `image` and `mask_image`")
+        self._refuse(output_type, eta, kwargs)
+        if latents is not None:
+            raise NotImplementedError("latents= is not supported by the inpainting path: the initial latents come from `image`")
+        if image is None:
+            raise ValueError("inpainting needs `image` (PIL, a list of PIL images or a tensor [B, 3, H, W])")
+        if mask_image is None:
+            raise ValueError("inpainting needs `mask_image` (PIL, a list of PIL images or a tensor; white = repaint)")
+        if torch.is_tensor(image) and image.dim() >= 3 and image.shape[-3] == 4:
+            raise NotImplementedError("a 4-channel latent `image` is not supported: pass the image itself")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
+        from .vae import latent_mask, preprocess, preprocess_mask
+        img = preprocess(image)                                              # image_processor.preprocess
+        if (height or img.shape[2], width or img.shape[3]) != tuple(img.shape[2:]):
+            raise NotImplementedError(f"height / width {height} x {width} differ from the image's {img.shape[2]} x {img.shape[3]}: resize the image first")
+        height, width = img.shape[2], img.shape[3]
+        mask = preprocess_mask(mask_image, height, width)                    # mask_processor.preprocess
+        cin = self.unet.config.in_channels                                   # num_channels_unet
+        if self.vae is None or not getattr(self.vae, "with_encoder", False):
+            raise NotImplementedError("inpainting needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
+        if prompt_embeds is None:
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
+                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
+        if pooled_prompt_embeds is None:
+            raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
+        S = prompt_embeds.shape[0]
+        B, Mb = img.shape[0], mask.shape[0]
+        if isinstance(generator, (list, tuple)) and len(generator) != S:
+            raise ValueError(f"got {len(generator)} generators for a batch of {S}")
+        if S < B or S % B:
+            raise ValueError(f"cannot duplicate an image batch of {B} to {S} samples")
+        if S < Mb or S % Mb:                                                 # prepare_mask_latents
+            raise ValueError(f"cannot duplicate a mask batch of {Mb} to {S} samples")
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps)
+        _, t_start = get_timesteps(sch, num_inference_steps, strength)
+        strength_max = float(strength) == 1.0                                # is_strength_max
+        eng = self.engine
+        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
+                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
+                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
+        eng.set_schedule(sch, num_inference_steps, control_guidance_start, control_guidance_end, denoising_end=denoising_end,
+                         t_start=t_start, inpaint=True)
+        h, w = height // 8, width // 8
+        vae = self.vae
+        per_sample = isinstance(generator, (list, tuple))
+        # prepare_latents: posterior sample of the image, then the add-noise noise (the image-to-image order)
+        need_z = cin == 4 or not strength_max
+        moments = None
+        if need_z:
+            moments = torch.cat([vae.encode_moments(img[j:j + 1]) for j in range(B)], 0) if per_sample else vae.encode_moments(img)
+        n1 = randn_latents((S if per_sample else B, 4, h, w), generator)
+        n2 = randn_latents((S, 4, h, w), generator)
+        masked_moments = n3 = None
+        if cin == 9:
+            # prepare_mask_latents: masked_image = init_image * (mask < 0.5), encoded and sampled after the two draws above
+            Bm = max(B, Mb)
+            if Bm % B or Bm % Mb:
+                raise ValueError(f"cannot pair an image batch of {B} with a mask batch of {Mb}")
+            masked = img.repeat(Bm // B, 1, 1, 1) * (mask.repeat(Bm // Mb, 1, 1, 1) < 0.5)
+            masked_moments = torch.cat([vae.encode_moments(masked[j:j + 1]) for j in range(Bm)], 0) if per_sample \
+                else vae.encode_moments(masked)
+            n3 = randn_latents((S if per_sample else Bm, 4, h, w), generator)
+        a, b = sch.add_noise_coefficients(t_start)
+        eng.prepare_inpaint(moments, n1, n2, vae.config.scaling_factor, a, b, latent_mask(mask, h, w), strength_max=strength_max,
+                            masked_moments=masked_moments, n3=n3)
+        out = eng.denoise(None, callback=callback, callback_steps=callback_steps).clone()
+        out = self._output(out, output_type)
+        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)

@@ -495,6 +495,9 @@ class StepState:
 
     def __init__(self):
         self.latents = None        # fp32 [S, 4, H, W] (NCHW) -- scheduler state
+        self.conv_in_extra = None  # fp32 [S, 5, H, W] (NCHW): [mask | masked-image latents], channels 4-8 of a 9-channel conv_in (inpainting UNet)
+        self.blend_tab = None      # fp32 [steps, 2] add_noise pair of the inpainting blend per step (4-channel UNet), or None
+        self.inp_z = self.inp_noise = self.inp_mask = None   # fp32 [S, 4 | 4 | 1, H, W]: image latents, add-noise noise, latent mask of that blend
         self.t_table = None        # fp32 [steps] timesteps
         self.step = None           # int32 [1] device step counter
         self.in_scale_tab = None   # fp32 [steps] scale_model_input factor (Euler) or None
@@ -513,6 +516,8 @@ class UNet2DConditionModel(nn.Module):
         self.config = cfg
         boc = cfg.block_out_channels
         nb = len(boc)
+        if cfg.in_channels not in (4, 9):
+            raise ValueError(f"in_channels must be 4 (SDXL base) or 9 (SDXL inpainting: latents, mask, masked-image latents), got {cfg.in_channels}")
         self.conv_in = Conv2d(cfg.in_channels, boc[0], 3)
         self.time_embedding = TimestepEmbedding(boc[0], cfg.time_embed_dim)
         self.add_embedding = TimestepEmbedding(cfg.projection_class_embeddings_input_dim, cfg.time_embed_dim)
@@ -728,9 +733,18 @@ class UNet2DConditionModel(nn.Module):
         # -- conv_in (+ CFG duplication + scale_model_input) --
         ctx.tag = 2
         x = ctx.new(B, Hl, Wl, boc[0])
+        cin, extra = cfg.in_channels, None
+        if cin == 9:
+            # diffusers StableDiffusionXLInpaintPipeline (num_channels_unet == 9): cat([scale_model_input(latents), mask, masked_image_latents], 1)
+            extra = getattr(st, "conv_in_extra", None)
+            if extra is None or tuple(extra.shape) != (S, 5, Hl, Wl):
+                raise L.ImhError(f"a UNet with in_channels = 9 reads [mask | masked-image latents] from StepState.conv_in_extra, fp32 "
+                                 f"[{S}, 5, {Hl}, {Wl}]; got {None if extra is None else tuple(extra.shape)}")
+        elif cin != 4:
+            raise L.ImhError(f"conv_in runs 4 or 9 input channels, not {cin}")
         ctx.ew(L.EW_CONV_IN, x, a=st.latents, w=_w(self.conv_in, ctx), bias=_b(self.conv_in, ctx),
                tab=st.in_scale_tab, step=st.step if st.in_scale_tab is not None else None,
-               i=(S, Hl, Wl, boc[0], B, 0), f=(1.0, 0, 0, 0), descr="conv_in",
+               i=(S, Hl, Wl, boc[0], B, 9 if cin == 9 else 0), f=(1.0, 0, 0, 0), descr="conv_in", x2=extra,
                nbytes=2.0 * B * Hl * Wl * boc[0])
         h = Feat(x)                      # (conv_in has no statistics epilogue: Feat.stats() takes one pass, shared by both readers)
         skips = [h]
@@ -814,7 +828,9 @@ class UNet2DConditionModel(nn.Module):
                                        added_cond_kwargs["time_ids"])
         t = timestep if torch.is_tensor(timestep) else torch.tensor([float(timestep)])
         st.t_value = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
-        st.latents = sample.to(torch.float32).contiguous()
+        st.latents = sample[:, :4].to(torch.float32).contiguous()
+        if sample.shape[1] == 9:                 # the inpainting UNet's [latents | mask | masked-image latents]
+            st.conv_in_extra = sample[:, 4:].to(torch.float32).contiguous()
         out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False)
         y = out.view(B, Hl, Wl, -1).permute(0, 3, 1, 2).to(sample.dtype)
         return (y,)

@@ -710,6 +710,48 @@ def preprocess(image):
     return 2.0 * x - 1.0
 
 
+def preprocess_mask(mask_image, height, width):
+    """diffusers StableDiffusionXLInpaintPipeline.mask_processor.preprocess(mask_image, height, width): a VaeImageProcessor with
+    do_normalize=False, do_binarize=True, do_convert_grayscale=True.  A PIL image, a list of them, or a float tensor in [0, 1] of shape
+    [H, W], [B, H, W] (a channel axis is inserted at 1, as upstream) or [B, 1, H, W] -> fp32 [B, 1, height, width] of zeros and ones
+    (1 = repaint).  Resized to the image's size by preprocess's rules (PIL: Lanczos, then mode "L", pixels / 255; tensor: nearest),
+    then binarised at 0.5: < 0.5 -> 0, else 1.  A mask that cannot be brought to one channel raises ValueError."""
+    import numpy as np
+    try:
+        from PIL import Image
+    except ImportError:                                    # pragma: no cover
+        Image = None
+    if Image is not None and isinstance(mask_image, Image.Image):
+        mask_image = [mask_image]
+    if isinstance(mask_image, (list, tuple)):
+        if not mask_image or Image is None or not all(isinstance(i, Image.Image) for i in mask_image):
+            raise ValueError("preprocess_mask: expected a PIL image, a list of PIL images or a tensor")
+        arrs = []
+        for im in mask_image:
+            if im.size != (width, height):
+                im = im.resize((width, height), resample=Image.LANCZOS)
+            arrs.append(np.asarray(im.convert("L")).astype(np.float32) / 255.0)
+        m = torch.from_numpy(np.stack(arrs, 0)).unsqueeze(1)
+    elif torch.is_tensor(mask_image):
+        m = mask_image.float()
+        if m.dim() == 2:
+            m = m[None, None]
+        elif m.dim() == 3:
+            m = m.unsqueeze(1)
+        if m.dim() != 4 or m.shape[1] != 1:
+            raise ValueError(f"preprocess_mask: a tensor mask is [H, W], [B, H, W] or [B, 1, H, W], got {tuple(mask_image.shape)}")
+        if tuple(m.shape[2:]) != (height, width):
+            m = torch.nn.functional.interpolate(m, size=(height, width))
+    else:
+        raise ValueError(f"preprocess_mask: unsupported mask type {type(mask_image).__name__}")
+    return (m >= 0.5).to(torch.float32).contiguous()
+
+
+def latent_mask(mask, h, w):
+    """prepare_mask_latents: F.interpolate(mask, size=(h, w)) -- nearest, source index floor(i * H / h) -- of a binary [B, 1, H, W] mask"""
+    return torch.nn.functional.interpolate(mask, size=(h, w)).contiguous()
+
+
 def decode_latents(vae: AutoencoderKL, latents, precision=None):
     """custom_pipelines.py:365-379"""
     return vae.decode(latents.float() / vae.config.scaling_factor, precision=precision)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMH_ABI_VERSION 10
+#define IMH_ABI_VERSION 11
 
 enum imh_status {
     IMH_OK = 0,
@@ -333,8 +333,14 @@ enum imh_ew_op {
     IMH_EW_TIMESTEP = 0,  /* diffusers Timesteps() sinusoid */
     IMH_EW_SILU = 1,
     IMH_EW_CONCAT = 2,    /* NHWC channel concat (up-block skips) */
-    IMH_EW_CONV_IN = 3,   /* conv_in + CFG duplication (custom_pipelines.py:332) + scale_model_input (:334) */
-    IMH_EW_CFG_STEP = 4,  /* CFG combine (:348-350) + scheduler.step (:357) */
+    IMH_EW_CONV_IN = 3,   /* conv_in + CFG duplication (custom_pipelines.py:332) + scale_model_input (:334).  ABI 11: i5 = input channels, 0 | 4 (the
+                           * latents alone) or 9 (the SDXL inpainting UNet): channels 4-8 = [mask | masked-image latents] come unscaled from `x2`,
+                           * fp32 NCHW [i0, 5, H, W], the same at every step; w is then [C0][9][3][3] */
+    IMH_EW_CFG_STEP = 4,  /* CFG combine (:348-350) + scheduler.step (:357).  ABI 11, with `mask` set: followed in the same pass by the masked
+                           * blend of diffusers StableDiffusionXLInpaintPipeline (4-channel UNet),
+                           *   y = (1 - m) * (ba * x2 + bb * noise) + m * y,   (ba, bb) = blend_tab[2 * *step + {0, 1}]  (step REQUIRED),
+                           * all fp32: x2 = the image latents z [i0, 4, i1], noise = the add-noise noise [i0, 4, i1], mask = the latent mask
+                           * [i4, i1] (1 = repaint; sample s reads mask s % i4, i4 >= 1); a == NULL: the blend alone (no CFG / scheduler update) */
     IMH_EW_CAST_F32 = 5,
     IMH_EW_ADD = 6,
     IMH_EW_STEP_SET = 7,  /* *y(int32) = i1 ? i0 : *y + 1 : the device-side step counter */
@@ -357,6 +363,11 @@ typedef struct imh_ew_args {
     int32_t i0, i1, i2, i3, i4, i5;
     float f0, f1, f2, f3;
     int32_t dtype;
+    /* ABI 11, all optional (NULL = the op as it was): see IMH_EW_CONV_IN / IMH_EW_CFG_STEP */
+    const float* x2;          /* CONV_IN: the step-invariant second source; CFG_STEP blend: the image latents */
+    const float* noise;       /* CFG_STEP blend: the add-noise noise */
+    const float* mask;        /* CFG_STEP blend: the latent mask; its presence selects the blend */
+    const float* blend_tab;   /* CFG_STEP blend: per-schedule (a, b) rows indexed by *step */
 } imh_ew_args;
 
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
