@@ -51,6 +51,7 @@ static GemmParams to_gemm(const imh_gemm_args* a) {
     p.ldx = a->ldx; p.ldw = a->ldw; p.ldy = a->ldy; p.ldr = a->ldr; p.ldra = a->ldra > 0 ? a->ldra : a->N;
     p.rows_per_batch = a->rows_per_batch; p.splits = a->splits; p.flags = a->flags;
     p.H = a->H; p.Wd = a->Wd; p.Cin = a->Cin; p.Ho = a->Ho; p.Wo = a->Wo; p.stride = a->stride; p.up = a->up; p.pad_lo = a->pad == 1 ? 0 : 1;
+    p.phase = 0; p.pN = 0;
     p.px = p.py = 1; p.tmx = p.tny = 0; p.xcd = a->xcd;
     p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes;
     p.early_res = g_ws_early;
@@ -93,8 +94,21 @@ static int do_gemm(const imh_gemm_args* a, hipStream_t s) {
     if ((p.flags & IMH_GF_VT_PERM) && p.splits == 1) bn = 128;   // the permutation lives in 16-column groups
     if (a->conv) {
         if (p.stride != 1 && p.stride != 2) { set_error("conv3x3: stride must be 1 or 2"); return IMH_ERR_ARG; }
-        if (p.up != 0 && p.up != 1) { set_error("conv3x3: up must be 0 or 1"); return IMH_ERR_ARG; }
+        if (p.up != 0 && p.up != 1 && p.up != 2) { set_error("conv3x3: up must be 0, 1 or 2"); return IMH_ERR_ARG; }
         if (a->pad != 0 && a->pad != 1) { set_error("conv3x3: pad must be 0 or 1"); return IMH_ERR_ARG; }
+        if (p.up == 2) {
+            // phase form of Upsample2D's conv (include/imh.h): four 2 x 2-tap convs on the low-res input, W phase-packed [4 Cout, 4 Cin];
+            // the kernels see a plain stride-1 conv geometry over the low-res pixels plus GemmParams.phase
+            if (!g_up_phase) { set_error("conv3x3: the phase form (up = 2) is switched off (imh_debug_set key 11)"); return IMH_ERR_ARG; }
+            if (p.stride != 1 || a->pad != 0 || p.H <= 0 || p.Wd <= 0 || p.Ho != 2 * p.H || p.Wo != 2 * p.Wd || p.M % (p.H * p.Wd) != 0 ||
+                p.N <= 0 || p.N % 4 || p.K != 4 * p.Cin) {
+                set_error("conv3x3: the phase form (up = 2) needs stride 1, pad 0, Ho x Wo = 2H x 2W, M = B*H*W low-res pixels, N = 4*Cout, "
+                          "K = 4*Cin (H=%d W=%d Ho=%d Wo=%d M=%d N=%d K=%d Cin=%d stride=%d)", p.H, p.Wd, p.Ho, p.Wo, p.M, p.N, p.K, p.Cin, p.stride);
+                return IMH_ERR_SHAPE;
+            }
+            p.phase = 1; p.pN = p.N / 4; p.up = 0; p.Ho = p.H; p.Wo = p.Wd;
+            return gemm_launch(p, a->dtype, a->conv, bm, bn, s);
+        }
         if (a->pad == 1) {
             // right / bottom padding (Downsample2D(padding=0)): stride 2 without upsampling, on the variants whose implicit-GEMM loaders
             // take pad_lo -- the LDS-halo conv3x3 (stride 1 only), the ping-pong and the sixteen-wave Linear forms do not
@@ -265,6 +279,7 @@ int imh_debug_set(int key, int value) {
     if (key == 7) { g_w16_pf = value; return IMH_OK; }        // sixteen-wave ff.net.0 tile: 1 (default) = the next launch's weights prefetched inside the K loop, 0 = behind the epilogue
     if (key == 9) { g_w16_form = value; return IMH_OK; }      // the 256 x 320 ff.net.0 tile: 0 = sixteen waves of 64 x 80, 1 = eight waves of 128 x 80
     if (key == 10) { g_f32_exact = value; return IMH_OK; }    // imh_f32 GEMM / conv: 1 = the exact fp32 MFMA kernel for every launch, 0 (default) = bf16 hi / lo split where the K tile fits
+    if (key == 11) { if (value >= 0) g_up_phase = value; return g_up_phase; }      // 0: up = 2 launches are refused (the host then runs the up = 1 form; A/B); value < 0: query
     if (key == 6) { g_ws_early = value; return IMH_OK; }      // 0: the residual rows of the wave-specialised launches fetched after the K loop (A/B)
     set_error("debug_set: unknown key %d", key);
     return IMH_ERR_ARG;

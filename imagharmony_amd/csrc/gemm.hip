@@ -458,7 +458,20 @@ size_t gemm_workspace_bytes(int M, int N, int splits) {
 
 int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t stream) {
     if (p.K % GEMM_BK != 0 || p.K <= 0) { set_error("gemm: K=%d must be a positive multiple of 64", p.K); return IMH_ERR_SHAPE; }
-    if (conv && (p.Cin % GEMM_BK != 0 || p.K != 9 * p.Cin)) { set_error("conv3x3: Cin=%d must be a multiple of 64 and K=9*Cin", p.Cin); return IMH_ERR_SHAPE; }
+    if (conv && (p.Cin % GEMM_BK != 0 || p.K != (p.phase ? 4 : 9) * p.Cin)) { set_error("conv3x3: Cin=%d must be a multiple of 64 and K=9*Cin (phase form: 4*Cin)", p.Cin); return IMH_ERR_SHAPE; }
+    if (p.phase) {
+        // phase form of the upsampler conv (imh_gemm_args.up == 2): the wave-specialised variants and the 256 x 320 ring carry its gather and
+        // its scattered store; a column tile must lie inside one phase; bias is the only epilogue input
+        const bool ws = bm == 1464 || bm == 2464 || bm == 24128 || bm == 23256;
+        const bool okv = (ws && bn == 160) || (bm == 23256 && bn == 128) || (bm == 5258 && bn == 320);
+        if (!conv || !okv || p.pN <= 0 || p.pN % bn || (p.pN & 7) || p.N != 4 * p.pN || p.splits > 1 || p.flags || p.residual || p.rowadd || p.X2 ||
+            p.ln_stats_out || p.gn_tab || p.gn_src.partial || p.Yt || p.ldy != p.pN || p.stride != 1 || p.pad_lo != 1 || p.up) {
+            set_error("conv3x3: the phase form (up = 2) needs a wave-specialised bn = 160 variant, 23256 x 128 or 5258 x 320, Cout a multiple of bn, "
+                      "ldy == Cout, bias as the only epilogue input, no split-K (bm=%d bn=%d Cout=%d N=%d ldy=%d splits=%d flags=%d)",
+                      bm, bn, p.pN, p.N, p.ldy, p.splits, p.flags);
+            return IMH_ERR_ARG;
+        }
+    }
     if (!conv && ((p.ldx & 7) || (p.ldw & 7))) { set_error("gemm: ldx/ldw must be multiples of 8 elements"); return IMH_ERR_SHAPE; }
     if (p.M <= 0 || p.N <= 0) { set_error("gemm: empty problem M=%d N=%d", p.M, p.N); return IMH_ERR_SHAPE; }
     if ((p.flags & GF_GEGLU) && (p.N & 15)) { set_error("geglu: N must be a multiple of 16"); return IMH_ERR_SHAPE; }
@@ -485,7 +498,8 @@ int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t s
     if (p.gn_out) {
         const int rows = gemm_gn_block_rows(bm, bn);
         const bool halo = bm >= 7000 && bm < 8000;
-        if (rows == 0 || p.N % 10 || p.N % (halo ? bn : 80) || p.gn_hw <= 0 || p.gn_hw % rows || p.M % p.gn_hw || p.gn_nblk != p.gn_hw / rows ||
+        const int cout = p.phase ? p.pN : p.N;              // (phase form: one block per (rows low-res pixels, phase), 4 gn_hw / rows per sample)
+        if (rows == 0 || cout % 10 || cout % (halo ? bn : 80) || p.gn_hw <= 0 || p.gn_hw % rows || p.M % p.gn_hw || p.gn_nblk != (p.phase ? 4 : 1) * (p.gn_hw / rows) ||
             p.splits > 1 || (p.flags & (GF_GEGLU | GF_VT_PERM | GF_OUT_F32 | GF_LN_ROW | GF_LN_COL)) ||
             (halo && (p.Ho % (rows * 4 / 16) || p.Wo % 16))) {
             set_error("gemm: gn_out needs a variant with a GroupNorm epilogue (%d rows per block for %dx%d), N a multiple of 10 and of the tile "

@@ -15,6 +15,7 @@
 
 namespace imh {
 
+int g_up_phase = 1;     // imh_debug_set key 11 (A/B): 0 = the phase form of the upsampler conv (up = 2) is refused, the host runs the up = 1 form
 int g_ws_early = 1;     // imh_debug_set key 6 (A/B): 1 = the residual-add launches of the wave-specialised kernel fetch their residual rows before the K loop
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
@@ -54,6 +55,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
     const int kt0 = z * per;
     const int kt1 = min(nkt, kt0 + per);
     const int nt = max(0, kt1 - kt0);
+    const int ph = (CONV && p.phase) ? n0 / p.pN : 0;        // phase form of the upsampler conv: the column tile's phase
 
     const unsigned char* zero = g_zero_page;
     const int srow = wave * 8 + (lane >> 3);
@@ -100,7 +102,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
         if (CONV) {
             const int tap = kt / cpt;
             const int ct = kt - tap * cpt;
-            const int ky = tap / 3, kx = tap - ky * 3;
+            int ky = tap / 3, kx = tap - ky * 3;
+            if (p.phase) { ky = (tap >> 1) + (ph >> 1); kx = (tap & 1) + (ph & 1); }     // 2 x 2 taps of the tile's phase (pad_lo = 1)
             const int Hv = p.H << p.up, Wv = p.Wd << p.up;
 #pragma unroll
             for (int i = 0; i < RX; ++i) {
@@ -193,6 +196,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
 #pragma unroll
                 for (int q = 0; q < 4 * FN; ++q) if (nb + q < p.N) o[q] = v[q];
             }
+        } else if (CONV && p.phase) {
+            epilogue_store<T, FN>(p, v, phase_row(p, m, ph), nb - ph * p.pN);
         } else {
             epilogue_store<T, FN>(p, v, m, nb);
         }
@@ -452,6 +457,7 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
     const int kt0 = z * per;
     const int kt1 = min(nkt, kt0 + per);
     const int nt = max(0, kt1 - kt0);
+    const int ph = (CONV && p.phase) ? n0 / p.pN : 0;        // phase form of the upsampler conv: the column tile's phase (0 otherwise)
 
     if (wave >= NC) {
         // ------------------------------------------------------------------ producer
@@ -501,6 +507,7 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
                 const int tap = kt / cpt;
                 ct = kt - tap * cpt;
                 ky = tap / 3; kx = tap - ky * 3;
+                if (p.phase) { ky = (tap >> 1) + (ph >> 1); kx = (tap & 1) + (ph & 1); }     // 2 x 2 taps of the tile's phase (pad_lo = 1)
             }
 #pragma unroll
             for (int k = 0; k < LP; ++k) {
@@ -679,13 +686,14 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
 #endif
 
     const int nb = n0 + wn * TN + (lane >> 4) * 4 * FN;
+    const int nbo = nb - ph * (CONV ? p.pN : 0);       // the lane's first OUTPUT channel (phase form: inside the phase's pN columns; else nb)
     // s_n, c_n (folded LayerNorm) or the bias of this lane's columns: fetched once, ahead of the stores (EpiPre; the LN
     // instantiations are at the register cap of twelve waves per CU and let the epilogue fetch the bias per row)
     float lnpre[8 * FN];
     const bool have_pre = ln_preload<4 * FN>(p, nb, lnpre);
     EpiPre<4 * FN> pre;
-    pre.ok = !p.rowadd && !p.residual && p.splits == 1 && epilogue_fast<T, 4 * FN>(p, nb);
-    if (pre.ok && p.bias) ldv<T, 4 * FN>((const T*)p.bias + nb, pre.bias);
+    pre.ok = !p.rowadd && !p.residual && p.splits == 1 && epilogue_fast<T, 4 * FN>(p, nbo);
+    if (pre.ok && p.bias) ldv<T, 4 * FN>((const T*)p.bias + nbo, pre.bias);
     LnArgs<4 * FN> ln;
     float st_s[FM], st_q[FM];
     // GroupNorm partials of the output (for the GroupNorm that reads it; imh_lnstats.h gn_emit): sub-runs of 10 channels
@@ -893,14 +901,19 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
             }
         } else {
             if constexpr (LN == 1) { ln.mean = st_s[i]; ln.rstd = st_q[i]; }
-            epilogue_store_pre<T, FN>(p, v, m, nb, lnpre, have_pre, LN != 0 ? &ln : nullptr, LN != 0 ? nullptr : &pre, lane,
+            // (phase form: GEMM row (b, y, x) goes to output pixel (b, 2 y + py, 2 x + px), channels nbo ..; launches with no row-add / residual)
+            const int mo = (CONV && p.phase) ? phase_row(p, m, ph) : m;
+            epilogue_store_pre<T, FN>(p, v, mo, nbo, lnpre, have_pre, LN != 0 ? &ln : nullptr, LN != 0 ? nullptr : &pre, lane,
                                       (LN == 0 && (4 * FN) % 10 == 0) ? &gna : nullptr, i == 0);
         }
     }
     if constexpr (LN == 0 && (4 * FN) % 10 == 0) {
         if (p.gn_out && p.splits == 1) {
             const int mw = m0 + wm * TM;
-            if (mw < p.M) gn_emit<4 * FN>(p.gn_out, p.gn_nblk, p.N / 10, mw / p.gn_hw, (mw % p.gn_hw) / TM, nb, gna, FM, lane);
+            // phase form: the partial block of (wave rows, phase) -- the TM low-res pixels' phase-ph output pixels -- at index
+            // ph * (gn_hw / TM) + row block; gn_nblk = 4 * gn_hw / TM blocks per sample, pN / 10 sub-runs
+            const int nsub = ((CONV && p.phase) ? p.pN : p.N) / 10;
+            if (mw < p.M) gn_emit<4 * FN>(p.gn_out, p.gn_nblk, nsub, mw / p.gn_hw, ph * (p.gn_hw / TM) + (mw % p.gn_hw) / TM, nbo, gna, FM, lane);
         }
     }
 }

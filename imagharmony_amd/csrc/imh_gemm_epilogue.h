@@ -50,6 +50,17 @@ inline void xcd_partition(GemmParams& p, int bm, int bn, int* grid) {
     *grid = 8 * p.tmx * p.tny;
 }
 
+// Phase form of the upsampler conv (GemmParams.phase): GEMM row m = low-res pixel (b, y, x), column tile of phase ph = 2 py + px ->
+// row of the [B, 2 H, 2 Wd, pN] output that receives it
+__device__ __forceinline__ int phase_row(const GemmParams& p, const int m, const int ph) {
+    const int hw = p.H * p.Wd;
+    const int b = m / hw;
+    const int rem = m - b * hw;
+    const int y = rem / p.Wd;
+    const int x = rem - y * p.Wd;
+    return ((b * 2 * p.H + 2 * y + (ph >> 1)) * 2 * p.Wd) + 2 * x + (ph & 1);
+}
+
 enum : int {
     GF_GEGLU = 1,      // columns interleaved in quads (value, value, gate, gate): out[2k], out[2k+1] = v[4k], v[4k+1] * gelu(v[4k+2], v[4k+3])
     GF_ACT_GELU = 2,   // exact-erf GELU on the (biased) result

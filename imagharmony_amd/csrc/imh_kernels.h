@@ -48,6 +48,11 @@ struct GemmParams {
     // implicit-GEMM conv3x3: input H x Wd (virtual size << up), output Ho x Wo; input row oy * stride + ky - pad_lo (pad_lo = 1: one pixel
     // on every side, imh_gemm_args.pad 0; pad_lo = 0: right / bottom only, pad 1 -- the VAE encoder's Downsample2D)
     int H, Wd, Cin, Ho, Wo, stride, up, pad_lo;
+    // phase form of the conv behind a nearest x2 upsampling (imh_gemm_args.up == 2; set by api.hip): the GEMM runs over the LOW-res pixels
+    // (M = B H Wd, Ho = H, Wo = Wd, up = 0), N = 4 pN columns phase-major (phase = 2 py + px, pN = Cout), K = 4 Cin in (a, b, cin) order; a
+    // column tile lies inside one phase, reads the 2 x 2 taps (y + py - 1 + a, x + px - 1 + b) and stores row (b, y, x) to pixel
+    // (b, 2 y + py, 2 x + px) of the [B, 2 H, 2 Wd, pN] output (imh_gemm_epilogue.h phase_row)
+    int phase, pN;
     // XCD-aware tile placement (set by the launchers): the 8 XCDs form a px x py grid over the tile space
     int px, py, tmx, tny;
     int xcd;               // requested cell shape (imh_gemm_args.xcd): 0 = cost model, 2 .. 5 = (8,1) (4,2) (2,4) (1,8)
@@ -110,6 +115,7 @@ extern int g_attn_mode;
 extern int g_xcd_mode;
 extern int g_halo_mode;
 extern int g_ws_early;
+extern int g_up_phase;
 
 struct SmallAttnParams {
     const void* Q; const void* K; const void* V; void* O;

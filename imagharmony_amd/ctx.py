@@ -40,6 +40,31 @@ def _read_tuning():
         return {}
 
 
+# Upsample2D = nearest x2 + conv3x3(pad 1): of the nine taps of output pixel (2y + py, 2x + px) several read the SAME low-res pixel, so every
+# output phase (py, px) is a 2 x 2-tap conv on the low-res input whose weights are sums of the 3 x 3 ones -- rows: py = 0: a = 0 -> ky 0,
+# a = 1 -> ky 1 + 2; py = 1: a = 0 -> ky 0 + 1, a = 1 -> ky 2 (columns alike), tap (a, b) at low-res pixel (y + py - 1 + a, x + px - 1 + b),
+# zero outside the low-res image
+_PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def phase_pack(w4):
+    """[Cout, Cin, 3, 3] -> the phase-packed weight [4 * Cout, 4 * Cin] of Ctx.conv3x3(up=2), fp32: row block p = 2 * py + px, K order
+    (a, b, cin); every entry the fp32 sum of the 1, 2 or 4 taps it stands for (the caller rounds ONCE to the model dtype)"""
+    w4 = w4.detach().float()
+    Cout, Cin = w4.shape[:2]
+    out = w4.new_empty(4, Cout, 2, 2, Cin)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    acc = None
+                    for ky in _PHASE_TAPS[py][a]:
+                        for kx in _PHASE_TAPS[px][b]:
+                            acc = w4[:, :, ky, kx] if acc is None else acc + w4[:, :, ky, kx]
+                    out[2 * py + px, :, a, b, :] = acc
+    return out.reshape(4 * Cout, 4 * Cin)
+
+
 class GnStats:
     """GroupNorm partials of ONE tensor (csrc/imh_lnstats.h gn_emit / norm.hip gn_stats_kernel): t [B, nblk, C / sub, 2] fp32 =
     (sum, M2) per (sample, pixel block, sub-run of `sub` channels); npart = elements per partial (0: the ragged blocks of the
@@ -211,6 +236,8 @@ class Ctx:
     _PP = (8256, 9128, 9256)                  # ping-pong (gemm_pp.hip)
     _HALO = (7128, 7564, 7328, 7428, 7256, 7356)   # LDS-halo conv3x3, stride 1 (7328 / 7428: weight rings; 7256 / 7356: 16 x 16 patch)
 
+    _PHASE = ((1464, 160), (2464, 160), (24128, 160), (23256, 160), (23256, 128), (5258, 320))   # tiles that run the phase form (conv3x3 up=2)
+
     @classmethod
     def _variant_ok(cls, bm, sp, flags, conv, stride, ln_pre, M=0, N=0, extras=False, pad=0):
         """extras: the launch has a bias, residual, row-add, second token source or transposed store (the epilogue inputs the
@@ -249,7 +276,8 @@ class Ctx:
         # a fifth key field: 1 = the entry for launches whose LayerNorm statistics are precomputed (other variants apply);
         # 2 = the entry for a stride-2 conv whose (M, N, K) coincides with a stride-1 conv of another resolution / batch;
         # 3 = the entry for a conv with fused x2 upsampling (round 6: the 64^2 -> 128^2 upsampler of UNet batch 2 shares (M, N, K) with the
-        # 64^2 ResBlock convs of UNet batch 8, which want the LDS-halo form that fuses their GroupNorm)
+        # 64^2 ResBlock convs of UNet batch 8, which want the LDS-halo form that fuses their GroupNorm);
+        # 4 = the phase form of an upsampler conv (conv3x3 up=2; keyed by ITS GEMM: M = B H W low-res pixels, N = 4 Cout, K = 4 Cin; conv_up_phase_cfg)
         cfg = (self.tuning.get(key + (1,)) if ln_pre else self.tuning.get(key + (2,)) if conv and stride == 2
                else self.tuning.get(key + (3,)) if conv and up else None) or self.tuning.get(key)
         if cfg is not None and self._variant_ok(cfg[0], cfg[2], flags, conv, stride, ln_pre, M, N, extras, pad):
@@ -440,8 +468,68 @@ class Ctx:
         lds = 2 * (((ph + 2) * 18 + 7) // 8) * 8 * 128 + S * bn * 128 + (K // 9) * 8
         return lds <= 160 * 1024
 
+    def conv_up_phase_cfg(self, B, H, W, Cin, Cout, cfg=None):
+        """tile variant (bm, bn, 1) of the phase form of an upsampler conv (conv3x3 up=2) over a [B, H, W, Cin] input, or None when the
+        launch does not qualify (the caller then runs the up=1 form): a column tile must lie inside one phase (Cout % bn == 0) on a variant
+        that carries the phase gather and store; imh_debug_set(11, 0) switches the form off (A/B)"""
+        if Cin % 64 or Cout % 8 or min(B, H, W) < 1 or self.lib.imh_debug_set(11, -1) != 1:
+            return None
+        c = cfg or self.tuning.get((B * H * W, 4 * Cout, 4 * Cin, 1, 4)) or ((23256, 160, 1) if Cout % 160 == 0 else (23256, 128, 1))
+        bm, bn, sp = c
+        if (bm, bn) not in self._PHASE or Cout % bn or sp != 1:
+            return None
+        return bm, bn, 1
+
+    def _conv3x3_phase(self, x, w, w_phase, bias, out, cfg, descr, gn_groups):
+        """conv3x3(up=2): the conv behind a nearest x2 upsampling as four 2 x 2-tap phase convs on the LOW-res input in one implicit GEMM --
+        M = B H W, N = 4 Cout (phase-major), K = 4 Cin: 4/9 of the multiply-adds of the up=1 form"""
+        B, H, W, Cin = x.shape
+        if w_phase is None:       # one-off callers (tests): pack from the [Cout, 9 Cin] weight here; models cache theirs (unet.Conv2d.packed_phase)
+            self._chk(w, descr + ".w")
+            if w.dim() != 2 or w.shape[1] != 9 * Cin:
+                raise L.ImhError(f"{descr}: w must be packed [Cout, 9*Cin]")
+            w_phase = phase_pack(w.view(w.shape[0], 3, 3, Cin).permute(0, 3, 1, 2)).to(self.dtype).contiguous()
+        self._chk(x, descr + ".x"); self._chk(w_phase, descr + ".w_phase")
+        Cout = w_phase.shape[0] // 4
+        if not x.is_contiguous() or not w_phase.is_contiguous() or tuple(w_phase.shape) != (4 * Cout, 4 * Cin):
+            raise L.ImhError(f"{descr}: x must be contiguous NHWC and w_phase [4*Cout, 4*Cin]")
+        c = self.conv_up_phase_cfg(B, H, W, Cin, Cout, cfg=cfg)
+        if c is None:
+            raise L.ImhError(f"{descr}: the phase form (up=2) does not run this launch (Cin {Cin} % 64, Cout {Cout} % tile width, variant "
+                             f"{cfg}, imh_debug_set key 11); use up=1 (Ctx.conv_up_phase_cfg)")
+        bm, bn, sp = c
+        Ho, Wo = 2 * H, 2 * W
+        M, N, K = B * H * W, 4 * Cout, 4 * Cin
+        if out is None:
+            out = self.new(B, Ho, Wo, Cout)
+        a = L.GemmArgs()
+        a.X, a.W, a.Y, a.bias = x.data_ptr(), w_phase.data_ptr(), out.data_ptr(), self._p(bias)
+        a.M, a.N, a.K = M, N, K
+        a.ldx, a.ldw, a.ldy = Cin, K, Cout
+        a.rows_per_batch = H * W
+        a.splits, a.flags, a.dtype, a.conv, a.bm, a.bn = 1, 0, self.dt, 1, bm, bn
+        a.xcd = self._xcd_for(N, 0, 1)
+        a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.stride, a.up, a.pad = H, W, Cin, Ho, Wo, 1, 2, 0
+        gs = None
+        rows = self.lib.imh_gemm_gn_block_rows(bm, bn)
+        if gn_groups and rows > 0 and Cout % 80 == 0 and (H * W) % rows == 0:
+            # one partial per (sample, `rows` consecutive low-res pixels, phase, 10 channels): block ph * (H W / rows) + low-res row block
+            nblk = 4 * (H * W // rows)
+            t = self.new(B, nblk, Cout // 10, 2, dtype=torch.float32)
+            a.gn_out, a.gn_nblk, a.gn_hw = t.data_ptr(), nblk, H * W
+            gs = GnStats(t, nblk, 10, rows * 10, Cout)
+        es = x.element_size()
+        # (recorded as the conv it computes -- output pixels x Cout x 9 Cin, geometry up = 2, the conv's algorithmic FLOPs like every other
+        # launch; the launch executes 4/9 of them, 2 M N K)
+        self._emit(L.OP_GEMM, a, descr=descr, flops=2.0 * (B * Ho * Wo) * Cout * 9 * Cin, nbytes=es * (M * Cin + N * K + 4 * M * Cout),
+                   keep=(x, w_phase, out, bias) + ((gs.t,) if gs else ()),
+                   shape=(B * Ho * Wo, Cout, 9 * Cin, 1, (B, H, W, Cin, 1, 2)),
+                   epi=dict(flags=0, bias=bias is not None, residual=False, rowadd=False, rows_per_batch=Ho * Wo, cfg=(bm, bn, sp),
+                            gn_out=(gs.nblk, Ho * Wo) if gs else None, gn_in=None, x2=0))
+        return (out, gs) if gn_groups else out
+
     def conv3x3(self, x, w, bias=None, stride=1, up=0, residual=None, rowadd=None, ldra=0, out=None, cfg=None,
-                descr="conv3x3", gn_groups=0, gn=None, x2=None, pad=0):
+                descr="conv3x3", gn_groups=0, gn=None, x2=None, pad=0, w_phase=None):
         """x: NHWC [B, H, W, Cin]; w: packed [Cout, 9*Cin]; returns NHWC [B, Ho, Wo, Cout]; with gn_groups > 0 (the output is
         a GroupNorm input) -> (y, GnStats or None) as gemm(gn_out=...).
         gn = (table [B, Cin, 2] fp32 from gn_table(), silu) or (GnSpec, silu): the input's GroupNorm (+ SiLU) is applied inside the
@@ -449,7 +537,14 @@ class Ctx:
         the table itself from the producers' partials (no table launch); x2: the input is the channel concat [x | x2].  Both need the
         LDS-halo variant (conv_fuses_gn).
         pad = 1: no padding on the top / left, one zero pixel on the right / bottom (diffusers Downsample2D(padding=0), the VAE
-        encoder's downsamplers; stride 2): Ho = (H - 2) // 2 + 1."""
+        encoder's downsamplers; stride 2): Ho = (H - 2) // 2 + 1.
+        up = 2: the same result as up = 1 (nearest x2 upsampling, then the conv) computed in the phase form (_conv3x3_phase; w_phase =
+        phase_pack() of the weight in the model dtype, packed here from w when None); bias only, raises when the launch does not qualify
+        (conv_up_phase_cfg)."""
+        if up == 2:
+            if stride != 1 or pad or residual is not None or rowadd is not None or gn is not None or x2 is not None:
+                raise L.ImhError(f"{descr}: the phase form (up=2) is a plain stride-1 conv with a bias (no residual, row-add, fused GroupNorm or second source)")
+            return self._conv3x3_phase(x, w, w_phase, bias, out, cfg, descr, gn_groups)
         self._chk(x, descr + ".x"); self._chk(w, descr + ".w")
         B, H, W, C1 = x.shape
         Cin = C1 + (x2.shape[-1] if x2 is not None else 0)

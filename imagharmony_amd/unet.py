@@ -49,6 +49,7 @@ LN_STATS_HANDOVER = os.environ.get("IMH_LN_STATS", "1") != "0"
 # covers (conv_in, split-K / ring variants) get theirs from one statistics pass.  False = every tensor takes the pass (A/B;
 # IMH_GN_STATS=0).
 GN_STATS_HANDOVER = os.environ.get("IMH_GN_STATS", "1") != "0"
+UPSAMPLE_PHASE = os.environ.get("IMH_UPSAMPLE_PHASE", "1") != "0"     # Upsample2D's conv in the phase form (Ctx.conv3x3 up=2) where it qualifies
 # ... and the GroupNorm itself -- diffusers ResnetBlock2D: norm -> SiLU -> conv -- is applied INSIDE the consuming
 # conv3x3's halo staging wherever that conv runs on the LDS-halo kernel (the 128 x 128 and 64 x 64 levels): no normalised tensor in
 # memory, and the up path's torch.cat([hidden, skip], 1) is read from its two producers by the same kernel (and by conv_shortcut's
@@ -133,6 +134,17 @@ class Conv2d(nn.Module):
             w = self.weight.detach().permute(0, 2, 3, 1).reshape(self.weight.shape[0], -1)
             c = (key, w.to(device=ctx.device, dtype=ctx.dtype).contiguous())
             self._imh_packed = c
+        return c[1]
+
+    def packed_phase(self, ctx):
+        """the 3 x 3 weight of an upsampler conv in the phase form of Ctx.conv3x3(up=2): [4 * Cout, 4 * Cin], pre-summed in fp32 from
+        the stored weight and rounded once to the model dtype (ctx.phase_pack), cached."""
+        from .ctx import phase_pack
+        key = (_vkey(self.weight), ctx.dtype, str(ctx.device))
+        c = getattr(self, "_imh_packed_phase", None)
+        if c is None or c[0] != key:
+            c = (key, phase_pack(self.weight).to(device=ctx.device, dtype=ctx.dtype).contiguous())
+            self._imh_packed_phase = c
         return c[1]
 
 
@@ -784,7 +796,12 @@ class UNet2DConditionModel(nn.Module):
             if blk.upsamplers is not None:
                 ctx.tag = 40 + bi
                 u = blk.upsamplers[0].conv
-                r_ = ctx.conv3x3(h.t, u.packed(ctx), bias=_b(u, ctx), up=1, descr="upsample", gn_groups=1 if ho else 0)
+                Bu, Hu, Wu, Cu = h.t.shape
+                if UPSAMPLE_PHASE and ctx.conv_up_phase_cfg(Bu, Hu, Wu, Cu, u.weight.shape[0]) is not None:
+                    # four 2 x 2-tap phase convs on the low-res input: 4/9 of the multiply-adds of the conv over the upsampled image
+                    r_ = ctx.conv3x3(h.t, None, bias=_b(u, ctx), up=2, w_phase=u.packed_phase(ctx), descr="upsample", gn_groups=1 if ho else 0)
+                else:
+                    r_ = ctx.conv3x3(h.t, u.packed(ctx), bias=_b(u, ctx), up=1, descr="upsample", gn_groups=1 if ho else 0)
                 h.free(ctx)
                 h = Feat(*r_) if ho else Feat(r_)
         # -- out --

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMH_ABI_VERSION 11
+#define IMH_ABI_VERSION 12
 
 enum imh_status {
     IMH_OK = 0,
@@ -69,6 +69,17 @@ enum imh_gemm_flags {
  *   Padding by `pad` (ABI 10): 0 = one zero pixel on every side (Ho = (H - 1) / stride + 1); 1 = none on the top / left and
  *   one on the right / bottom -- diffusers Downsample2D(padding=0), conv(F.pad(x, (0, 1, 0, 1)), stride 2): input row
  *   2 oy + ky, zero beyond H - 1, Ho = (H - 2) / 2 + 1 (the VAE encoder's downsamplers); stride 2, up = 0 only.
+ *   up = 2 (ABI 12): the PHASE form of Upsample2D's conv -- the same result as up = 1 with 4/9 of the multiply-adds.  Output pixel
+ *   (2y + py, 2x + px) of a 3x3 conv over a nearest x2 upsampling reads only the 2 x 2 low-res pixels (y + py - 1 + a, x + px - 1 + b),
+ *   a, b in {0, 1} (zero outside the low-res image), with weights that are sums of the 3x3 taps (rows: py = 0: a = 0 -> ky 0, a = 1 ->
+ *   ky 1 + 2; py = 1: a = 0 -> ky 0 + 1, a = 1 -> ky 2; columns alike).  The caller passes the implicit GEMM itself: X = the low-res
+ *   NHWC input, M = B*H*Wd low-res pixels, N = 4*Cout, K = 4*Cin, W = [4*Cout, 4*Cin] with row block p = 2 py + px and K order
+ *   (a, b, cin) (pre-summed in fp32, rounded once), Ho x Wo = 2H x 2Wd, Y = [B, Ho, Wo, Cout] with ldy = Cout, bias[Cout] as the only
+ *   epilogue input, stride 1, pad 0, no split-K.  Row (b, y, x) of column tile phase p is stored to pixel (b, 2y + py, 2x + px).  A
+ *   column tile must lie inside one phase: variants 1464 / 2464 / 24128 / 23256 x 160, 23256 x 128, 5258 x 320 with Cout % bn == 0,
+ *   IMH_ERR_ARG otherwise (the host then runs up = 1).  gn_out (bn = 160 variants): one partial per (sample, block of
+ *   imh_gemm_gn_block_rows consecutive LOW-res pixels, phase, 10 channels), i.e. of those pixels' phase-p output pixels, at block index
+ *   p * (gn_hw / rows) + low-res block; gn_hw = H*Wd, gn_nblk = 4 * gn_hw / rows, N / 10 read as Cout / 10.
  *   Replaces diffusers ResnetBlock2D.conv1/conv2, Downsample2D.conv, Upsample2D(+interpolate), conv_out.
  * K must be a multiple of 64; M and N are arbitrary (edge tiles read a zero page).
  * bm/bn/splits = 0 selects the built-in heuristic.  splits > 1 needs `partial`
@@ -448,6 +459,8 @@ int imh_plan_get_kind(const imh_plan* p, int index);
  * with the service waves transforming the whole halo), key 6: residual rows fetched before / after the K loop, key 7: ff.net.0's prefetch
  * of the next launch's weights inside (1) / behind (0) its K loop, key 9: the 256 x 320 ff.net.0 tile on eight (1) / sixteen (0) waves,
  * key 1: query -- 1 if the library was built with -DIMH_EXPERIMENTAL,
+ * key 11: the phase form of the upsampler conv (imh_gemm_args.up == 2): 1 (default) accepted, 0 refused with IMH_ERR_ARG so that the host
+ * runs the up = 1 form (A/B in one process); a negative value only queries; RETURNS the current value (not a status),
  * A/B and test use only: the values are process-wide plain ints read at launch time, not meant to change while another
  * thread is launching */
 int imh_debug_set(int key, int value);

@@ -8,6 +8,8 @@ plan (median over rounds).  Knobs per configuration:
     attn       imh_debug_set(4, mode): self-attention key loop
     xattn      imh_debug_set(3, mode): 1 one head per workgroup, 2 / 3 / 4 two heads with 0 / 2 / 4 producer waves
     tuning     {"M,N,K,conv[,1]": [bm, bn, splits]} overrides on top of tuning.json
+    up_phase   imh_debug_set(11, 0 | 1) while recording: 0 = the library refuses the phase form of the upsampler convs (conv3x3 up=2), the
+               forward records the up=1 form (the nine-tap conv over the upsampled image)
 Usage: python tools/forward_ab.py [--rounds 5] [--configs name1,name2,...] [--stacked S] > gpurun_out/forward_ab.json"""
 import argparse
 import collections
@@ -31,6 +33,10 @@ _PF_DEFAULT = (_CtxD.PF_BIG, _CtxD.PF_BIG_CAP)
 CONFIGS = collections.OrderedDict([
     # round 4 (the round-2 / round-3 sessions' configurations are in git history; their results in profiles/r03_forward_ab_*.json)
     ("base", dict()),
+    # the two Upsample2D convs as nine-tap convs over the x2-upsampled image (the form before the phase form) / the phase form on other tiles
+    ("upsample_up1", dict(up_phase=0)),
+    ("upsample_phase_24128", dict(tuning={"2048,5120,5120,1,4": [24128, 160, 1], "8192,2560,2560,1,4": [24128, 160, 1]})),
+    ("upsample_phase_5258", dict(tuning={"2048,5120,5120,1,4": [5258, 320, 1], "8192,2560,2560,1,4": [5258, 320, 1]})),
     # round 6: where does the tail prefetch of the 26-MB ff.net.0 weight go?  cap = only the first N MB prefetched (by the launch before); chunk = N-MB pieces
     # handed to the launches before, nearest first
     ("pf_cap8", dict(pf_chunk=8 << 20, pf_cap=True)), ("pf_cap4", dict(pf_chunk=4 << 20, pf_cap=True)), ("pf_off", dict(pf_chunk=4096, pf_cap=True)),
@@ -144,6 +150,7 @@ def main():
         lib.imh_debug_set(6, int(c.get("ws_early", 1)))
         lib.imh_debug_set(7, int(c.get("w16_pf", 1)))
         lib.imh_debug_set(9, int(c.get("w16_form", 1)))
+        lib.imh_debug_set(11, int(c.get("up_phase", 1)))      # read while RECORDING (Ctx.conv_up_phase_cfg): the plan holds up=1 or up=2 launches
         from imagharmony_amd.ctx import Ctx as _Ctx
         _Ctx.PF_CHUNK, _Ctx.PF_CAP_ONLY, _Ctx.PF_BACK = int(c.get("pf_chunk", 0)), bool(c.get("pf_cap", False)), int(c.get("pf_back", 3))
         _Ctx.PF_BIG, _Ctx.PF_BIG_CAP = int(c.get("pf_big", _PF_DEFAULT[0])), int(c.get("pf_big_cap", _PF_DEFAULT[1]))
@@ -153,6 +160,7 @@ def main():
         rec, out, st = record(u, dtype, 128, S=a.stacked, tuning=tun, cells=int(c.get("cells", 0)))
         rec.run()
         torch.cuda.synchronize()
+        lib.imh_debug_set(11, 1)
         _Ctx.PF_CHUNK, _Ctx.PF_CAP_ONLY, _Ctx.PF_BACK = 0, False, 3
         _Ctx.PF_BIG, _Ctx.PF_BIG_CAP = _PF_DEFAULT
         plans[n] = (rec, c)
