@@ -34,6 +34,10 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--guidance", type=float, default=5.0)
+    ap.add_argument("--clip-backend", choices=("none", "hip", "transformers"), default="none",
+                    help="CLIP vision tower behind the image prompt: none = stand-in embeddings (default); hip = imagharmony_amd's "
+                         "CLIPVisionEncoder; transformers = the stock module.  --clip DIR loads a saved tower, else seeded random weights at ViT-bigG/14 size")
+    ap.add_argument("--clip")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -60,6 +64,26 @@ def main():
     # encoders are outside the path (no tokenizer vocabulary / CLIP weights offline): stand-in embeddings of the right shape
     g = torch.Generator().manual_seed(0)
     clip_embeds = torch.randn(1, 1280, generator=g)
+    if a.clip_backend != "none":                                          # the image prompt through a real tower (random pixels stand in for the image)
+        px = torch.randn(1, 3, 224, 224, generator=g).to(dev, dtype)
+        if a.clip_backend == "hip":
+            from imagharmony_amd import CLIPVisionEncoder, CLIPVisionEncoderConfig
+            if a.clip:
+                enc = CLIPVisionEncoder.from_pretrained(a.clip, device=dev, dtype=dtype)
+            else:
+                torch.manual_seed(4321)
+                with torch.device(dev):
+                    enc = CLIPVisionEncoder(CLIPVisionEncoderConfig.vit_bigg())
+                for prm in enc.parameters():                              # LayerNorm-scale activations: weights of a trained tower's order
+                    if prm.dim() > 1:
+                        prm.normal_(0, 0.02)
+                enc = enc.to(dtype)
+        else:
+            from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection
+            enc = (CLIPVisionModelWithProjection.from_pretrained(a.clip) if a.clip else CLIPVisionModelWithProjection(CLIPVisionConfig(
+                hidden_size=1664, intermediate_size=8192, num_hidden_layers=48, num_attention_heads=16, projection_dim=1280,
+                hidden_act="gelu"))).eval().to(dev, dtype)
+        clip_embeds = enc(px).image_embeds
     prompt = (torch.randn(1, 77, 2048, generator=g), torch.randn(1, 77, 2048, generator=g),
               torch.randn(1, 1280, generator=g), torch.randn(1, 1280, generator=g))
     extra = torch.randn(1, 77, 2048, generator=g)

@@ -8,6 +8,8 @@ __version__ = "0.1.0"
 # the reference package's exports (ip_adapter/__init__.py:1-11), resolved lazily so that importing the package
 # does not import torch
 __all__ = ["IPAdapter", "IPAdapterPlus", "IPAdapterPlusXL", "IPAdapterXL", "IPAdapterFull"]
+# the CLIP vision tower on the HIP path (clip_vision.py), lazily as well
+_CLIP = ("CLIPVisionEncoder", "CLIPVisionEncoderConfig")
 
 
 # the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
@@ -18,6 +20,9 @@ def __getattr__(name):
     if name in __all__:
         from . import ip_adapter
         return getattr(ip_adapter, name)
+    if name in _CLIP:
+        from . import clip_vision
+        return getattr(clip_vision, name)
     if name in _PIPELINES:
         from . import pipeline
         return getattr(pipeline, name)

@@ -177,6 +177,15 @@ static int do_attn_small(const imh_small_attn_args* a, hipStream_t s) {
     return attention_small_launch(p, a->dtype, s);
 }
 
+static int do_attn_enc(const imh_enc_attn_args* a, hipStream_t s) {
+    if (!a || !a->Q || !a->K || !a->V || !a->O) { set_error("attention_enc: null pointer argument"); return IMH_ERR_ARG; }
+    EncAttnParams p;
+    p.Q = a->Q; p.K = a->K; p.V = a->V; p.O = a->O;
+    p.B = a->B; p.H = a->H; p.L = a->L; p.d = a->d;
+    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.scale = a->scale;
+    return attention_enc_launch(p, a->dtype, s);
+}
+
 static NormParams to_norm(const imh_norm_args* a) {
     NormParams p;
     p.x = a->x; p.y = a->y; p.gamma = a->gamma; p.beta = a->beta; p.partial = a->partial;
@@ -214,6 +223,7 @@ struct imh_op {
         imh_small_attn_args sattn;
         imh_gemm_args gemm2[2];
         imh_xattn_args xattn;
+        imh_enc_attn_args eattn;
     } u;
 };
 
@@ -236,6 +246,7 @@ static int run_op(const imh_op& o, hipStream_t s) {
         case IMH_OP_ATTN_SMALL: return do_attn_small(&o.u.sattn, s);
         case IMH_OP_GEMM_DUAL: return do_gemm_dual(&o.u.gemm2[0], &o.u.gemm2[1], s);
         case IMH_OP_XATTN: return do_xattn(&o.u.xattn, s);
+        case IMH_OP_ATTN_ENC: return do_attn_enc(&o.u.eattn, s);
     }
     set_error("plan: unknown op kind %d", o.kind);
     return IMH_ERR_ARG;
@@ -256,6 +267,7 @@ static size_t args_size(int kind) {
         case IMH_OP_ATTN_SMALL: return sizeof(imh_small_attn_args);
         case IMH_OP_GEMM_DUAL: return 2 * sizeof(imh_gemm_args);
         case IMH_OP_XATTN: return sizeof(imh_xattn_args);
+        case IMH_OP_ATTN_ENC: return sizeof(imh_enc_attn_args);
     }
     return 0;
 }
@@ -302,6 +314,8 @@ int imh_attention(const imh_attn_args* a, void* stream) { return do_attn(a, (hip
 int imh_cross_attention(const imh_xattn_args* a, void* stream) { return do_xattn(a, (hipStream_t)stream); }
 
 int imh_attention_small(const imh_small_attn_args* a, void* stream) { return do_attn_small(a, (hipStream_t)stream); }
+
+int imh_attention_enc(const imh_enc_attn_args* a, void* stream) { return do_attn_enc(a, (hipStream_t)stream); }
 
 int imh_groupnorm(const imh_norm_args* a, void* stream) {
     if (!a) { set_error("groupnorm: null pointer argument"); return IMH_ERR_ARG; }

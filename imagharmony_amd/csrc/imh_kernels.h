@@ -125,6 +125,16 @@ struct SmallAttnParams {
 };
 int attention_small_launch(const SmallAttnParams& p, int dtype, hipStream_t stream);
 
+// bidirectional encoder attention, head dim any multiple of 8 up to 128 (attention_enc.hip): row-major Q / K / V / O [B*L, ld*],
+// head h at columns h*d..
+struct EncAttnParams {
+    const void* Q; const void* K; const void* V; void* O;
+    int B, H, L, d;
+    int ldq, ldk, ldv, ldo;
+    float scale;
+};
+int attention_enc_launch(const EncAttnParams& p, int dtype, hipStream_t stream);
+
 struct NormParams {
     const void* x;
     void* y;

@@ -212,6 +212,8 @@ class Ctx:
             rc = self.lib.imh_attention_small(C.byref(args), s)
         elif kind == L.OP_XATTN:
             rc = self.lib.imh_cross_attention(C.byref(args), s)
+        elif kind == L.OP_ATTN_ENC:
+            rc = self.lib.imh_attention_enc(C.byref(args), s)
         else:
             rc = self.lib.imh_elementwise(ew_op, C.byref(args), s)
         L.check(rc, descr or f"op kind {kind}")
@@ -773,6 +775,27 @@ class Ctx:
         a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
         a.scale, a.dtype = scale, self.dt
         self._emit(L.OP_ATTN_SMALL, a, descr=descr, flops=2.0 * B * H * Lq * Lk * (dq + dv), keep=(q, k, v, out))
+        return out
+
+    def attention_enc(self, q, k, v, B, H, L_, d, scale=None, out=None, descr="attention_enc"):
+        """bidirectional encoder attention with a generic head dim (imh_attention_enc): q, k, v [B*L, >= H*d] row-major with
+        any row stride -- e.g. the three column ranges of one packed QKV GEMM output -- -> [B*L, H*d]"""
+        for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+            self._chk(t, f"{descr}.{nm}")
+            if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != B * L_ or t.shape[1] < H * d:
+                raise L.ImhError(f"{descr}: {nm} {tuple(t.shape)} must be row-major [{B * L_}, >= {H * d}]")
+        if out is None:
+            out = self.new(B * L_, H * d)
+        self._chk(out, descr + ".out")
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != B * L_ or out.shape[1] < H * d:
+            raise L.ImhError(f"{descr}: out {tuple(out.shape)} must be row-major [{B * L_}, >= {H * d}]")
+        a = L.EncAttnArgs()
+        a.Q, a.K, a.V, a.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+        a.B, a.H, a.L, a.d = B, H, L_, d
+        a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+        a.scale, a.dtype = float(scale if scale is not None else d ** -0.5), self.dt
+        self._emit(L.OP_ATTN_ENC, a, descr=descr, flops=4.0 * B * H * L_ * L_ * d,
+                   nbytes=float(q.element_size()) * 4 * B * L_ * H * d, keep=(q, k, v, out))
         return out
 
     # ------------------------------------------------------------------ norms

@@ -65,7 +65,13 @@ class IPAdapter:
 
     def __init__(self, sd_pipe, image_encoder_path, ip_ckpt, device, num_tokens=4, target_blocks=None,
                  number_class_crossattention=None, image_encoder=None, dtype=torch.float16, clip_embeddings_dim=1280,
-                 clip_hidden_size=1280, clip_image_processor=None):
+                 clip_hidden_size=1280, clip_image_processor=None, image_encoder_backend="transformers"):
+        """image_encoder_backend: what ``image_encoder_path`` is loaded into -- "transformers" (default): the stock
+        CLIPVisionModelWithProjection; "hip": imagharmony_amd.clip_vision.CLIPVisionEncoder (the tower on this library's kernels).  An
+        ``image_encoder`` passed in is used as it is, whichever of the two it is."""
+        if image_encoder_backend not in ("transformers", "hip"):
+            raise ValueError(f"image_encoder_backend={image_encoder_backend!r}: 'transformers' or 'hip'")
+        self.image_encoder_backend = image_encoder_backend
         self.device = device
         self.dtype = dtype
         self.image_encoder_path = image_encoder_path
@@ -78,7 +84,12 @@ class IPAdapter:
         if image_encoder is not None and clip_image_processor is None:
             from transformers import CLIPImageProcessor                                     # ip_adapter.py:84
             self.clip_image_processor = CLIPImageProcessor()
-        if image_encoder is None and image_encoder_path is not None:
+        if image_encoder is None and image_encoder_path is not None and image_encoder_backend == "hip":
+            from transformers import CLIPImageProcessor
+            from .clip_vision import CLIPVisionEncoder
+            self.image_encoder = CLIPVisionEncoder.from_pretrained(image_encoder_path, device=self.device, dtype=dtype)
+            self.clip_image_processor = clip_image_processor or CLIPImageProcessor()
+        elif image_encoder is None and image_encoder_path is not None:
             from transformers import CLIPImageProcessor, CLIPVisionModelWithProjection       # ip_adapter.py:81-84
             self.image_encoder = CLIPVisionModelWithProjection.from_pretrained(image_encoder_path).to(self.device, dtype=dtype)
             self.clip_image_processor = CLIPImageProcessor()

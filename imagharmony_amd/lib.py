@@ -13,10 +13,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _EXP_PATH = os.path.join(_HERE, "..", "tools", "tmp_libs", "libimh_hip_experimental.so")
 LIB_PATH = os.environ.get("IMH_LIB_PATH") or (_EXP_PATH if os.environ.get("IMH_EXPERIMENTAL") == "1" else os.path.join(_HERE, "libimh_hip.so"))
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 IMH_DT_BF16, IMH_DT_F16 = 0, 1
 GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL = 1, 2, 4, 8, 16, 32, 64
-OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN = 0, 1, 2, 3, 4, 5, 6, 7
+OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN, OP_ATTN_ENC = 0, 1, 2, 3, 4, 5, 6, 7, 8
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
  EW_ROW_STATS, EW_STEP_ROW) = range(12)
@@ -80,6 +80,12 @@ class SmallAttnArgs(C.Structure):
                 ("ldq", _i32), ("ldk", _i32), ("ldv", _i32), ("ldo", _i32), ("scale", _f32), ("dtype", _i32)]
 
 
+class EncAttnArgs(C.Structure):
+    _fields_ = [("Q", _vp), ("K", _vp), ("V", _vp), ("O", _vp),
+                ("B", _i32), ("H", _i32), ("L", _i32), ("d", _i32),
+                ("ldq", _i32), ("ldk", _i32), ("ldv", _i32), ("ldo", _i32), ("scale", _f32), ("dtype", _i32)]
+
+
 class NormArgs(C.Structure):
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("partial", _vp),
                 ("B", _i32), ("HW", _i32), ("C", _i32), ("groups", _i32), ("rows", _i32),
@@ -121,6 +127,7 @@ SYMBOLS = [
     ("imh_attention", C.c_int, [C.POINTER(AttnArgs), _vp]),
     ("imh_cross_attention", C.c_int, [C.POINTER(XAttnArgs), _vp]),
     ("imh_attention_small", C.c_int, [C.POINTER(SmallAttnArgs), _vp]),
+    ("imh_attention_enc", C.c_int, [C.POINTER(EncAttnArgs), _vp]),
     ("imh_groupnorm", C.c_int, [C.POINTER(NormArgs), _vp]),
     ("imh_groupnorm_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("imh_groupnorm_stats_blocks", C.c_int, [C.c_int, C.c_int]),

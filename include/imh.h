@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMH_ABI_VERSION 12
+#define IMH_ABI_VERSION 13
 
 enum imh_status {
     IMH_OK = 0,
@@ -290,6 +290,33 @@ typedef struct imh_small_attn_args {
 
 int imh_attention_small(const imh_small_attn_args* a, void* stream);
 
+/* ---- bidirectional encoder attention, generic head dim (ABI 13) ----------------------------
+ * O[b, q, h*d:(h+1)*d] = softmax(Q K^T * scale) V per (batch, head), no mask beyond the sequence end: the self-attention of
+ * the CLIP vision tower behind the image prompt -- image_encoder(...).image_embeds / .hidden_states[-2]
+ * (ip_adapter/ip_adapter.py:81-84,163-164,411-415; ViT-H/14: 16 heads x 80, ViT-bigG/14: 16 heads x 104, L = 257).
+ *   Q, K, V, O : plain row-major [B*L, ld*]; head h at columns h*d..; Q, K and V may be three column ranges of ONE packed
+ *                [B*L, 3*H*d] buffer written by a single QKV GEMM (ldq = ldk = ldv = 3*H*d).  No padding rows, no
+ *                pre-permuted or transposed layouts: keys at or beyond L are masked and never read, query rows at or
+ *                beyond L are never stored; nothing outside rows [0, B*L) of any operand is touched.
+ *   d          : any multiple of 8 up to 128 (IMH_ERR_SHAPE otherwise); the contraction dim is zero-padded to the MFMA
+ *                K step inside LDS.  L >= 1, any length (online softmax over key tiles of 64).
+ *   ld*        : multiples of 8 elements, >= H*d; base pointers 16-byte aligned (IMH_ERR_ARG).
+ * Scores and P V on v_mfma_f32_16x16x32, softmax (max, sum, exp) in fp32.  Grid = (query blocks of 64, H, B).
+ * In a plan: kind IMH_OP_ATTN_ENC.
+ */
+typedef struct imh_enc_attn_args {
+    const void* Q;
+    const void* K;
+    const void* V;
+    void* O;
+    int32_t B, H, L, d;
+    int32_t ldq, ldk, ldv, ldo;
+    float scale;
+    int32_t dtype;
+} imh_enc_attn_args;
+
+int imh_attention_enc(const imh_enc_attn_args* a, void* stream);
+
 /* ---- normalisation ----------------------------------------------------------------------
  * imh_groupnorm: GroupNorm(groups) over NHWC x[B, HW, C] with optional fused SiLU
  *   (diffusers ResnetBlock2D.norm1/norm2 + nonlinearity, Transformer2DModel.norm, conv_norm_out), in three steps that can run
@@ -427,7 +454,7 @@ int imh_f32(int op, const imh_f32_args* a, void* stream);
 /* ---- plans: a recorded sequence of the calls above, replayed from C++ (one UNet forward is
  * ~1000 launches; Python would be the bottleneck) and optionally captured into a hipGraph. ---- */
 enum imh_op_kind { IMH_OP_GEMM = 0, IMH_OP_ATTN = 1, IMH_OP_GROUPNORM = 2, IMH_OP_LAYERNORM = 3, IMH_OP_EW = 4,
-                   IMH_OP_ATTN_SMALL = 5, IMH_OP_GEMM_DUAL = 6, IMH_OP_XATTN = 7 };
+                   IMH_OP_ATTN_SMALL = 5, IMH_OP_GEMM_DUAL = 6, IMH_OP_XATTN = 7, IMH_OP_ATTN_ENC = 8 };
 
 typedef struct imh_plan imh_plan;
 
