@@ -20,6 +20,13 @@
  *   - layouts: activations are token-major / NHWC ([B, H*W, C] row-major); weights are
  *     [out, in] row-major exactly as torch.nn.Linear stores them; conv3x3 weights are
  *     pre-packed to [Cout][ky][kx][Cin] (imagharmony_amd.unet.Conv2d.packed).
+ *   - memory: a launch touches its operands and nothing else.  An operand is the rows x columns an op's description gives it
+ *     (row r = columns [0, cols) at r * ld; the gap [cols, ld) of a row belongs to the caller), plus the padding an op makes part of
+ *     it (imh_attention's K rows / V^T columns).  Every op below says in one sentence ("Memory:") what that is for it.  Nothing is
+ *     STORED outside the outputs, and no value LOADED from outside an operand reaches a result: edge tiles clamp or redirect their
+ *     loads (to a zero page, or to a valid row whose products are masked) instead of running past the operand.  A load whose value is
+ *     discarded is not observable and not promised either way.  tests/test_gpu_guarded_ops.py holds every op to this with NaN-filled
+ *     guard bands around every operand (tests/guarded.py).
  */
 #ifndef IMH_H_
 #define IMH_H_
@@ -82,6 +89,13 @@ enum imh_gemm_flags {
  *   p * (gn_hw / rows) + low-res block; gn_hw = H*Wd, gn_nblk = 4 * gn_hw / rows, N / 10 read as Cout / 10.
  *   Replaces diffusers ResnetBlock2D.conv1/conv2, Downsample2D.conv, Upsample2D(+interpolate), conv_out.
  * K must be a multiple of 64; M and N are arbitrary (edge tiles read a zero page).
+ * Memory: reads rows [0, M) of X (and X2), rows [0, N) of W, bias[0, N), rows [0, M) x columns [0, N) of residual (row stride ldr),
+ *   rowadd rows [0, ceil(M / rows_per_batch)) x columns [0, N) (row stride ldra) and, as given, ln_s / ln_c / ln_stats / gn_tab /
+ *   gn_part / gn_gamma / gn_beta over the same rows / channels; conv == 1: pixels inside [0, H) x [0, Wd) only (the padding ring is
+ *   zeros made in the kernel, never read).  Writes rows [0, M) x columns [0, N) of Y at row stride ldy (N / 2 columns with GEGLU;
+ *   columns [0, yt_col0) with Yt, whose rows [0, N - yt_col0) x columns [0, M) are written at row stride ldyt), ln_stats_out
+ *   [M][ln_slots_out][2], gn_out [M / gn_hw][gn_nblk][N / 10][2], and -- scratch, any bits -- the first
+ *   imh_gemm_workspace_bytes(M, N, splits) bytes of `partial`.  Row gaps [N, ldy) and rows >= M of every buffer are not touched.
  * bm/bn/splits = 0 selects the built-in heuristic.  splits > 1 needs `partial`
  * (imh_gemm_workspace_bytes) and runs a second reduce+epilogue kernel.
  */
@@ -209,6 +223,9 @@ size_t imh_gemm_workspace_bytes(int M, int N, int splits);
  *        padding columns must be finite (zero).
  *   K2/Vt2 (optional): the image-prompt key set of the IP branch, same layouts.
  * Lk_pad, Lk2_pad multiples of 64.
+ * Memory: reads rows [0, B*Lq) of Q, rows [0, B*Lk_pad) of K and columns [0, B*Lk_pad) of every Vt row (+ K2 / Vt2 alike over Lk2_pad) --
+ *   the padding rows / columns are part of the operand and are loaded, hence "finite" -- scale2_tab[*step] and *step; writes rows
+ *   [0, B*Lq) x columns [0, H*64) of O.  Lq is arbitrary: query rows >= Lq of the last query block are neither read into a result nor stored.
  */
 typedef struct imh_attn_args {
     const void* Q;
@@ -245,6 +262,9 @@ int imh_attention(const imh_attn_args* a, void* stream);
  *   X  : [B*Lq, ldx] token rows, C = H*64 columns; un-normalised when ln_s != NULL
  *   Wq : [H*64, ldw] = attn.to_q.weight ([out, in]); with ln_s != NULL pre-scaled by the LayerNorm gamma,
  *        ln_s[d] = sum_k gamma_k Wq[d,k], ln_c[d] = sum_k beta_k Wq[d,k] (fp32) as for IMH_GF_LN_ROW
+ * Memory: reads rows [0, B*Lq) x columns [0, C) of X, all of Wq [C, C], ln_s / ln_c [C], ln_stats [B*Lq][ln_slots][2] and the key / value
+ *   caches exactly as imh_attention does (padding included); writes rows [0, B*Lq) x columns [0, C) of O.  The one-head form takes any Lq;
+ *   the wide five-head form (imh_debug_set key 3 = 10, or chosen by shape) whole 128-query blocks and H % 5 == 0 only (IMH_ERR_SHAPE).
  */
 typedef struct imh_xattn_args {
     const void* X;
@@ -276,7 +296,12 @@ int imh_cross_attention(const imh_xattn_args* a, void* stream);
 
 /* small generic attention (arbitrary head dims, short sequences), row-major Q/K/V, one softmax:
  * HarmonyAttention's Cross_Attention (ip_adapter/attention_processor.py:35-56, head_dim 40 / value_dim 64)
- * and the Resampler's PerceiverAttention core (ip_adapter/resampler.py:66-76).  Once per image. */
+ * and the Resampler's PerceiverAttention core (ip_adapter/resampler.py:66-76).  Once per image.
+ * Q [B*Lq, ldq], K [B*Lk, ldk], V [B*Lk, ldv], O [B*Lq, ldo], head h at columns h*dq.. (Q, K) / h*dv.. (V, O); K and V may be two column
+ * ranges of one buffer.  Lk <= 8192, dq <= 1024 (IMH_ERR_SHAPE).  Two kernels, same result to rounding: the head's K^T and V resident in
+ * LDS when dq, dv, ldk, ldv are multiples of 8 and they fit 150 KB, else one pass per query from global memory.
+ * Memory: reads rows [0, B*Lq) x columns [0, H*dq) of Q, rows [0, B*Lk) x [0, H*dq) of K and x [0, H*dv) of V; writes rows [0, B*Lq) x
+ *   columns [0, H*dv) of O; no padding rows anywhere (keys >= Lk exist only as zeros in LDS). */
 typedef struct imh_small_attn_args {
     const void* Q;
     const void* K;
@@ -329,6 +354,10 @@ int imh_attention_enc(const imh_enc_attn_args* a, void* stream);
  *     apply       y = silu?(x * scale + shift) as a pass (IMH_GN_APPLY) -- or inside the consuming conv3x3 (imh_gemm_args.gn_tab)
  * imh_layernorm: LayerNorm over the last dim of x[rows, C] (BasicTransformerBlock.norm1/2/3,
  *   ip_adapter.py:39, resampler.py:15,42,43,104, train.py:238).  gamma/beta may be NULL.
+ * Memory (imh_groupnorm): x and y are dense [B, HW, C]; reads x, gamma / beta [C], and per mode partial (+ partial2) [B][nblk][C / sub][2] or
+ *   table [B][C][2]; writes y (ALL / APPLY / TABLE_APPLY), partial [B][imh_groupnorm_stats_blocks][C / sub][2] (STATS), table [B][C][2]
+ *   (TABLE), and in mode ALL -- scratch -- the first imh_groupnorm_workspace_bytes(B, HW, C, groups) bytes of `partial`.
+ * Memory (imh_layernorm): reads and writes the dense rows [0, rows) x [0, C) of x / y and gamma / beta [C].
  */
 enum imh_gn_mode {
     IMH_GN_ALL = 0,     /* statistics + table + apply; `partial` = workspace of imh_groupnorm_workspace_bytes() */
@@ -408,6 +437,9 @@ typedef struct imh_ew_args {
     const float* blend_tab;   /* CFG_STEP blend: per-schedule (a, b) rows indexed by *step */
 } imh_ew_args;
 
+/* Memory: every elementwise op reads and writes exactly the elements its description counts (n, or the i0..i5 extents) of dense buffers;
+ * IMH_EW_SOFTMAX and IMH_EW_ROW_STATS take row strides and leave the gaps [cols, ld) alone; IMH_EW_STEP_SET touches the one int32 at y;
+ * IMH_EW_STEP_ROW reads row *step of `a` only; `tab` / `blend_tab` are read at row *step only. */
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
@@ -449,6 +481,9 @@ typedef struct imh_f32_args {
     float add_a, add_b;      /* ABI 10: IMH_F32_IMG2IMG_INIT's add-noise pair */
 } imh_f32_args;
 
+/* Memory: IMH_F32_GEMM as imh_gemm (rows [0, M) of X / residual / Y at ldx / ldr / ldy, rows [0, N) of W at ldw, any M, N; conv: pixels
+ * inside the image only); the GroupNorm steps read / write dense [B, HW, C], ws [B][nblk][groups][2] and the table [B][C][2];
+ * IMH_F32_SOFTMAX rows [0, M) x columns [0, N) at ldx / ldy (X == Y allowed); IMH_F32_IMG2IMG_INIT its four dense tensors. */
 int imh_f32(int op, const imh_f32_args* a, void* stream);
 
 /* ---- plans: a recorded sequence of the calls above, replayed from C++ (one UNet forward is
