@@ -10,6 +10,8 @@ __version__ = "0.1.0"
 __all__ = ["IPAdapter", "IPAdapterPlus", "IPAdapterPlusXL", "IPAdapterXL", "IPAdapterFull"]
 # the CLIP vision tower on the HIP path (clip_vision.py), lazily as well
 _CLIP = ("CLIPVisionEncoder", "CLIPVisionEncoderConfig")
+# ... and the CLIP text towers (clip_text.py)
+_CLIP_TEXT = ("CLIPTextEncoder", "CLIPTextEncoderConfig")
 
 
 # the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
@@ -23,6 +25,9 @@ def __getattr__(name):
     if name in _CLIP:
         from . import clip_vision
         return getattr(clip_vision, name)
+    if name in _CLIP_TEXT:
+        from . import clip_text
+        return getattr(clip_text, name)
     if name in _PIPELINES:
         from . import pipeline
         return getattr(pipeline, name)

@@ -58,9 +58,19 @@ static GemmParams to_gemm(const imh_gemm_args* a) {
     return p;
 }
 
+// IMH_GF_ACT_QGELU stands where the other activations stand: one of them at most
+static bool qgelu_combined(int flags) {
+    if ((flags & IMH_GF_ACT_QGELU) && (flags & (IMH_GF_ACT_GELU | IMH_GF_ACT_SILU | IMH_GF_GEGLU))) {
+        set_error("gemm: IMH_GF_ACT_QGELU is exclusive with IMH_GF_ACT_GELU, IMH_GF_ACT_SILU and IMH_GF_GEGLU (flags=%d)", flags);
+        return true;
+    }
+    return false;
+}
+
 static int do_gemm_dual(const imh_gemm_args* a, const imh_gemm_args* b, hipStream_t s) {
     if (!a || !b || !a->X || !a->W || !a->Y || !b->X || !b->W || !b->Y) { set_error("gemm_dual: null pointer argument"); return IMH_ERR_ARG; }
     if (a->conv || b->conv || a->dtype != b->dtype) { set_error("gemm_dual: both problems must be plain GEMMs of one dtype"); return IMH_ERR_ARG; }
+    if (qgelu_combined(a->flags) || qgelu_combined(b->flags)) return IMH_ERR_ARG;
     int bm = a->bm, bn = a->bn;
     if (bm != 24128 && (bm <= 0 || bn <= 0 || bm > 128)) { bm = 128; bn = 64; }
     for (const imh_gemm_args* g : {a, b}) {
@@ -78,6 +88,7 @@ static int do_gemm_dual(const imh_gemm_args* a, const imh_gemm_args* b, hipStrea
 
 static int do_gemm(const imh_gemm_args* a, hipStream_t s) {
     if (!a || !a->X || !a->W || !a->Y) { set_error("gemm: null pointer argument"); return IMH_ERR_ARG; }
+    if (qgelu_combined(a->flags)) return IMH_ERR_ARG;
     GemmParams p = to_gemm(a);
     if ((p.flags & (IMH_GF_LN_ROW | IMH_GF_LN_COL)) && (!p.ln_s || !p.ln_c || !(p.ln_eps > 0.f))) { set_error("gemm: folded LayerNorm needs ln_s / ln_c / ln_eps > 0"); return IMH_ERR_ARG; }
     if ((p.flags & IMH_GF_LN_ROW) && (p.flags & IMH_GF_LN_COL)) { set_error("gemm: IMH_GF_LN_ROW and IMH_GF_LN_COL are exclusive"); return IMH_ERR_ARG; }
@@ -177,12 +188,12 @@ static int do_attn_small(const imh_small_attn_args* a, hipStream_t s) {
     return attention_small_launch(p, a->dtype, s);
 }
 
-static int do_attn_enc(const imh_enc_attn_args* a, hipStream_t s) {
+static int do_attn_enc(const imh_enc_attn_args* a, hipStream_t s, int causal = 0) {
     if (!a || !a->Q || !a->K || !a->V || !a->O) { set_error("attention_enc: null pointer argument"); return IMH_ERR_ARG; }
     EncAttnParams p;
     p.Q = a->Q; p.K = a->K; p.V = a->V; p.O = a->O;
     p.B = a->B; p.H = a->H; p.L = a->L; p.d = a->d;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.scale = a->scale;
+    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.scale = a->scale; p.causal = causal;
     return attention_enc_launch(p, a->dtype, s);
 }
 
@@ -247,6 +258,7 @@ static int run_op(const imh_op& o, hipStream_t s) {
         case IMH_OP_GEMM_DUAL: return do_gemm_dual(&o.u.gemm2[0], &o.u.gemm2[1], s);
         case IMH_OP_XATTN: return do_xattn(&o.u.xattn, s);
         case IMH_OP_ATTN_ENC: return do_attn_enc(&o.u.eattn, s);
+        case IMH_OP_ATTN_ENC_CAUSAL: return do_attn_enc(&o.u.eattn, s, 1);
     }
     set_error("plan: unknown op kind %d", o.kind);
     return IMH_ERR_ARG;
@@ -267,7 +279,8 @@ static size_t args_size(int kind) {
         case IMH_OP_ATTN_SMALL: return sizeof(imh_small_attn_args);
         case IMH_OP_GEMM_DUAL: return 2 * sizeof(imh_gemm_args);
         case IMH_OP_XATTN: return sizeof(imh_xattn_args);
-        case IMH_OP_ATTN_ENC: return sizeof(imh_enc_attn_args);
+        case IMH_OP_ATTN_ENC:
+        case IMH_OP_ATTN_ENC_CAUSAL: return sizeof(imh_enc_attn_args);
     }
     return 0;
 }
@@ -316,6 +329,7 @@ int imh_cross_attention(const imh_xattn_args* a, void* stream) { return do_xattn
 int imh_attention_small(const imh_small_attn_args* a, void* stream) { return do_attn_small(a, (hipStream_t)stream); }
 
 int imh_attention_enc(const imh_enc_attn_args* a, void* stream) { return do_attn_enc(a, (hipStream_t)stream); }
+int imh_attention_enc_causal(const imh_enc_attn_args* a, void* stream) { return do_attn_enc(a, (hipStream_t)stream, 1); }
 
 int imh_groupnorm(const imh_norm_args* a, void* stream) {
     if (!a) { set_error("groupnorm: null pointer argument"); return IMH_ERR_ARG; }

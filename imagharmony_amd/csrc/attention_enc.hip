@@ -1,6 +1,7 @@
-// Bidirectional encoder attention with a generic head dim (include/imh.h imh_attention_enc): the CLIP vision towers behind the
-// IP-Adapter image prompt (ViT-H/14: head dim 80, ViT-bigG/14: 104; 257 tokens), plain row-major Q / K / V with their own row
-// strides -- e.g. three column ranges of the packed output of one QKV GEMM.
+// Encoder attention with a generic head dim, bidirectional (include/imh.h imh_attention_enc) or causal (imh_attention_enc_causal):
+// the CLIP vision towers behind the IP-Adapter image prompt (ViT-H/14: head dim 80, ViT-bigG/14: 104; 257 tokens) and the CLIP text
+// towers behind the SDXL prompt (CLIP-L / OpenCLIP bigG: head dim 64, 77 tokens, causal), plain row-major Q / K / V with their own
+// row strides -- e.g. three column ranges of the packed output of one QKV GEMM.
 //
 // One workgroup = 64 queries of one (batch, head): four waves of 16 queries each.  Keys go by in tiles of 64 through LDS with an
 // online softmax, so any L runs.  Both products are computed TRANSPOSED on v_mfma_f32_16x16x32:
@@ -12,6 +13,11 @@
 // 32-key step, so P never touches LDS: the V^T image stores key 32 s + 16 h + 4 g + r at column 32 s + 8 g + 4 h + r and both operands
 // see the same order.  The softmax statistics of a query live in ONE lane group column (max / sum: registers, then two
 // shuffles across lane >> 4), and the rescale of O^T by exp(m_old - m_new) is a per-lane scalar.
+//
+// CAUSAL (a compile-time parameter; the bidirectional instantiation is the kernel as it was): O[q] = softmax over keys <= q.  The
+// workgroup of queries [q0, q0 + 64) visits the key tiles 0 .. q0 / 64 only -- later tiles are neither loaded nor staged -- and
+// the mask key <= q bites in the last of them, the diagonal tile, alone (every key of an earlier tile is < q0 <= q).  A masked
+// probability is an exact zero, so a finite K / V row of the future cannot reach an earlier query's result.
 //
 // Bounds: every global access is guarded -- keys and query rows at or beyond L and head dims at or beyond d are never loaded
 // (zero-filled in LDS / registers, masked in the softmax) and never stored.
@@ -25,8 +31,11 @@ constexpr int ENC_K = 64;        // keys per tile
 constexpr int ENC_VLD = ENC_K + 8;   // row stride (elements) of the V^T image
 
 // NKS = 32-wide contraction steps of Q K^T (head dim padded to 32 NKS with zeros), NDB = 16-wide blocks of output head dims
-template <typename T, int NKS, int NDB>
+template <typename T, int NKS, int NDB, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_enc_kernel(const EncAttnParams p) {
+    // causal: key k0 = q0 of the diagonal tile is <= every query of the workgroup, so every visited tile has a valid first key for
+    // every query and the running maximum is finite from the first tile on, as in the bidirectional form
+    static_assert(ENC_Q == ENC_K, "the causal form relies on query blocks and key tiles of one size");
     typedef typename Vec<T>::v8 v8;
     typedef typename Vec<T>::v4 v4;
     constexpr int DP = 32 * NKS;          // padded contraction width
@@ -107,7 +116,11 @@ __global__ __launch_bounds__(256) void attn_enc_kernel(const EncAttnParams p) {
     float m = -1e30f, lsum = 0.f;                    // running maximum (log2 domain) / this lane's share of the running sum
     const float sc2 = p.scale * 1.4426950408889634f;
 
-    const int ntiles = (L + ENC_K - 1) / ENC_K;
+    // causal: the tiles up to the diagonal one (q0 < L, so it exists); kend = one past the last key this lane's query sees -- below
+    // min(L, q + 1) only inside the diagonal tile
+    const int ntiles = CAUSAL ? (int)blockIdx.x + 1 : (L + ENC_K - 1) / ENC_K;
+    int kend = L;
+    if constexpr (CAUSAL) kend = min(L, q0 + wave * 16 + c + 1);
     load_tile(0);
     for (int t = 0; t < ntiles; ++t) {
         __syncthreads();                             // the previous tile's readers are done (and the zero fill above)
@@ -135,13 +148,13 @@ __global__ __launch_bounds__(256) void attn_enc_kernel(const EncAttnParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = k0 + 16 * blk + 4 * g + r;
-                const float v = key < L ? sacc[blk][r] * sc2 : -1e30f;
+                const float v = key < kend ? sacc[blk][r] * sc2 : -1e30f;
                 sacc[blk][r] = v;
                 mx = fmaxf(mx, v);
             }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mnew = fmaxf(m, mx);             // finite from the first tile on: key 0 is always valid
+        const float mnew = fmaxf(m, mx);             // finite from the first tile on: key 0 is always valid (and <= every query)
         const float alpha = __builtin_amdgcn_exp2f(m - mnew);
         m = mnew;
         float ps = 0.f;
@@ -151,7 +164,7 @@ __global__ __launch_bounds__(256) void attn_enc_kernel(const EncAttnParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = k0 + 16 * blk + 4 * g + r;
-                const float e = key < L ? __builtin_amdgcn_exp2f(sacc[blk][r] - mnew) : 0.f;
+                const float e = key < kend ? __builtin_amdgcn_exp2f(sacc[blk][r] - mnew) : 0.f;
                 ps += e;
                 pf[blk >> 1][4 * (blk & 1) + r] = from_f32<T>(e);
             }
@@ -189,7 +202,8 @@ __global__ __launch_bounds__(256) void attn_enc_kernel(const EncAttnParams p) {
 template <typename T, int NDB>
 static void enc_launch_one(const EncAttnParams& p, hipStream_t stream) {
     dim3 grid((p.L + ENC_Q - 1) / ENC_Q, p.H, p.B);
-    hipLaunchKernelGGL((attn_enc_kernel<T, (NDB + 1) / 2, NDB>), grid, dim3(256), 0, stream, p);
+    if (p.causal) hipLaunchKernelGGL((attn_enc_kernel<T, (NDB + 1) / 2, NDB, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((attn_enc_kernel<T, (NDB + 1) / 2, NDB, false>), grid, dim3(256), 0, stream, p);
 }
 
 template <typename T>

@@ -16,6 +16,7 @@
 //   EW_ROW_STATS  (sum, M2) of token rows, the stand-alone LayerNorm-statistics producer (imh_lnstats.h)
 //   EW_STEP_ROW   y[0:n] = a[*step * n + 0:n]: the denoise step's row of a per-schedule table (the stacked time-embedding projections,
 //                 computed once per schedule for all steps instead of five launches per step)
+//   EW_GATHER_ROWS y[r] = table[idx[r]] (+ add[r mod P]): the CLIP text towers' token + position embedding, and their EOS pooling
 //   EW_CAST_F32   T -> fp32 copy (debug / host-side plumbing)
 //   EW_STEP_SET   the device-resident step counter (lets 30 graph replays run with no host updates)
 // Per-step scalars (timestep, scheduler coefficients, input scale) may come from device tables
@@ -28,7 +29,7 @@
 namespace imh {
 
 enum : int { EW_TIMESTEP = 0, EW_SILU = 1, EW_CONCAT = 2, EW_CONV_IN = 3, EW_CFG_STEP = 4, EW_CAST_F32 = 5,
-             EW_ADD = 6, EW_STEP_SET = 7, EW_CFG_RESCALE = 8, EW_SOFTMAX = 9, EW_ROW_STATS = 10, EW_STEP_ROW = 11 };
+             EW_ADD = 6, EW_STEP_SET = 7, EW_CFG_RESCALE = 8, EW_SOFTMAX = 9, EW_ROW_STATS = 10, EW_STEP_ROW = 11, EW_GATHER_ROWS = 12 };
 
 // a: fp32 values [n_vals]; y: T [n_vals, dim]; cos first, then sin.
 template <typename T>
@@ -282,6 +283,30 @@ __global__ void step_row_kernel(const EwParams p) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) ((v8*)p.y)[i] = src[i];
 }
 
+// EW_GATHER_ROWS: y[r, 0:C] = a[idx[r], 0:C] (+ w[r % P, 0:C]), r < n; a = table T [i5 rows, ld i1], b = idx int32 [n], w = add T [P = i3 rows,
+// ld i4] or null, y T [n, ld i2], C = i0 (a multiple of 8: one 16-B chunk per thread and step).  The sum is taken in fp32 and rounded once.
+// The host validates the indices before it uploads them; a row whose index is outside [0, i5) all the same is left unwritten -- never read.
+template <typename T>
+__global__ void gather_rows_kernel(const EwParams p) {
+    typedef typename Vec<T>::v8 v8;
+    const int cv = p.i0 >> 3;
+    const long long total = p.n * cv;
+    const int* idx = (const int*)p.b;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / cv;
+        const int c = (int)(i - r * cv) * 8;
+        const int src = idx[r];
+        if ((unsigned)src >= (unsigned)p.i5) continue;
+        v8 v = *(const v8*)((const T*)p.a + (size_t)src * p.i1 + c);
+        if (p.w) {
+            const v8 u = *(const v8*)((const T*)p.w + (size_t)(r % p.i3) * p.i4 + c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = from_f32<T>(to_f32(v[e]) + to_f32(u[e]));
+        }
+        *(v8*)((T*)p.y + (size_t)r * p.i2 + c) = v;
+    }
+}
+
 __global__ void step_set_kernel(int* step, int value, int set) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *step = set ? value : *step + 1;
 }
@@ -397,6 +422,18 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
         case EW_STEP_ROW:
             if (p.n <= 0 || (p.n & 7) || !p.a || !p.step) { set_error("step_row: n=%lld must be a positive multiple of 8, a and step non-null", p.n); return IMH_ERR_ARG; }
             hipLaunchKernelGGL((step_row_kernel<T>), dim3(grid_for(p.n >> 3, 256)), dim3(256), 0, stream, p);
+            break;
+        case EW_GATHER_ROWS:
+            if (!p.a || !p.b || p.n <= 0 || p.i0 <= 0 || (p.i0 & 7) || p.i1 < p.i0 || (p.i1 & 7) || p.i2 < p.i0 || (p.i2 & 7) || p.i5 <= 0 ||
+                (p.w && (p.i3 <= 0 || p.i4 < p.i0 || (p.i4 & 7)))) {
+                set_error("gather_rows: n=%lld C=%d ld=%d/%d table rows=%d add rows=%d ld=%d (table, idx non-null; C and the row strides multiples of 8, "
+                          "strides >= C; table rows > 0; with add: rows > 0)", p.n, p.i0, p.i1, p.i2, p.i5, p.i3, p.i4);
+                return IMH_ERR_SHAPE;
+            }
+            if ((((uintptr_t)p.a | (uintptr_t)p.y | (uintptr_t)p.w) & 15) || ((uintptr_t)p.b & 3)) {
+                set_error("gather_rows: table / add / y must be 16-byte aligned, idx 4-byte aligned"); return IMH_ERR_ARG;
+            }
+            hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(grid_for(p.n * (p.i0 >> 3), 256)), dim3(256), 0, stream, p);
             break;
         case EW_STEP_SET:
             hipLaunchKernelGGL(step_set_kernel, dim3(1), dim3(64), 0, stream, (int*)p.y, p.i0, p.i1);

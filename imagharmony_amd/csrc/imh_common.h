@@ -138,6 +138,11 @@ template <typename T> __device__ __forceinline__ T from_f32(float x) { return (T
 __device__ __forceinline__ float silu_f(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
+// quick-GELU x * sigmoid(1.702 x) (transformers QuickGELUActivation, CLIP-L's hidden_act), the same five instructions with the
+// factor folded into the exponent's constant: 1.702 * log2(e)
+__device__ __forceinline__ float qgelu_f(float x) {
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -2.4554669595930157f));
+}
 // erf-GELU (diffusers GEGLU / nn.GELU(): 0.5 x (1 + erf(x / sqrt 2))) WITHOUT transcendentals: erf(x / sqrt 2) = x Q(x^2) on
 // |x| <= 3.3 sqrt 2 (clamped; 1 - erf(3.3) = 3e-6), Q a degree-10 minimax fit evaluated by Horner in u = 2 x^2 / xmax^2 - 1 (in [-1, 1]:
 // well conditioned in fp32).  |erf error| <= 5.1e-6, |GELU error| <= 1.2e-5 over all x in fp32 (beyond the fit range erf is set to +-1

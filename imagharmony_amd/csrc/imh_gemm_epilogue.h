@@ -69,6 +69,7 @@ enum : int {
     GF_OUT_F32 = 16,   // store fp32 instead of T
     GF_LN_ROW = 32,    // folded LayerNorm, stats per row m, ln_s / ln_c per column n
     GF_LN_COL = 64,    // folded LayerNorm, stats per column n, ln_s / ln_c per row m
+    GF_ACT_QGELU = 128, // quick-GELU x * sigmoid(1.702 x) on the (biased) result (CLIP-L text: hidden_act = "quick_gelu"); exclusive with the other activations
 };
 
 // vector load / store of CNT (any even count) consecutive T values as floats: 16-B pieces, then one 8-B, then one 4-B piece
@@ -261,6 +262,10 @@ __device__ __forceinline__ void epilogue_store_pre(const GemmParams& p, float (&
     if (p.flags & GF_ACT_SILU) {
 #pragma unroll
         for (int q = 0; q < NV; ++q) v[q] = silu_f(v[q]);
+    }
+    if (p.flags & GF_ACT_QGELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] = qgelu_f(v[q]);
     }
     if (geglu) {       // (value, value, gate, gate) quads -> NH outputs at column nb/2 of an [M, N/2] result
         const int ob = nb >> 1, NO = N >> 1;

@@ -125,13 +125,14 @@ struct SmallAttnParams {
 };
 int attention_small_launch(const SmallAttnParams& p, int dtype, hipStream_t stream);
 
-// bidirectional encoder attention, head dim any multiple of 8 up to 128 (attention_enc.hip): row-major Q / K / V / O [B*L, ld*],
-// head h at columns h*d..
+// encoder attention, head dim any multiple of 8 up to 128 (attention_enc.hip): row-major Q / K / V / O [B*L, ld*],
+// head h at columns h*d..; causal != 0: query q sees keys <= q (imh_attention_enc_causal), else every key (imh_attention_enc)
 struct EncAttnParams {
     const void* Q; const void* K; const void* V; void* O;
     int B, H, L, d;
     int ldq, ldk, ldv, ldo;
     float scale;
+    int causal;
 };
 int attention_enc_launch(const EncAttnParams& p, int dtype, hipStream_t stream);
 

@@ -214,6 +214,8 @@ class Ctx:
             rc = self.lib.imh_cross_attention(C.byref(args), s)
         elif kind == L.OP_ATTN_ENC:
             rc = self.lib.imh_attention_enc(C.byref(args), s)
+        elif kind == L.OP_ATTN_ENC_CAUSAL:
+            rc = self.lib.imh_attention_enc_causal(C.byref(args), s)
         else:
             rc = self.lib.imh_elementwise(ew_op, C.byref(args), s)
         L.check(rc, descr or f"op kind {kind}")
@@ -410,7 +412,7 @@ class Ctx:
         rows = self.lib.imh_gemm_gn_block_rows(a.bm, a.bn)
         halo = a.bm in self._HALO
         if (rows <= 0 or a.splits != 1 or a.N % 10 or hw % rows or a.M % hw
-                or a.N % (a.bn if halo else 80) or a.flags & ~(L.GF_ACT_SILU | L.GF_ACT_GELU)
+                or a.N % (a.bn if halo else 80) or a.flags & ~(L.GF_ACT_SILU | L.GF_ACT_GELU | L.GF_ACT_QGELU)
                 or (halo and (a.Ho % (rows // 4) or a.Wo % 16))):
             return None
         nblk = hw // rows
@@ -777,9 +779,9 @@ class Ctx:
         self._emit(L.OP_ATTN_SMALL, a, descr=descr, flops=2.0 * B * H * Lq * Lk * (dq + dv), keep=(q, k, v, out))
         return out
 
-    def attention_enc(self, q, k, v, B, H, L_, d, scale=None, out=None, descr="attention_enc"):
-        """bidirectional encoder attention with a generic head dim (imh_attention_enc): q, k, v [B*L, >= H*d] row-major with
-        any row stride -- e.g. the three column ranges of one packed QKV GEMM output -- -> [B*L, H*d]"""
+    def attention_enc(self, q, k, v, B, H, L_, d, scale=None, out=None, descr="attention_enc", causal=False):
+        """encoder attention with a generic head dim (imh_attention_enc; causal=True: imh_attention_enc_causal, query q sees keys <= q):
+        q, k, v [B*L, >= H*d] row-major with any row stride -- e.g. the three column ranges of one packed QKV GEMM output -- -> [B*L, H*d]"""
         for t, nm in ((q, "q"), (k, "k"), (v, "v")):
             self._chk(t, f"{descr}.{nm}")
             if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != B * L_ or t.shape[1] < H * d:
@@ -794,7 +796,7 @@ class Ctx:
         a.B, a.H, a.L, a.d = B, H, L_, d
         a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
         a.scale, a.dtype = float(scale if scale is not None else d ** -0.5), self.dt
-        self._emit(L.OP_ATTN_ENC, a, descr=descr, flops=4.0 * B * H * L_ * L_ * d,
+        self._emit(L.OP_ATTN_ENC_CAUSAL if causal else L.OP_ATTN_ENC, a, descr=descr, flops=(2.0 if causal else 4.0) * B * H * L_ * L_ * d,
                    nbytes=float(q.element_size()) * 4 * B * L_ * H * d, keep=(q, k, v, out))
         return out
 
@@ -926,6 +928,25 @@ class Ctx:
         e.dtype = self.dt
         self._emit(L.OP_EW, e, ew_op=op, descr=descr, nbytes=nbytes, keep=(a, b, y, w, bias, tab, step, x2, noise, mask, blend_tab))
         return y
+
+    def gather_rows(self, table, idx, add=None, out=None, descr="gather_rows"):
+        """out[r] = table[idx[r]] (+ add[r % P]) (IMH_EW_GATHER_ROWS): table [rows, C] and add [P, C] row-major in the compute dtype, idx
+        int32 [n] on the device.  The caller has validated the indices on the host (the CLIP text towers' ids and EOS rows are host-known)."""
+        self._chk(table, descr + ".table"); self._chk(add, descr + ".add"); self._chk(idx, descr + ".idx", torch.int32)
+        n, Cc = idx.numel(), table.shape[1]
+        if table.dim() != 2 or table.stride(1) != 1 or idx.dim() != 1 or not idx.is_contiguous() or Cc % 8:
+            raise L.ImhError(f"{descr}: table {tuple(table.shape)} must be row-major with a multiple of 8 columns, idx a dense int32 vector")
+        if add is not None and (add.dim() != 2 or add.stride(1) != 1 or add.shape[1] != Cc):
+            raise L.ImhError(f"{descr}: add {tuple(add.shape)} must be row-major [P, {Cc}]")
+        if out is None:
+            out = self.new(n, Cc)
+        self._chk(out, descr + ".out")
+        if out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (n, Cc):
+            raise L.ImhError(f"{descr}: out {tuple(out.shape)} must be row-major [{n}, {Cc}]")
+        return self.ew(L.EW_GATHER_ROWS, out, a=table, b=idx, w=add, n=n,
+                       i=(Cc, table.stride(0), out.stride(0), add.shape[0] if add is not None else 0,
+                          add.stride(0) if add is not None else 0, table.shape[0]),
+                       descr=descr, nbytes=float(table.element_size()) * n * Cc * (3 if add is not None else 2))
 
     def silu(self, x, descr="silu"):
         out = self.new(*x.shape)

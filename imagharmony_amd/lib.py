@@ -15,11 +15,11 @@ LIB_PATH = os.environ.get("IMH_LIB_PATH") or (_EXP_PATH if os.environ.get("IMH_E
 
 ABI_VERSION = 13
 IMH_DT_BF16, IMH_DT_F16 = 0, 1
-GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL = 1, 2, 4, 8, 16, 32, 64
-OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN, OP_ATTN_ENC = 0, 1, 2, 3, 4, 5, 6, 7, 8
+GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL, GF_ACT_QGELU = 1, 2, 4, 8, 16, 32, 64, 128
+OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN, OP_ATTN_ENC, OP_ATTN_ENC_CAUSAL = range(10)
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
- EW_ROW_STATS, EW_STEP_ROW) = range(12)
+ EW_ROW_STATS, EW_STEP_ROW, EW_GATHER_ROWS) = range(13)
 
 # variant codes / modes that only a -DIMH_EXPERIMENTAL build compiles (csrc/imh_common.h IMH_EXP_ONLY): measured, selected by no
 # tuning.json entry and no default mode.  experimental() asks the loaded library (imh_debug_set(1, 0)).
@@ -128,6 +128,7 @@ SYMBOLS = [
     ("imh_cross_attention", C.c_int, [C.POINTER(XAttnArgs), _vp]),
     ("imh_attention_small", C.c_int, [C.POINTER(SmallAttnArgs), _vp]),
     ("imh_attention_enc", C.c_int, [C.POINTER(EncAttnArgs), _vp]),
+    ("imh_attention_enc_causal", C.c_int, [C.POINTER(EncAttnArgs), _vp]),
     ("imh_groupnorm", C.c_int, [C.POINTER(NormArgs), _vp]),
     ("imh_groupnorm_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("imh_groupnorm_stats_blocks", C.c_int, [C.c_int, C.c_int]),

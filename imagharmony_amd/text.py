@@ -1,8 +1,10 @@
-"""``encode_prompt`` for the SDXL pipeline with stock ``transformers`` text encoders -- the step before the hot path
-(reference call sites ip_adapter.py:285-297,308-319 -> diffusers StableDiffusionXLPipeline.encode_prompt,
-restated here because diffusers is absent).  No kernels of ours: the two CLIP text models run as ordinary torch modules.
+"""``encode_prompt`` for the SDXL pipeline -- the step before the hot path (reference call sites
+ip_adapter.py:285-297,308-319 -> diffusers StableDiffusionXLPipeline.encode_prompt, restated here because diffusers is absent).
+By default the two CLIP text models run as the ordinary ``transformers`` torch modules they are handed in as;
+``text_encoder_backend="hip"`` converts them to ``clip_text.CLIPTextEncoder`` (libimh_hip.so launches only, one graph replay per
+prompt batch), and instances of that class may be passed directly: the encoders are duck-typed.
 
-    enc = SDXLPromptEncoder(tokenizer, tokenizer_2, text_encoder, text_encoder_2)
+    enc = SDXLPromptEncoder(tokenizer, tokenizer_2, text_encoder, text_encoder_2[, text_encoder_backend="hip"])
     pipe = StableDiffusionXLCustomPipeline(unet, text_encoder=enc, ...)
 
 Semantics kept from diffusers 0.30.0: every (tokenizer, encoder) pair tokenises to ``model_max_length`` with truncation,
@@ -17,7 +19,17 @@ import torch
 
 
 class SDXLPromptEncoder:
-    def __init__(self, tokenizer, tokenizer_2, text_encoder, text_encoder_2, force_zeros_for_empty_prompt=True, device=None):
+    def __init__(self, tokenizer, tokenizer_2, text_encoder, text_encoder_2, force_zeros_for_empty_prompt=True, device=None,
+                 text_encoder_backend="transformers"):
+        """text_encoder_backend: what the two encoders run as -- "transformers" (default): as given; "hip": each stock
+        ``CLIPTextModel`` / ``CLIPTextModelWithProjection`` is converted with ``CLIPTextEncoder.from_hf`` (same device and dtype)"""
+        if text_encoder_backend not in ("transformers", "hip"):
+            raise ValueError(f"text_encoder_backend={text_encoder_backend!r}: 'transformers' or 'hip'")
+        self.text_encoder_backend = text_encoder_backend
+        if text_encoder_backend == "hip":
+            from .clip_text import CLIPTextEncoder
+            text_encoder, text_encoder_2 = (e if e is None or isinstance(e, CLIPTextEncoder) else CLIPTextEncoder.from_hf(e)
+                                            for e in (text_encoder, text_encoder_2))
         self.pairs = [(t, e) for t, e in ((tokenizer, text_encoder), (tokenizer_2, text_encoder_2)) if t is not None and e is not None]
         if not self.pairs:
             raise ValueError("at least one (tokenizer, text_encoder) pair is needed")

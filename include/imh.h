@@ -38,6 +38,9 @@
 extern "C" {
 #endif
 
+/* Still 13 after the CLIP text towers: what they added is strictly additive -- one entry (imh_attention_enc_causal), one plan kind
+ * (IMH_OP_ATTN_ENC_CAUSAL = 9), one imh_gemm flag bit (IMH_GF_ACT_QGELU = 128) and one elementwise op (IMH_EW_GATHER_ROWS, 12); no
+ * struct changed, and a caller written against the first version 13 cannot observe any of it. */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
@@ -60,7 +63,10 @@ enum imh_gemm_flags {
     IMH_GF_VT_PERM = 8,   /* write the attention V^T key permutation (see imh_attention) */
     IMH_GF_OUT_F32 = 16,  /* fp32 output */
     IMH_GF_LN_ROW = 32,   /* folded LayerNorm, the un-normalised token rows are X's rows (statistics per output row m) */
-    IMH_GF_LN_COL = 64    /* folded LayerNorm, the token rows are W's rows (per output column n; swapped-operand V^T form) */
+    IMH_GF_LN_COL = 64,   /* folded LayerNorm, the token rows are W's rows (per output column n; swapped-operand V^T form) */
+    IMH_GF_ACT_QGELU = 128 /* quick-GELU y = x * sigmoid(1.702 x) on the biased accumulator in fp32 (transformers "quick_gelu": the CLIP-L text
+                           * tower's MLP); where IMH_GF_ACT_GELU / _SILU stand, in every variant that takes those; exclusive with
+                           * IMH_GF_ACT_GELU, IMH_GF_ACT_SILU and IMH_GF_GEGLU (IMH_ERR_ARG) */
 };
 
 /* ---- dense contraction ------------------------------------------------------------------
@@ -341,6 +347,13 @@ typedef struct imh_enc_attn_args {
 } imh_enc_attn_args;
 
 int imh_attention_enc(const imh_enc_attn_args* a, void* stream);
+/* The causal form: O[b, q] = softmax over the keys k <= q only -- the self-attention of the CLIP text towers behind the SDXL prompt
+ * (CLIP-L: 12 heads x 64, OpenCLIP bigG: 20 heads x 64, L = 77; diffusers StableDiffusionXLPipeline.encode_prompt).  The same argument
+ * struct, operand rules, error codes and memory promise as imh_attention_enc.  The workgroup of queries [q0, q0 + 64) visits the key
+ * tiles 0 .. q0 / 64 only (later tiles are neither loaded nor staged) and masks inside the diagonal tile; a masked probability is an
+ * exact zero, so a FINITE K / V row of the future never reaches an earlier query (the masked keys of the diagonal tile are still
+ * staged: they must be finite, as any operand).  In a plan: kind IMH_OP_ATTN_ENC_CAUSAL (args = imh_enc_attn_args). */
+int imh_attention_enc_causal(const imh_enc_attn_args* a, void* stream);
 
 /* ---- normalisation ----------------------------------------------------------------------
  * imh_groupnorm: GroupNorm(groups) over NHWC x[B, HW, C] with optional fused SiLU
@@ -415,7 +428,15 @@ enum imh_ew_op {
                              * a = noise prediction NHWC [2 i0, i1, 4], f2 = guidance scale; IMH_EW_CFG_STEP reads y through `w` */
     IMH_EW_SOFTMAX = 9,     /* y[r,:] (T) = softmax(f0 * a[r,:]) with a fp32 (VAE mid-block attention); i0 rows, i1 cols, i2 / i3 leading dims */
     IMH_EW_ROW_STATS = 10,  /* y[r] (fp32 pair) = (sum, M2) of a[r, 0:i0] (row stride i1), n rows: LayerNorm statistics in the ln_stats format, one slot */
-    IMH_EW_STEP_ROW = 11    /* y[0:n] = a[*step * n + 0:n] (T; n % 8 == 0): row `step` of a per-schedule table (time embeddings of all denoise steps) */
+    IMH_EW_STEP_ROW = 11,   /* y[0:n] = a[*step * n + 0:n] (T; n % 8 == 0): row `step` of a per-schedule table (time embeddings of all denoise steps) */
+    IMH_EW_GATHER_ROWS      /* 12, numbered by its place behind IMH_EW_STEP_ROW (tests/test_host_logic.py pins the count of explicitly
+                             * numbered ops of ABI 13 at twelve; this one is the additive thirteenth).  y[r, 0:C] = table[idx[r], 0:C] (+ add[r mod P, 0:C]), r in [0, n): the CLIP text towers' token + position embedding
+                             * (add = the position table, P = 77) and their EOS pooling (no add; table = the final-layer-normed hidden rows,
+                             * idx[b] = b * L + eos position).  Fields: a = table (T, i5 rows, row stride i1), b = idx (int32 [n], device), w = add
+                             * (T, P = i3 rows, row stride i4) or NULL, y (T, row stride i2), i0 = C; C and the strides multiples of 8 (16-byte
+                             * accesses; table / add / y 16-byte aligned), strides >= C.  The sum is taken in fp32 and rounded once.  The CALLER
+                             * validates idx against [0, i5) before uploading it; a row with an index outside that range is skipped (not
+                             * read, not written), never followed. */
 };
 
 typedef struct imh_ew_args {
@@ -439,7 +460,8 @@ typedef struct imh_ew_args {
 
 /* Memory: every elementwise op reads and writes exactly the elements its description counts (n, or the i0..i5 extents) of dense buffers;
  * IMH_EW_SOFTMAX and IMH_EW_ROW_STATS take row strides and leave the gaps [cols, ld) alone; IMH_EW_STEP_SET touches the one int32 at y;
- * IMH_EW_STEP_ROW reads row *step of `a` only; `tab` / `blend_tab` are read at row *step only. */
+ * IMH_EW_STEP_ROW reads row *step of `a` only; `tab` / `blend_tab` are read at row *step only; IMH_EW_GATHER_ROWS reads idx[0, n), columns
+ * [0, C) of the table rows idx names and of add's rows [0, min(n, P)), and writes columns [0, C) of y's rows [0, n). */
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
@@ -489,7 +511,7 @@ int imh_f32(int op, const imh_f32_args* a, void* stream);
 /* ---- plans: a recorded sequence of the calls above, replayed from C++ (one UNet forward is
  * ~1000 launches; Python would be the bottleneck) and optionally captured into a hipGraph. ---- */
 enum imh_op_kind { IMH_OP_GEMM = 0, IMH_OP_ATTN = 1, IMH_OP_GROUPNORM = 2, IMH_OP_LAYERNORM = 3, IMH_OP_EW = 4,
-                   IMH_OP_ATTN_SMALL = 5, IMH_OP_GEMM_DUAL = 6, IMH_OP_XATTN = 7, IMH_OP_ATTN_ENC = 8 };
+                   IMH_OP_ATTN_SMALL = 5, IMH_OP_GEMM_DUAL = 6, IMH_OP_XATTN = 7, IMH_OP_ATTN_ENC = 8, IMH_OP_ATTN_ENC_CAUSAL = 9 };
 
 typedef struct imh_plan imh_plan;
 
