@@ -19,13 +19,24 @@ from imagharmony_amd import pns                                           # noqa
 from imagharmony_amd.ip_adapter import IPAdapterXL                        # noqa: E402
 from imagharmony_amd.modules import HarmonyAttention                      # noqa: E402
 from imagharmony_amd.pipeline import StableDiffusionXLCustomPipeline      # noqa: E402
-from imagharmony_amd.schedulers import DDIMScheduler                      # noqa: E402
+from imagharmony_amd import schedulers as hs                              # noqa: E402
 from imagharmony_amd.unet import UNet2DConditionModel, UNetConfig         # noqa: E402
 from imagharmony_amd.vae import AutoencoderKL, decode_latents, postprocess   # noqa: E402
 
 
+SCHEDULERS = {
+    "ddim": hs.DDIMScheduler,
+    "euler": hs.EulerDiscreteScheduler,
+    "dpmpp2m": hs.DPMSolverMultistepScheduler,
+    "dpmpp2m-karras": lambda: hs.DPMSolverMultistepScheduler(use_karras_sigmas=True),
+    "euler-a": hs.EulerAncestralDiscreteScheduler,           # stochastic: each denoise draws its per-step noise (torch's global generator)
+}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scheduler", choices=sorted(SCHEDULERS), default="ddim",
+                    help="sampler of the preview and the final denoise (dpmpp2m-karras at 20-25 steps is the usual SDXL choice)")
     ap.add_argument("--out", default="out.png")
     ap.add_argument("--unet"); ap.add_argument("--vae"); ap.add_argument("--ip-ckpt")
     ap.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
@@ -55,7 +66,7 @@ def main():
         unet = unet.init_random_(1234).to(dtype)
     vae = AutoencoderKL.from_safetensors(a.vae, device=dev, dtype=dtype) if a.vae else AutoencoderKL().init_random_(1).to(dev, dtype)
     pns.broadcast_module_(unet)                                           # identical replicas on every rank
-    pipe = StableDiffusionXLCustomPipeline(unet, scheduler=DDIMScheduler(), device=dev, dtype=dtype, vae=vae)
+    pipe = StableDiffusionXLCustomPipeline(unet, scheduler=SCHEDULERS[a.scheduler](), device=dev, dtype=dtype, vae=vae)
     pipe.enable_vae_tiling()                                              # test.py:73
     ha = HarmonyAttention(image_hidden_size=1280, text_context_dim=2048, inter_dim=2560, cross_heads=8, reshape_blocks=8,
                           cross_value_dim=64, scale=1.0, fusion_method="cross_attention")     # test.py:82-91

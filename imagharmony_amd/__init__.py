@@ -16,6 +16,8 @@ _CLIP_TEXT = ("CLIPTextEncoder", "CLIPTextEncoderConfig")
 
 # the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
 _PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline")
+# the schedulers of the device-resident loop (schedulers.py): the two linear ones and the multistep / ancestral ones
+_SCHEDULERS = ("DDIMScheduler", "EulerDiscreteScheduler", "DPMSolverMultistepScheduler", "EulerAncestralDiscreteScheduler")
 
 
 def __getattr__(name):
@@ -31,4 +33,7 @@ def __getattr__(name):
     if name in _PIPELINES:
         from . import pipeline
         return getattr(pipeline, name)
+    if name in _SCHEDULERS:
+        from . import schedulers
+        return getattr(schedulers, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

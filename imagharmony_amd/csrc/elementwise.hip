@@ -9,6 +9,9 @@
 //                 x' = cx*x + ce*eps (DDIM eta=0 / Euler), noise pred read
 //                 NHWC, latents kept NCHW fp32 (custom_pipelines.py:357); optionally followed in the same pass by the
 //                 masked blend of SDXL inpainting on a 4-channel UNet
+//   EW_CFG_MSTEP  the same launch for the multistep and ancestral samplers (DPM-Solver++ 2M, its SDE variant, Euler ancestral):
+//                 x' = cx*x + ce*eps + ch*h + cn*z and h' = hx*x + he*eps from one six-column table row, h a history slot,
+//                 z the step's row of a host-filled noise bank
 //   EW_CFG_RESCALE per-sample factor of rescale_noise_cfg (custom_pipelines.py:351-354; arXiv 2305.08891 3.4):
 //                 phi * std(eps_text) / std(eps_cfg) + (1 - phi), consumed by EW_CFG_STEP through `w`
 //   EW_SOFTMAX    row softmax of fp32 scores -> T probabilities (the VAE mid-block attention: one head of width
@@ -29,7 +32,8 @@
 namespace imh {
 
 enum : int { EW_TIMESTEP = 0, EW_SILU = 1, EW_CONCAT = 2, EW_CONV_IN = 3, EW_CFG_STEP = 4, EW_CAST_F32 = 5,
-             EW_ADD = 6, EW_STEP_SET = 7, EW_CFG_RESCALE = 8, EW_SOFTMAX = 9, EW_ROW_STATS = 10, EW_STEP_ROW = 11, EW_GATHER_ROWS = 12 };
+             EW_ADD = 6, EW_STEP_SET = 7, EW_CFG_RESCALE = 8, EW_SOFTMAX = 9, EW_ROW_STATS = 10, EW_STEP_ROW = 11, EW_GATHER_ROWS = 12,
+             EW_CFG_MSTEP = 13 };
 
 // a: fp32 values [n_vals]; y: T [n_vals, dim]; cos first, then sin.
 template <typename T>
@@ -200,6 +204,55 @@ __global__ void cfg_step_kernel(const EwParams p) {
             const float pv = ba * p.x2[i] + bb * p.noise[i];
             lat[i] = (1.0f - m) * pv + m * lat[i];
         }
+    }
+}
+
+// EW_CFG_MSTEP (imh.h): the general step behind the multistep and ancestral samplers (schedulers.py DPMSolverMultistepScheduler,
+// EulerAncestralDiscreteScheduler).  Same CFG combine, rescale factor and optional blend as cfg_step_kernel; the update reads one row of
+// a six-column table, (cx, ce, ch, cn, hx, he) = tab[6 * *step ..]:
+//   x' = cx * x + ce * eps + ch * h + cn * z,   h' = hx * x + he * eps
+// h = p.b, fp32 [S, 4, HW], one history slot (the previous step's data prediction), read then overwritten by the same thread; z = row
+// *step of the noise bank p.bias, fp32 [n, S, 4, HW].  Either may be NULL: the term is absent and h is not written.  All fp32; the
+// first two terms are written as cfg_step_kernel writes them, so that with ch = cn = 0 and no h / bank the result has the same bits.
+template <typename T, bool BLEND>
+__global__ void cfg_mstep_kernel(const EwParams p) {
+    const int S = p.i0, HW = p.i1;
+    const long long total = (long long)S * HW * 4;
+    const T* np_ = (const T*)p.a;
+    float* lat = (float*)p.y;
+    float* hist = (float*)p.b;
+    const int row = *p.step;
+    const float* c = p.tab + (size_t)row * 6;
+    const float cx = c[0], ce = c[1], ch = c[2], cn = c[3], hx = c[4], he = c[5];
+    const float* z = p.bias ? (const float*)p.bias + (size_t)row * (size_t)total : nullptr;
+    float ba = 0.f, bb = 0.f;
+    if constexpr (BLEND) { ba = p.blend_tab[row * 2]; bb = p.blend_tab[row * 2 + 1]; }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int pix = (int)(i % HW);
+        const int chn = (int)((i / HW) % 4);
+        const int s = (int)(i / ((long long)HW * 4));
+        float eps;
+        if (p.i3) {
+            const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
+            const float cnd = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + chn]);
+            eps = u + p.f2 * (cnd - u);
+        } else {
+            eps = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
+        }
+        if (p.w) eps *= ((const float*)p.w)[s];            // guidance_rescale factor of this sample (EW_CFG_RESCALE)
+        const float x = lat[i];
+        float y = cx * x + ce * eps;
+        if (hist) {
+            y += ch * hist[i];
+            hist[i] = hx * x + he * eps;
+        }
+        if (z) y += cn * z[i];
+        if constexpr (BLEND) {
+            const float m = p.mask[(size_t)(s % p.i4) * HW + pix];
+            const float pv = ba * p.x2[i] + bb * p.noise[i];
+            y = (1.0f - m) * pv + m * y;
+        }
+        lat[i] = y;
     }
 }
 
@@ -400,6 +453,21 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
             }
             if (!p.a) { set_error("cfg_step: null noise prediction"); return IMH_ERR_ARG; }
             hipLaunchKernelGGL((cfg_step_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+            break;
+        case EW_CFG_MSTEP:
+            if (!p.a || !p.tab || !p.step || p.i0 <= 0 || p.i1 <= 0) {
+                set_error("cfg_mstep: needs the noise prediction, the six-column table, step and S, HW > 0");
+                return IMH_ERR_ARG;
+            }
+            if (p.mask) {
+                if (!p.x2 || !p.noise || !p.blend_tab || p.i4 < 1) {
+                    set_error("cfg_mstep: the masked blend needs x2 (image latents), noise, blend_tab and i4 = mask batch >= 1");
+                    return IMH_ERR_ARG;
+                }
+                hipLaunchKernelGGL((cfg_mstep_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+                break;
+            }
+            hipLaunchKernelGGL((cfg_mstep_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
             break;
         case EW_CFG_RESCALE:
             if (p.i0 <= 0 || p.i1 <= 0) { set_error("cfg_rescale: empty problem"); return IMH_ERR_SHAPE; }

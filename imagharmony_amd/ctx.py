@@ -911,8 +911,19 @@ class Ctx:
 
     # ------------------------------------------------------------------ elementwise
     def ew(self, op, y, a=None, b=None, w=None, bias=None, tab=None, step=None, n=0, i=(0, 0, 0, 0, 0, 0),
-           f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0, x2=None, noise=None, mask=None, blend_tab=None):
-        """x2 / noise / mask / blend_tab (fp32, imh.h ABI 11): conv_in's second source, the masked blend behind the CFG step"""
+           f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0, x2=None, noise=None, mask=None, blend_tab=None, hist=None, bank=None):
+        """x2 / noise / mask / blend_tab (fp32, imh.h ABI 11): conv_in's second source, the masked blend behind the CFG step.
+        hist / bank (fp32, IMH_EW_CFG_MSTEP only): the history slot the step reads and rewrites in place and the per-step noise bank;
+        they travel in the fields `b` and `bias` (imh_ew_args does not grow), so they exclude b= / bias="""
+        if hist is not None or bank is not None:
+            if op != L.EW_CFG_MSTEP or b is not None or bias is not None:
+                raise L.ImhError(f"{descr}: hist / bank belong to EW_CFG_MSTEP and take the place of b / bias")
+            for t, nm in ((hist, "hist"), (bank, "bank")):
+                if t is not None:
+                    self._chk(t, f"{descr}.{nm}", torch.float32)
+                    if not t.is_contiguous():
+                        raise L.ImhError(f"{descr}: {nm} must be contiguous")
+            b, bias = hist, bank
         e = L.EwArgs()
         e.a, e.b, e.y, e.w, e.bias = self._p(a), self._p(b), y.data_ptr(), self._p(w), self._p(bias)
         e.tab, e.step = self._p(tab), self._p(step)

@@ -44,6 +44,8 @@ class DenoiseEngine:
         self._sched_key = None
         self.t_start = 0         # image-to-image: the first step of the schedule that runs (set_schedule)
         self.inpaint = None      # None | "blend" (4-channel UNet: masked blend in the step) | "concat" (9-channel UNet: conv_in reads the mask)
+        self.general = False     # the schedule steps through the six-column table (EW_CFG_MSTEP): multistep / ancestral samplers (set_schedule)
+        self.stochastic = False  # ... and reads a noise row per step
 
     # -- conditioning (once per image / per PNS run; shared by every candidate seed) --
     @torch.no_grad()
@@ -86,13 +88,15 @@ class DenoiseEngine:
         old = self.st
         self.st = st
         if old is not None:                      # keep per-run tables
-            for k in ("latents", "t_table", "step", "in_scale_tab", "ip_scale_tab", "coef_tab", "blend_tab") + self._INPAINT_BUFFERS:
+            for k in ("latents", "t_table", "step", "in_scale_tab", "ip_scale_tab", "coef_tab", "blend_tab") + self._GENERAL_STEP + self._INPAINT_BUFFERS:
                 setattr(st, k, getattr(old, k, None))
         self.plan = None                         # conditioning buffers changed -> re-record
         return st
 
     # inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
     _INPAINT_BUFFERS = ("inp_z", "inp_noise", "inp_mask", "conv_in_extra")
+    # what a plan that ends with the general step (EW_CFG_MSTEP) points at besides: the six-column table, the history slot and the noise bank
+    _GENERAL_STEP = ("coef6_tab", "hist", "noise_bank")
 
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
@@ -104,7 +108,14 @@ class DenoiseEngine:
         same schedule, so the mode is part of the plan key.
         t_start > 0 (image-to-image, diffusers get_timesteps): the loop runs timesteps[t_start:] -- the device step counter starts at
         t_start, so the full schedule's tables, time-embedding rows and recorded plan serve; denoising_end then cuts the truncated list
-        and the IP-scale gating window counts it"""
+        and the IP-scale gating window counts it.
+        A scheduler with ``general_step`` (schedulers.DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler) hands over a six-column
+        table, tables(t_start)["coef6"], in place of ``coef``; the plan then ends with EW_CFG_MSTEP.  Its row at t_start is first order, so
+        a text-to-image and an image-to-image call get different tables -- and, the table being part of the fingerprint, different plans --
+        exactly where the rows differ.  Allocated here for such a schedule: st.hist, fp32 [S, 4, H, W] (the previous data prediction, when
+        the scheduler needs one), and st.noise_bank, fp32 [num_inference_steps, S, 4, H, W], for a stochastic scheduler: row r is the
+        noise of step r, filled by denoise() before the loop.  At 1024^2 the bank is 4 * 128 * 128 * 4 B = 256 KiB per step and sample,
+        about 8 MB per sample for 30 steps."""
         st, dev = self.st, self.device
         t_start = int(t_start)
         if not 0 <= t_start < int(num_inference_steps):
@@ -114,9 +125,10 @@ class DenoiseEngine:
         # the key carries a fingerprint of the tables themselves (timesteps, coefficients, input scale, init sigma): a scheduler instance
         # configured differently (betas, spacing, prediction type) under the same class name must not reuse another schedule's plan
         scheduler.set_timesteps(num_inference_steps)
-        tab = scheduler.tables()
+        general = bool(getattr(scheduler, "general_step", False))
+        tab = scheduler.tables(t_start) if general else scheduler.tables()
         fp = hashlib.sha1()
-        for k in ("timesteps", "coef", "in_scale"):
+        for k in ("timesteps", "coef", "in_scale") + (("coef6",) if general else ()):      # every table the plan reads
             v = tab.get(k)
             fp.update(b"-" if v is None else v.detach().to("cpu", torch.float64).contiguous().numpy().tobytes())
         fp.update(repr(float(tab["init_noise_sigma"])).encode())
@@ -139,11 +151,13 @@ class DenoiseEngine:
         key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), mode)
         self.t_start = t_start
         self.inpaint = mode
+        self.general = general
+        self.stochastic = general and bool(getattr(scheduler, "stochastic", False))
         hit = self._plans.get(key)
         if hit is not None:
             # a schedule this engine has run under this conditioning: its tables, time-embedding rows and recorded plan are still there
             # (the plan's launches point at them), so a preview / final alternation re-records nothing
-            for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab"):
+            for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + self._GENERAL_STEP:
                 setattr(st, k, hit["st"][k])
             self.steps, self.init_noise_sigma = hit["steps"], hit["init_noise_sigma"]
             self.plan, self.noise_pred, self._temb_ctx = hit["plan"], hit["noise_pred"], hit["temb_ctx"]
@@ -151,7 +165,16 @@ class DenoiseEngine:
             self._sched_key = key
             return
         st.t_table = tab["timesteps"].to(dev)
-        st.coef_tab = tab["coef"].contiguous().to(dev)
+        st.coef_tab = tab["coef"].contiguous().to(dev) if tab.get("coef") is not None else None
+        st.coef6_tab = st.hist = st.noise_bank = None
+        if general:
+            if tuple(tab["coef6"].shape) != (int(num_inference_steps), 6):
+                raise L.ImhError(f"the scheduler's coef6 table is {tuple(tab['coef6'].shape)}, expected ({int(num_inference_steps)}, 6)")
+            st.coef6_tab = tab["coef6"].to(torch.float32).contiguous().to(dev)
+            if getattr(scheduler, "needs_history", False):
+                st.hist = torch.zeros(self.S, 4, self.H, self.W, dtype=torch.float32, device=dev)
+            if self.stochastic:
+                st.noise_bank = torch.zeros(int(num_inference_steps), self.S, 4, self.H, self.W, dtype=torch.float32, device=dev)
         st.in_scale_tab = tab["in_scale"].to(dev) if tab["in_scale"] is not None else None
         st.ip_scale_tab = torch.tensor(gate, dtype=torch.float32, device=dev)
         st.blend_tab = self.blend_table(scheduler, num_inference_steps, n).to(dev) if mode == "blend" else None
@@ -180,11 +203,16 @@ class DenoiseEngine:
         for k in ("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
                   "xcd_candidates", "xcd_cells", "t_start", "inpaint"):
             setattr(e, k, getattr(self, k))
+        e.general, e.stochastic = self.general, self.stochastic
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
         st.t_table, st.coef_tab, st.in_scale_tab, st.ip_scale_tab = src.t_table, src.coef_tab, src.in_scale_tab, src.ip_scale_tab
         st.blend_tab = getattr(src, "blend_tab", None)               # (the mask, image latents and noise are the fork's own: _record)
+        st.coef6_tab = getattr(src, "coef6_tab", None)
+        for k in ("hist", "noise_bank"):                             # the general step's state is the fork's own, like its latents
+            v = getattr(src, k, None)
+            setattr(st, k, None if v is None else torch.zeros_like(v))
         st.step = torch.zeros(1, dtype=torch.int32, device=self.device)
         e.st = st
         return e
@@ -228,8 +256,12 @@ class DenoiseEngine:
                 fac = tail.new(self.S, dtype=torch.float32)
                 tail.ew(L.EW_CFG_RESCALE, fac, a=self.np_full, i=(self.S, self.H * self.W, 0, 0, 0, 0),
                         f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
-            tail.ew(L.EW_CFG_STEP, st.latents, a=self.np_full, w=fac, tab=st.coef_tab, step=st.step,
-                    i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
+            if self.general:
+                tail.ew(L.EW_CFG_MSTEP, st.latents, a=self.np_full, w=fac, tab=st.coef6_tab, step=st.step, hist=st.hist, bank=st.noise_bank,
+                        i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+mstep")
+            else:
+                tail.ew(L.EW_CFG_STEP, st.latents, a=self.np_full, w=fac, tab=st.coef_tab, step=st.step,
+                        i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
             tail.ew(L.EW_STEP_SET, st.step, i=(0, 0, 0, 0, 0, 0), descr="step++")
             if self.use_graph:
                 tail.capture()
@@ -242,7 +274,14 @@ class DenoiseEngine:
             fac = rec.new(self.S, dtype=torch.float32)
             rec.ew(L.EW_CFG_RESCALE, fac, a=out, i=(self.S, self.H * self.W, 0, 0, 0, 0),
                    f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
-        if self.inpaint == "blend":
+        if self.general:
+            # the multistep / ancestral samplers: the same launch with the six-column row, the history slot and the step's noise row
+            # (imh.h IMH_EW_CFG_MSTEP); the blend rides in it as it rides in EW_CFG_STEP
+            kw = dict(x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab) if self.inpaint == "blend" else {}
+            rec.ew(L.EW_CFG_MSTEP, st.latents, a=out, w=fac, tab=st.coef6_tab, step=st.step, hist=st.hist, bank=st.noise_bank,
+                   i=(self.S, self.H * self.W, 0, int(self.do_cfg), self.S if kw else 0, 0), f=(0.0, 0.0, self.guidance, 0.0),
+                   descr="cfg+mstep+blend" if kw else "cfg+mstep", **kw)
+        elif self.inpaint == "blend":
             # ... and upstream's masked blend in the same launch (imh.h IMH_EW_CFG_STEP): no extra launch, no extra pass over the latents
             rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
                    i=(self.S, self.H * self.W, 0, int(self.do_cfg), self.S, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step+blend",
@@ -262,7 +301,7 @@ class DenoiseEngine:
             return
         st = self.st
         self._plans[self._sched_key] = dict(
-            st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab")},
+            st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + self._GENERAL_STEP},
             steps=self.steps, init_noise_sigma=self.init_noise_sigma, plan=self.plan, noise_pred=self.noise_pred,
             temb_ctx=self._temb_ctx, plan_tail=getattr(self, "plan_tail", None), np_full=getattr(self, "np_full", None))
         while len(self._plans) > self.max_cached_plans:              # (each plan keeps ~2 GB of activation buffers alive at 1024^2)
@@ -295,21 +334,54 @@ class DenoiseEngine:
         self.xcd_times_ms = times
         return min(times, key=times.get), times
 
+    @staticmethod
+    def draw_step_noise(shape, steps, generator=None):
+        """the per-step noise of a stochastic scheduler, fp32 [steps, *shape]: one randn_latents(shape, generator) call per step that
+        runs, in step order -- the order in which diffusers' scheduler.step consumes the generator (a generator list: one draw per
+        sample and step).  The caller makes the initial-latents draws first."""
+        from .pipeline import randn_latents
+        return torch.stack([randn_latents(tuple(shape), generator) for _ in range(int(steps))], 0)
+
+    def _start_general_step(self, generator=None, step_noise=None):
+        """before the loop of a plan that ends with EW_CFG_MSTEP: the history slot is zeroed (the first row that runs is first order and
+        has ch = 0, but 0 * NaN is NaN: stale contents must not be relied on to be finite), and a stochastic scheduler's noise goes into
+        rows t_start .. steps - 1 of the bank, so that the loop itself stays graph replays with no host work in between"""
+        st = self.st
+        if st.hist is not None:
+            st.hist.zero_()
+        if not self.stochastic:
+            if step_noise is not None:
+                raise L.ImhError("step_noise= is for stochastic schedulers; this schedule draws no noise")
+            return
+        m = self.steps - self.t_start
+        shape = (self.S, 4, self.H, self.W)
+        if step_noise is None:
+            step_noise = self.draw_step_noise(shape, m, generator)
+        if tuple(step_noise.shape) != (m,) + shape:
+            raise L.ImhError(f"step_noise {tuple(step_noise.shape)} for {m} steps of {shape}")
+        st.noise_bank[self.t_start:self.steps].copy_(step_noise.to(self.device, torch.float32))
+
     @torch.no_grad()
     def denoise_cfg_split(self, latents, exchange):
         """One candidate's denoise shared by TWO ranks (engines with cfg_role 0 and 1 on the same conditioning and noise): per step
         each runs the UNet on its half of the CFG pair, `exchange(mine [S*HW*4...]) -> (uncond, cond)` swaps the halves (pns.
         pair_exchange: one all_gather of [S, HW, 4] values over xGMI), and both apply the identical combine + scheduler step, so
         the latents stay bit-equal on the two ranks without further traffic.  The two-stage PNS tail (assets/1.png: the judged-best
-        noise x the full denoise) is then `steps` batch-S forwards deep instead of batch-2S ones."""
+        noise x the full denoise) is then `steps` batch-S forwards deep instead of batch-2S ones.
+        A multistep scheduler's tail plan ends with the same EW_CFG_MSTEP as the one-rank plan.  Stochastic schedulers (SDE-DPM-Solver++,
+        Euler ancestral) are refused here: the two ranks would have to fill identical noise banks."""
         if getattr(self, "cfg_role", None) is None or not self.do_cfg:
             raise L.ImhError("denoise_cfg_split needs an engine whose conditioning was set with cfg_role = 0 / 1 and guidance > 1")
+        if self.stochastic:
+            raise NotImplementedError("denoise_cfg_split does not run stochastic schedulers: both ranks would need identical noise banks")
         if self.t_start or self.inpaint:
             raise NotImplementedError("denoise_cfg_split runs whole text-to-image schedules (t_start = 0, no inpainting)")
         if self.plan is None:
             self._record()
         st = self.st
         st.latents.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)
+        if self.general:
+            self._start_general_step()
         self.eager.ew(L.EW_STEP_SET, st.step, i=(0, 1, 0, 0, 0, 0), descr="step=0")
         for _ in range(self.steps):
             self.plan.replay()
@@ -371,11 +443,15 @@ class DenoiseEngine:
         return st.latents
 
     @torch.no_grad()
-    def denoise(self, latents, callback=None, callback_steps=1):
+    def denoise(self, latents, callback=None, callback_steps=1, generator=None, step_noise=None):
         """latents: [S, 4, H/8, W/8] unit-variance noise (CPU or device), or None: the latent buffer already holds the initial latents
         (prepare_img2img).  Runs the steps t_start .. steps - 1 of the schedule (t_start = 0 unless set_schedule was given one).  Returns
         final fp32 latents (output_type='latent' of custom_pipelines.py:365-379).  callback(i, t, latents) every ``callback_steps``
-        steps (:359-363; i counts the steps that run from 0) is the only thing that makes the host wait inside the loop."""
+        steps (:359-363; i counts the steps that run from 0) is the only thing that makes the host wait inside the loop.
+        A stochastic scheduler (SDE-DPM-Solver++, Euler ancestral) reads one noise row per step: ``step_noise``, fp32 [steps that run,
+        S, 4, H/8, W/8], or drawn here from ``generator`` (draw_step_noise: one randn_latents call per step, in step order, after the
+        caller's initial-latents draws -- diffusers' order; None: torch's global generator, as diffusers).  It is copied into the
+        device noise bank BEFORE the loop (about 8 MB per sample for 30 steps at 1024^2), so the loop is still graph replays only."""
         if getattr(self, "cfg_role", None) is not None and self.do_cfg:
             raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
         if self.inpaint and latents is not None:
@@ -388,6 +464,10 @@ class DenoiseEngine:
         if latents is not None:
             st.latents.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)     # prepare_latents :255-265
         t0 = self.t_start
+        if self.general:
+            self._start_general_step(generator, step_noise)
+        elif step_noise is not None:
+            raise L.ImhError("step_noise= is for stochastic schedulers; this schedule draws no noise")
         self.eager.ew(L.EW_STEP_SET, st.step, i=(t0, 1, 0, 0, 0, 0), descr="step=t_start")
         for i in range(t0, self.steps):                                     # :325 -- no host work per step
             self.plan.replay()

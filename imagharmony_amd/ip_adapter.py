@@ -263,6 +263,8 @@ class IPAdapterXL(IPAdapter):
         ``batch`` = preview candidates stacked per UNet forward on a rank; None (default) = as many as the rank holds, up
         to 4 (BASELINE.json configs[4] runs 4 per GPU): a stacked forward costs 1.27x less per candidate than one at a
         time on MI355X (bench.py ``stacked_candidates`` / ``pns_two_stage``); the final denoise is batch 1 either way.
+        Under a stochastic scheduler on the pipe (SDE-DPM-Solver++, Euler ancestral) the per-step noise of every preview and of the
+        final denoise comes from torch's global generator (pns.two_stage_fns has the details): a seed then fixes the initial noise only.
         Returns dict(images, best_seed, scores, latents).  Text-to-image only: an image-to-image or inpainting pipeline raises NotImplementedError."""
         from . import pns
         from .pipeline import StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline

@@ -19,7 +19,7 @@ GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL
 OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN, OP_ATTN_ENC, OP_ATTN_ENC_CAUSAL = range(10)
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
- EW_ROW_STATS, EW_STEP_ROW, EW_GATHER_ROWS) = range(13)
+ EW_ROW_STATS, EW_STEP_ROW, EW_GATHER_ROWS, EW_CFG_MSTEP) = range(14)
 
 # variant codes / modes that only a -DIMH_EXPERIMENTAL build compiles (csrc/imh_common.h IMH_EXP_ONLY): measured, selected by no
 # tuning.json entry and no default mode.  experimental() asks the loaded library (imh_debug_set(1, 0)).

@@ -108,7 +108,7 @@ class StableDiffusionXLCustomPipeline:
                          denoising_end=denoising_end)
         if latents is None:
             latents = randn_latents((S, 4, height // 8, width // 8), generator)       # prepare_latents :255-265
-        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps).clone()
+        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps, generator=generator).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
 
@@ -209,7 +209,7 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
         n2 = randn_latents((S, 4, h, w), generator)
         a, b = sch.add_noise_coefficients(t_start)
         eng.prepare_img2img(moments, n1, n2, vae.config.scaling_factor, a, b)
-        out = eng.denoise(None, callback=callback, callback_steps=callback_steps).clone()
+        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, generator=generator).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
 
@@ -323,6 +323,6 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
         a, b = sch.add_noise_coefficients(t_start)
         eng.prepare_inpaint(moments, n1, n2, vae.config.scaling_factor, a, b, latent_mask(mask, h, w), strength_max=strength_max,
                             masked_moments=masked_moments, n3=n3)
-        out = eng.denoise(None, callback=callback, callback_steps=callback_steps).clone()
+        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, generator=generator).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)

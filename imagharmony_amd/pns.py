@@ -136,7 +136,12 @@ class ClipPreferenceJudge:
 def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, **schedule_kw):
     """The two-stage schedule of assets/1.png on a ``DenoiseEngine`` whose conditioning is set: every candidate seed
     gets a ``preview_steps`` denoise ("+10 steps"), the judged-best noise the full ``final_steps`` one ("+30 steps").
-    Returns (preview_fn, final_fn) for ``run_pns``."""
+    Returns (preview_fn, final_fn) for ``run_pns``.
+    Under a stochastic scheduler (SDE-DPM-Solver++, Euler ancestral) these functions hand the engine no generator: each denoise draws
+    its per-step noise from torch's global generator, so a candidate seed fixes the initial noise only -- the preview and the final
+    run of the chosen seed use unrelated step noise, a seed does not reproduce its latent, and ranks differ.  Pass
+    ``engine.denoise(noise, generator=...)`` / ``step_noise=`` yourself where that matters; the deterministic samplers (DDIM, Euler,
+    DPM++ 2M with or without Karras sigmas) are unaffected."""
     def preview(noise):
         engine.set_schedule(scheduler, preview_steps, **schedule_kw)
         return engine.denoise(noise).clone()

@@ -510,6 +510,9 @@ class StepState:
         self.conv_in_extra = None  # fp32 [S, 5, H, W] (NCHW): [mask | masked-image latents], channels 4-8 of a 9-channel conv_in (inpainting UNet)
         self.blend_tab = None      # fp32 [steps, 2] add_noise pair of the inpainting blend per step (4-channel UNet), or None
         self.inp_z = self.inp_noise = self.inp_mask = None   # fp32 [S, 4 | 4 | 1, H, W]: image latents, add-noise noise, latent mask of that blend
+        self.coef6_tab = None      # fp32 [steps, 6] (cx, ce, ch, cn, hx, he) of the general step (multistep / ancestral schedulers), or None
+        self.hist = None           # fp32 [S, 4, H, W] its history slot: the previous step's data prediction, or None
+        self.noise_bank = None     # fp32 [steps, S, 4, H, W] its per-step noise (stochastic schedulers), or None
         self.t_table = None        # fp32 [steps] timesteps
         self.step = None           # int32 [1] device step counter
         self.in_scale_tab = None   # fp32 [steps] scale_model_input factor (Euler) or None

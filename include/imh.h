@@ -40,7 +40,8 @@ extern "C" {
 
 /* Still 13 after the CLIP text towers: what they added is strictly additive -- one entry (imh_attention_enc_causal), one plan kind
  * (IMH_OP_ATTN_ENC_CAUSAL = 9), one imh_gemm flag bit (IMH_GF_ACT_QGELU = 128) and one elementwise op (IMH_EW_GATHER_ROWS, 12); no
- * struct changed, and a caller written against the first version 13 cannot observe any of it. */
+ * struct changed, and a caller written against the first version 13 cannot observe any of it.  The same holds for the general
+ * CFG + scheduler step of the multistep and ancestral samplers, IMH_EW_CFG_MSTEP (13): one more elementwise op on imh_ew_args as it is. */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
@@ -429,7 +430,7 @@ enum imh_ew_op {
     IMH_EW_SOFTMAX = 9,     /* y[r,:] (T) = softmax(f0 * a[r,:]) with a fp32 (VAE mid-block attention); i0 rows, i1 cols, i2 / i3 leading dims */
     IMH_EW_ROW_STATS = 10,  /* y[r] (fp32 pair) = (sum, M2) of a[r, 0:i0] (row stride i1), n rows: LayerNorm statistics in the ln_stats format, one slot */
     IMH_EW_STEP_ROW = 11,   /* y[0:n] = a[*step * n + 0:n] (T; n % 8 == 0): row `step` of a per-schedule table (time embeddings of all denoise steps) */
-    IMH_EW_GATHER_ROWS      /* 12, numbered by its place behind IMH_EW_STEP_ROW (tests/test_host_logic.py pins the count of explicitly
+    IMH_EW_GATHER_ROWS,     /* 12, numbered by its place behind IMH_EW_STEP_ROW (tests/test_host_logic.py pins the count of explicitly
                              * numbered ops of ABI 13 at twelve; this one is the additive thirteenth).  y[r, 0:C] = table[idx[r], 0:C] (+ add[r mod P, 0:C]), r in [0, n): the CLIP text towers' token + position embedding
                              * (add = the position table, P = 77) and their EOS pooling (no add; table = the final-layer-normed hidden rows,
                              * idx[b] = b * L + eos position).  Fields: a = table (T, i5 rows, row stride i1), b = idx (int32 [n], device), w = add
@@ -437,6 +438,17 @@ enum imh_ew_op {
                              * accesses; table / add / y 16-byte aligned), strides >= C.  The sum is taken in fp32 and rounded once.  The CALLER
                              * validates idx against [0, i5) before uploading it; a row with an index outside that range is skipped (not
                              * read, not written), never followed. */
+    IMH_EW_CFG_MSTEP        /* 13, by its place behind IMH_EW_GATHER_ROWS (additive: imh_ew_args does not grow, the ABI version stays).  The
+                             * general CFG + scheduler step of the multistep and ancestral samplers (DPM-Solver++ 2M, SDE-DPM-Solver++ 2M, Euler
+                             * ancestral), one pass over the fp32 NCHW latents y [i0, 4, i1]:
+                             *   eps = IMH_EW_CFG_STEP's: a = noise prediction NHWC [2 i0 | i0, i1, 4] (i3 = 1: [uncond | cond], f2 = guidance scale),
+                             *         times w[s] when w (the IMH_EW_CFG_RESCALE factor) is set;
+                             *   (cx, ce, ch, cn, hx, he) = tab[6 * *step + 0..5]   (tab and step REQUIRED; fp32 [n, 6]);
+                             *   y' = cx * y + ce * eps + ch * h + cn * z,   h' = hx * y + he * eps   (all fp32),
+                             * h = `b`, a fp32 history buffer [i0, 4, i1] that the launch READS AND WRITES in place (each element by one
+                             * thread), z = row *step of the fp32 noise bank `bias` [n, i0, 4, i1].  b == NULL / bias == NULL: that term is
+                             * absent (and h is not written).  With `mask` set the masked blend of IMH_EW_CFG_STEP follows in the same pass, same
+                             * fields, same blend_tab -- except that `a` is REQUIRED here: there is no blend-alone form (a == NULL is an error).  With ch = cn = 0 and neither h nor bank the result equals IMH_EW_CFG_STEP's bit for bit. */
 };
 
 typedef struct imh_ew_args {
@@ -461,7 +473,9 @@ typedef struct imh_ew_args {
 /* Memory: every elementwise op reads and writes exactly the elements its description counts (n, or the i0..i5 extents) of dense buffers;
  * IMH_EW_SOFTMAX and IMH_EW_ROW_STATS take row strides and leave the gaps [cols, ld) alone; IMH_EW_STEP_SET touches the one int32 at y;
  * IMH_EW_STEP_ROW reads row *step of `a` only; `tab` / `blend_tab` are read at row *step only; IMH_EW_GATHER_ROWS reads idx[0, n), columns
- * [0, C) of the table rows idx names and of add's rows [0, min(n, P)), and writes columns [0, C) of y's rows [0, n). */
+ * [0, C) of the table rows idx names and of add's rows [0, min(n, P)), and writes columns [0, C) of y's rows [0, n).  IMH_EW_CFG_MSTEP reads
+ * its six-column `tab` and the noise bank `bias` at row *step only (6 floats and i0 * 4 * i1 floats), and reads and writes exactly the
+ * i0 * 4 * i1 elements of y and of the history buffer `b`. */
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
