@@ -321,6 +321,32 @@ int imh_gemm_pick_config(int M, int N, int K, int* bm, int* bn, int* splits) {
 size_t imh_gemm_workspace_bytes(int M, int N, int splits) { return gemm_workspace_bytes(M, N, splits); }
 int imh_gemm_stats_slot_width(int bm, int bn) { return gemm_stats_slot_width(bm, bn); }
 int imh_gemm_gn_block_rows(int bm, int bn) { return gemm_gn_block_rows(bm, bn); }
+int imh_conv_halo_lds_bytes(int bm, int bn, int Cin, int gn) { return conv_halo_lds_bytes(bm, bn, Cin, gn); }
+
+// every check of imh_gemm without the launch: the call is issued into a stream capture of its own whose graph is thrown away, so the
+// validators that run are the launchers' own and nothing executes.  The capture stream belongs to the calling thread and to the device
+// that is current at the call (one per device the thread ever checks on, created at the first check there and kept for the life of the
+// thread); the cost is one begin / end capture pair per call, paid where a launch is recorded and never at replay
+int imh_gemm_check(const imh_gemm_args* a) {
+    static thread_local std::vector<hipStream_t> streams;          // [device]
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) { (void)hipGetLastError(); set_error("gemm_check: no current device"); return IMH_ERR_LAUNCH; }
+    if ((size_t)dev >= streams.size()) streams.resize(dev + 1, nullptr);
+    hipStream_t& cs = streams[dev];
+    if (!cs && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) {
+        cs = nullptr; (void)hipGetLastError();
+        set_error("gemm_check: no stream to validate on"); return IMH_ERR_LAUNCH;
+    }
+    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("gemm_check: begin: %s", hipGetErrorString(e)); return IMH_ERR_LAUNCH; }
+    const int rc = do_gemm(a, cs);
+    hipGraph_t g = nullptr;
+    e = hipStreamEndCapture(cs, &g);
+    if (g) hipGraphDestroy(g);
+    if (rc != IMH_OK) { (void)hipGetLastError(); return rc; }
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("gemm_check: end: %s", hipGetErrorString(e)); return IMH_ERR_LAUNCH; }
+    return IMH_OK;
+}
 
 int imh_attention(const imh_attn_args* a, void* stream) { return do_attn(a, (hipStream_t)stream); }
 

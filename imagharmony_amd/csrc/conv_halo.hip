@@ -495,12 +495,32 @@ __global__ __launch_bounds__(64 * (8 + HWV), HWV ? (8 + HWV) / 4 : (S == 2 ? 2 :
 // instead of 0.6 and 24.6 KB instead of 42.5 KB of operands per step for the 320-channel convolutions at the 128 x 128 latent)
 // with a 2- / 3-slot weight ring
 int conv_hws_launch(const GemmParams& p, int dtype, int ph, int tiles_x, int tiles_y, int tiles_n, int B, int lds_tab, hipStream_t stream);     // conv_hws.hip
+int conv_hws_lds_bytes(int ph, int lds_tab);                                                                                                                  // conv_hws.hip
+static int halo_patch_rows(int bm) { return bm == 7564 ? 4 : ((bm == 7256 || bm == 7356) ? 16 : 8); }
+static int halo_ring_slots(int bm, int bn) { return bn == 80 ? (halo_patch_rows(bm) == 16 ? 2 : 3) : ((bm == 7328 || bm == 7356) ? 3 : (bm == 7428 ? 4 : 2)); }
+// which kernel family runs variant bm x bn under the current g_halo_mode: the wave-specialised conv_hws.hip or the kernels of this file
+static bool halo_runs_hws(int bm, int bn) { return bn == 160 && (bm == 7128 || bm == 7256 || bm == 7356) && g_halo_mode == 0; }
+
+// bytes of LDS a launch of LDS-halo variant bm x bn takes for Cin input channels, gn != 0: with the fused GroupNorm front end's table --
+// of the kernel the launch would run under the current g_halo_mode; the ONE statement of it (conv_halo_launch / conv_hws_launch refuse
+// above 160 KB, imh_conv_halo_lds_bytes hands it to the host layer); -1: not an LDS-halo variant
+int conv_halo_lds_bytes(int bm, int bn, int Cin, int gn) {
+    if (bm != 7128 && bm != 7564 && bm != 7328 && bm != 7428 && bm != 7256 && bm != 7356) return -1;
+    if ((bn != 320 && bn != 160 && bn != 80) || Cin < 0) return -1;
+    const int ph = halo_patch_rows(bm), tab = gn ? Cin * 8 : 0;
+    if (halo_runs_hws(bm, bn)) return conv_hws_lds_bytes(ph, tab);
+    const bool ks = bn == 80;
+    int lds = 2 * (((ph + 2) * CH_HW + 7) / 8) * 8 * GEMM_ROW_BYTES + halo_ring_slots(bm, bn) * (ks ? 3 : 1) * bn * GEMM_ROW_BYTES + tab;
+    if (ks && lds < 4 * (ph / 4) * 5 * 64 * 16) lds = 4 * (ph / 4) * 5 * 64 * 16;       // the pairs' accumulator exchange (40 / 80 KB) reuses the staging area
+    return lds;
+}
+
 int conv_halo_launch(const GemmParams& p, int dtype, int bm, int bn, hipStream_t stream) {
-    const int ph = bm == 7564 ? 4 : ((bm == 7256 || bm == 7356) ? 16 : 8);
+    const int ph = halo_patch_rows(bm);
     // bn = 80: k halves per wave pair, three taps per step, service waves -- 7128 x 80: 8 x 16 patch, 3-slot ring; 7256 x 80: 16 x 16 patch
     // (256 pixels x 80 couts: 44 KB of LDS-DMA per 240-MFMA step instead of 22.6 KB per 80 on 7128 x 160), 2-slot ring
     const bool ks = bn == 80;
-    const int S = ks ? (ph == 16 ? 2 : 3) : ((bm == 7328 || bm == 7356) ? 3 : (bm == 7428 ? 4 : 2));
+    const int S = halo_ring_slots(bm, bn);
     if (p.stride != 1 || p.splits > 1 || p.Cin % GEMM_BK != 0 || p.K != 9 * p.Cin || (bn != 320 && bn != 160 && bn != 80) || ((S > 2 || ph == 16) && bn != 160 && !ks) ||
         (ks && bm != 7128 && bm != 7256)) {
         set_error("conv_halo: stride-1 conv3x3 with Cin %% 64 == 0, splits == 1, bn 320 | 160 (160 only for the 3- / 4-slot rings) | 80 (7128 only) (stride=%d splits=%d Cin=%d bm=%d bn=%d)", p.stride, p.splits, p.Cin, bm, bn);
@@ -517,9 +537,8 @@ int conv_halo_launch(const GemmParams& p, int dtype, int bm, int bn, hipStream_t
         set_error("conv_halo: Cin1=%d must be a positive multiple of 64, = Cin=%d exactly when there is no second source", p.Cin1, p.Cin);
         return IMH_ERR_ARG;
     }
-    int lds = 2 * (((ph + 2) * CH_HW + 7) / 8) * 8 * GEMM_ROW_BYTES + S * (ks ? 3 : 1) * bn * GEMM_ROW_BYTES + (gnf ? p.Cin * 8 : 0);
-    if (ks && lds < 4 * (ph / 4) * 5 * 64 * 16) lds = 4 * (ph / 4) * 5 * 64 * 16;       // the pairs' accumulator exchange (40 / 80 KB) reuses the staging area
-    if (lds > 160 * 1024) { set_error("conv_halo: %d bytes of LDS (variant %d x %d, Cin=%d with the GroupNorm table)", lds, bm, bn, p.Cin); return IMH_ERR_SHAPE; }
+    const int lds = conv_halo_lds_bytes(bm, bn, p.Cin, gnf);
+    if (!halo_runs_hws(bm, bn) && lds > 160 * 1024) { set_error("conv_halo: %d bytes of LDS (variant %d x %d, Cin=%d with the GroupNorm table)", lds, bm, bn, p.Cin); return IMH_ERR_SHAPE; }
     // the fused GroupNorm front end runs on the form with four halo waves (the input side off the MFMA waves); g_halo_mode
     // (imh_debug_set key 5, A/B): 1 forces the eight-wave form, 2 the halo-wave form for every launch
     // the four halo waves for every launch (round 5: the un-fused launches gain too -- upsample 8192 x 1280 x 11520 258 -> 245 us,
@@ -527,7 +546,7 @@ int conv_halo_launch(const GemmParams& p, int dtype, int bm, int bn, hipStream_t
     const bool hw4 = g_halo_mode != 1;
     // round 6: the 16 x 16 / 8 x 16 patch x 160 couts forms run wave-specialised (conv_hws.hip: same geometry, bit-identical results);
     // g_halo_mode 6 = the kernels below (A/B, the bit-identity test)
-    if (!ks && bn == 160 && (bm == 7128 || bm == 7256 || bm == 7356) && g_halo_mode == 0)
+    if (halo_runs_hws(bm, bn))
         return conv_hws_launch(p, dtype, ph, tiles_x, tiles_y, tiles_n, B, gnf ? p.Cin * 8 : 0, stream);
 #define IMH_CH6(TT, FNV, FMV, SV, HV, KSV, SVCV) IMH_CH7(TT, FNV, FMV, SV, HV, KSV, SVCV, false)
 #define IMH_CH7(TT, FNV, FMV, SV, HV, KSV, SVCV, SHV) do { auto kern = conv_halo_kernel<TT, FNV, FMV, SV, HV, KSV, SVCV, SHV>; static DynLdsOnce lds_once; \

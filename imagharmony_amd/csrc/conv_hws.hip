@@ -357,11 +357,16 @@ __global__ __launch_bounds__(64 * (HW_NC + HW_NP), 1) void conv_hws_kernel(const
     if (p.gn_out) gn_emit<4 * FN>(p.gn_out, p.gn_nblk, p.N / 10, b, (ty * tiles_x + tx) * 4 + wm, nb, gna, FM, lane);
 }
 
-// ph = 16 | 8 (the 7256 / 7356 and 7128 variant codes at 160 couts); lds_tab = bytes of the GroupNorm table (0 without the fused front end)
-int conv_hws_launch(const GemmParams& p, int dtype, int ph, int tiles_x, int tiles_y, int tiles_n, int B, int lds_tab, hipStream_t stream) {
+// bytes of LDS of one workgroup: two halo buffers, the weight ring (three slots for the 16-row patch, four for the 8-row one), the table
+int conv_hws_lds_bytes(int ph, int lds_tab) {
     const int hpieces = ((ph + 2) * HW_HW + 7) / 8;
     const int S = ph == 16 ? 3 : 4;
-    const int lds = 2 * hpieces * 8 * GEMM_ROW_BYTES + S * HW_W_BYTES + lds_tab;
+    return 2 * hpieces * 8 * GEMM_ROW_BYTES + S * HW_W_BYTES + lds_tab;
+}
+
+// ph = 16 | 8 (the 7256 / 7356 and 7128 variant codes at 160 couts); lds_tab = bytes of the GroupNorm table (0 without the fused front end)
+int conv_hws_launch(const GemmParams& p, int dtype, int ph, int tiles_x, int tiles_y, int tiles_n, int B, int lds_tab, hipStream_t stream) {
+    const int lds = conv_hws_lds_bytes(ph, lds_tab);
     if (lds > 160 * 1024) { set_error("conv_hws: %d bytes of LDS (patch height %d, Cin=%d with the GroupNorm table)", lds, ph, p.Cin); return IMH_ERR_SHAPE; }
     if ((size_t)p.N * p.ldw * 2 >= (1ull << 32)) { set_error("conv_hws: weight matrix beyond 4 GB (32-bit row offsets)"); return IMH_ERR_SHAPE; }
     dim3 grid(B * tiles_y * tiles_x * tiles_n);

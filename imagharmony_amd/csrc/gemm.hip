@@ -489,9 +489,11 @@ int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t s
     }
     if (p.ln_stats_out) {
         const int w = gemm_stats_slot_width(bm, bn);
-        if (w == 0 || p.N % w || p.ln_slots_out != p.N / w || conv || p.splits > 1 || (p.flags & (GF_GEGLU | GF_VT_PERM | GF_OUT_F32))) {
+        // (the folded-LayerNorm launches of the wave-specialised kernels end in their lean epilogue, which emits no statistics)
+        if (w == 0 || p.N % w || p.ln_slots_out != p.N / w || conv || p.splits > 1 || (p.flags & (GF_GEGLU | GF_VT_PERM | GF_OUT_F32)) ||
+            (bm >= 256 && (p.flags & (GF_LN_ROW | GF_LN_COL)))) {
             set_error("gemm: ln_stats_out needs a variant with a statistics epilogue (slot width %d for %dx%d), N %% width == 0, "
-                      "ln_slots_out == N / width, a plain output (N=%d slots=%d flags=%d splits=%d conv=%d)", w, bm, bn, p.N, p.ln_slots_out, p.flags, p.splits, conv);
+                      "ln_slots_out == N / width, a plain output, no folded LayerNorm off the plain tiles (N=%d slots=%d flags=%d splits=%d conv=%d)", w, bm, bn, p.N, p.ln_slots_out, p.flags, p.splits, conv);
             return IMH_ERR_ARG;
         }
     }

@@ -68,6 +68,7 @@ int gemm_gn_block_rows(int bm, int bn);         // pixels per gn_out block of a 
 int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t stream);
 int gemm_dual_launch(GemmParams a, GemmParams b, int dtype, int bm, int bn, hipStream_t stream);
 int gemm_w16_launch(const GemmParams& p, int dtype, hipStream_t stream);      // variant 26256 x 320 (gemm_w16.hip)
+int conv_halo_lds_bytes(int bm, int bn, int Cin, int gn);    // LDS of one LDS-halo conv3x3 launch under the current g_halo_mode (conv_halo.hip), -1 = no such variant
 
 struct AttnParams {
     const void* Q;    // [B, Lq, ldq] (+ head*64 columns)

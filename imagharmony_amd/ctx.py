@@ -192,6 +192,9 @@ class Ctx:
     # ------------------------------------------------------------------ emit
     def _emit(self, kind, args, ew_op=0, descr="", flops=0.0, nbytes=0.0, keep=(), shape=None, epi=None):
         if self.record:
+            if kind == L.OP_GEMM and not self.dry:
+                # a launch the library refuses is refused HERE, not when the plan first runs (imh_plan_add copies the arguments unseen)
+                L.check(self.lib.imh_gemm_check(C.byref(args)), descr or "gemm")
             rc = self.lib.imh_plan_add(self.plan, kind, C.byref(args), ew_op, self.tag)
             if rc < 0:
                 L.check(rc, "imh_plan_add")
@@ -244,8 +247,9 @@ class Ctx:
 
     @classmethod
     def _variant_ok(cls, bm, sp, flags, conv, stride, ln_pre, M=0, N=0, extras=False, pad=0):
-        """extras: the launch has a bias, residual, row-add, second token source or transposed store (the epilogue inputs the
-        sixteen-wave tile has none of: gemm_w16_launch refuses them, and whole tiles only); pad: the conv padding mode
+        """extras: the launch has a bias, residual, row-add, second token source (x2) or transposed store (yt) -- the epilogue inputs the
+        sixteen-wave tile has none of (gemm_w16_launch refuses them, and whole tiles only); x2 and yt narrow the choice further in gemm()
+        itself (plain / wave-specialised tiles; _yt_config); pad: the conv padding mode
         (imh_gemm_args.pad -- 1, right / bottom only, runs on every conv-capable variant except the LDS-halo kernels)"""
         plain = bm <= 128
         if pad and (not conv or bm in cls._HALO + cls._PP + cls._W16):
@@ -308,9 +312,13 @@ class Ctx:
         input -> (y, gn) with gn = GnStats from the epilogue, or None when the chosen variant has no such epilogue (the consumer
         then runs gn_stats over y).
         yt = (Yt [N - col0, ldyt], col0): output columns >= col0 are stored transposed in the V^T layout into Yt instead of y (y
-        then holds columns [0, col0)); wave-specialised bn = 160 variants, flags == GF_LN_ROW only (the one-launch [Q|K|V]).
+        then holds columns [0, col0)); wave-specialised bn = 160 variants and 23256 x 128, flags == GF_LN_ROW only, whole tiles, no
+        residual / row-add (the one-launch [Q|K|V]); without cfg= a table entry or heuristic tile that cannot do it gives way to the first
+        such variant that tiles M, N and col0 (_yt_config), and where none does the call raises here.
         x2: the token operand is the column concat [x | x2] (K = x.shape[1] + x2.shape[1]; the up blocks' conv_shortcut over
-        torch.cat([hidden, skip], 1)) read from its two producers -- plain 64 / 128 tiles and the wave-specialised variants."""
+        torch.cat([hidden, skip], 1)) read from its two producers -- plain 64 / 128 tiles (split-K included) and the wave-specialised
+        variants; without cfg= any other table entry gives way to a plain tile.
+        In a recording context the library's launch checks run at this call (imh_gemm_check), so a refusal never waits for the replay."""
         self._chk(x, descr + ".x"); self._chk(w, descr + ".w")
         M = M if M is not None else x.shape[0]
         K = K if K is not None else x.shape[1] + (x2.shape[1] if x2 is not None else 0)
@@ -343,6 +351,8 @@ class Ctx:
             raise L.ImhError(f"{descr}: stats_out and gn_out are mutually exclusive (one consumer norm per output)")
         bm, bn, sp = cfg or self._config(M, N, K, 0, flags, ln_pre=ln_stats is not None, extras=any(
             t is not None for t in (bias, residual, rowadd, x2, yt)))
+        if yt is not None:
+            bm, bn, sp = self._yt_config(M, N, int(yt[1]), flags, (bm, bn, sp), cfg is not None, residual is not None or rowadd is not None, descr)
         if x2 is not None and not (bm <= 128 or bm in self._WS):
             if cfg is not None:
                 raise L.ImhError(f"{descr}: variant {bm} does not read a two-source token operand")
@@ -380,7 +390,9 @@ class Ctx:
         st = None
         if stats_out and not _args_only:
             wd = self.lib.imh_gemm_stats_slot_width(bm, bn)
-            if wd > 0 and N % wd == 0 and sp == 1 and not flags & (L.GF_GEGLU | L.GF_VT_PERM | L.GF_OUT_F32):
+            # (a folded-LayerNorm launch of a wave-specialised variant ends in the lean epilogue, which emits none: gemm_launch refuses)
+            if wd > 0 and N % wd == 0 and sp == 1 and not flags & (L.GF_GEGLU | L.GF_VT_PERM | L.GF_OUT_F32) \
+                    and not (bm > 128 and flags & (L.GF_LN_ROW | L.GF_LN_COL)):
                 st = (self.new(M, N // wd, 2, dtype=torch.float32), N // wd)
                 a.ln_stats_out, a.ln_slots_out = st[0].data_ptr(), st[1]
         gn = self._gn_epilogue(a, gn_out) if gn_out is not None and not _args_only else None
@@ -405,6 +417,27 @@ class Ctx:
         if gn_out is not None:
             return out, gn
         return out
+
+    # (bm, bn, tile rows) that carry the transposed store (gemm_launch: every wave-specialised variant at bn = 160, and 23256 x 128)
+    _YT = ((23256, 160, 256), (24128, 160, 128), (2464, 160, 64), (1464, 160, 64), (23256, 128, 256), (22128, 160, 128))
+
+    def _yt_config(self, M, N, col0, flags, c, forced, extra, descr):
+        """tile variant of a yt= launch (gemm_launch's rule for imh_gemm_args.Yt): a wave-specialised bn = 160 variant or 23256 x 128, flags ==
+        GF_LN_ROW only, no residual / row-add / split-K, whole tiles, 0 < col0 < N a multiple of bn.  c = what the table / heuristic (or the
+        caller: forced) chose; when that is not such a variant the first of _YT the library builds that tiles M, N and col0 serves"""
+        if flags != L.GF_LN_ROW or extra or not 0 < col0 < N:
+            raise L.ImhError(f"{descr}: Yt (the transposed V^T store, yt=) needs flags == GF_LN_ROW only, no residual / row-add and 0 < col0 < N "
+                             f"(flags={flags}, col0={col0}, N={N})")
+        fits = lambda bm, bn, rows: M % rows == 0 and N % bn == 0 and col0 % bn == 0
+        for bm, bn, rows in self._YT:
+            if (bm, bn) == tuple(c[:2]) and c[2] == 1 and fits(bm, bn, rows):
+                return c
+        if not forced:
+            for bm, bn, rows in self._YT:
+                if L.variant_built((bm, bn)) and fits(bm, bn, rows):
+                    return bm, bn, 1
+        raise L.ImhError(f"{descr}: Yt (the transposed V^T store, yt=) needs a wave-specialised bn = 160 variant or 23256 x 128 with whole tiles and col0 a "
+                         f"multiple of bn (variant {tuple(c)}, M={M}, N={N}, col0={col0})")
 
     def _gn_epilogue(self, a, hw):
         """GroupNorm partials from the launch's epilogue (imh_gemm_args.gn_out) if its variant and shape have one: fills the
@@ -467,10 +500,10 @@ class Ctx:
         bm, bn, sp = cfg or self._config(M, N, K, 1, 0, stride=stride, up=up)
         if bm not in self._HALO or stride != 1 or up:
             return False
-        ph = 4 if bm == 7564 else (16 if bm in (7256, 7356) else 8)
-        S = (6 if ph == 16 else 9) if bn == 80 else (3 if bm in (7328, 7356) else (4 if bm == 7428 else 2))     # (x 80: two / three slots of three tap tiles each)
-        lds = 2 * (((ph + 2) * 18 + 7) // 8) * 8 * 128 + S * bn * 128 + (K // 9) * 8
-        return lds <= 160 * 1024
+        # the table of the front end ([Cin][2] fp32) shares the workgroup's LDS with the halo buffers and the weight ring, whose depth differs
+        # between the kernel families and with the A/B mode (imh_debug_set key 5): the launcher's own byte count, not a copy of it
+        lds = self.lib.imh_conv_halo_lds_bytes(bm, bn, K // 9, 1)
+        return 0 < lds <= 160 * 1024
 
     def conv_up_phase_cfg(self, B, H, W, Cin, Cout, cfg=None):
         """tile variant (bm, bn, 1) of the phase form of an upsampler conv (conv3x3 up=2) over a [B, H, W, Cin] input, or None when the

@@ -124,6 +124,8 @@ SYMBOLS = [
     ("imh_gemm_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("imh_gemm_stats_slot_width", C.c_int, [C.c_int, C.c_int]),
     ("imh_gemm_gn_block_rows", C.c_int, [C.c_int, C.c_int]),
+    ("imh_conv_halo_lds_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("imh_gemm_check", C.c_int, [C.POINTER(GemmArgs)]),
     ("imh_attention", C.c_int, [C.POINTER(AttnArgs), _vp]),
     ("imh_cross_attention", C.c_int, [C.POINTER(XAttnArgs), _vp]),
     ("imh_attention_small", C.c_int, [C.POINTER(SmallAttnArgs), _vp]),

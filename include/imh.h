@@ -41,7 +41,8 @@ extern "C" {
 /* Still 13 after the CLIP text towers: what they added is strictly additive -- one entry (imh_attention_enc_causal), one plan kind
  * (IMH_OP_ATTN_ENC_CAUSAL = 9), one imh_gemm flag bit (IMH_GF_ACT_QGELU = 128) and one elementwise op (IMH_EW_GATHER_ROWS, 12); no
  * struct changed, and a caller written against the first version 13 cannot observe any of it.  The same holds for the general
- * CFG + scheduler step of the multistep and ancestral samplers, IMH_EW_CFG_MSTEP (13): one more elementwise op on imh_ew_args as it is. */
+ * CFG + scheduler step of the multistep and ancestral samplers, IMH_EW_CFG_MSTEP (13): one more elementwise op on imh_ew_args as it is,
+ * and for the two query entries of the dispatch contract, imh_conv_halo_lds_bytes and imh_gemm_check. */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
@@ -217,6 +218,16 @@ int imh_gemm_pick_config(int M, int N, int K, int* bm, int* bn, int* splits);
 int imh_gemm_stats_slot_width(int bm, int bn);
 /* rows per GroupNorm partial block written by tile variant (bm, bn) through gn_out; 0 = no such epilogue */
 int imh_gemm_gn_block_rows(int bm, int bn);
+/* bytes of LDS one launch of LDS-halo conv3x3 variant (bm, bn) takes for Cin input channels, gn != 0: with the table of the fused
+ * GroupNorm front end (gn_tab / gn_part) -- of the kernel the launch would run under the current imh_debug_set key 5 setting.  The
+ * launchers refuse above 160 KB with IMH_ERR_SHAPE; a host layer that chooses between the fused form and passes asks here instead of
+ * restating ring depths.  -1: (bm, bn) is not an LDS-halo variant. */
+int imh_conv_halo_lds_bytes(int bm, int bn, int Cin, int gn);
+/* every check imh_gemm(a, .) makes, without running anything (the launch goes into a stream capture whose graph is discarded):
+ * IMH_OK, or the status imh_gemm would return with imh_last_error() set.  For a caller that records launches into a plan and wants
+ * a refusal where the launch is recorded, not where the plan first runs.  Costs one begin / end capture pair on a
+ * stream the library keeps per calling thread and current device; meant for record time, not for a per-step path. */
+int imh_gemm_check(const imh_gemm_args* a);
 size_t imh_gemm_workspace_bytes(int M, int N, int splits);
 
 /* ---- attention, head_dim 64 -------------------------------------------------------------

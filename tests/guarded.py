@@ -66,6 +66,27 @@ class Arena:
         self._end = 0               # end of the last carve
         self._guard = 0             # its guard
 
+    def reset(self):
+        """the arena as constructed: the sentinel everywhere, no carves (views handed out before are dead)"""
+        self.mem.view(torch.int16).fill_(SENTINEL_I16)
+        self.carves, self._end, self._guard = [], 0, 0
+
+    def seal(self):
+        """every "out" carve so far becomes an "in": what earlier launches wrote are operands of the launch that follows, so that
+        written() speaks of that launch's own outputs"""
+        for c in self.carves:
+            if c["role"] == "out":
+                c["role"] = "in"
+
+    def written(self):
+        """name of the first carve other than an input ("out" / "scratch") that no longer holds the sentinel bit for bit, else None --
+        for a refused launch: it must have left its outputs, side outputs and workspaces untouched"""
+        pat = torch.tensor(SENTINEL, dtype=torch.uint8, device=self.device)
+        for c in self.carves:
+            if c["role"] != "in" and c["end"] > c["off"] and bool((self.mem[c["off"]:c["end"]].view(-1, 2) != pat).any()):
+                return c["name"]
+        return None
+
     # -------------------------------------------------------------------------------------------- layout
     @staticmethod
     def _next(end, prev_guard, pitch):

@@ -78,6 +78,30 @@ def test_in_range_writes_pass():
     assert torch.isnan(raw).all()
 
 
+def test_written_names_a_touched_output_and_reset_starts_over():
+    """what the refusal checks of test_gpu_dispatch_contract.py stand on: an untouched output reads as untouched, one written element of an
+    output / workspace is named, inputs and sealed outputs of earlier launches do not count, reset() gives the arena back as constructed"""
+    a = _arena(16 * MIB)
+    a.place(torch.randn(4, 8))
+    pre = a.carve((4, 8), torch.float32)                          # written by an earlier launch, then an operand
+    pre.fill_(1.0)
+    a.seal()
+    assert [c["role"] for c in a.carves] == ["in", "in"]
+    y = a.carve((9, 24), torch.bfloat16, ld=32)
+    ws = a.carve((2, 4096), torch.uint8, role="scratch")
+    assert a.written() is None
+    y[8, 23] = 0.5
+    assert a.written() == a.carves[2]["name"]
+    a.reset()
+    assert a.carves == [] and (a.mem.view(torch.int16) == guarded.SENTINEL_I16).all()
+    a.place(torch.randn(4, 8))
+    a.carve((9, 24), torch.bfloat16, ld=32)
+    ws = a.carve((2, 4096), torch.uint8, role="scratch")
+    assert a.carves[0]["off"] >= MIB and a.written() is None      # the layout starts from the front again
+    ws[1, 4095] = 0
+    assert a.written() == a.carves[2]["name"] and not a.damage()
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32, torch.int32])
 @pytest.mark.parametrize("side", ["before", "after", "row gap"])
 def test_one_stray_element_is_found_and_named(dtype, side):
