@@ -5,6 +5,7 @@ whole path (PIL in -> CLIP-shaped embeddings -> HarmonyAttention + ImageProjMode
 
     python examples/pns_edit.py --out out.png [--unet unet.safetensors] [--vae vae.safetensors] [--ip-ckpt ip_adapter.bin]
                                 [--seeds 0 1 2 3] [--steps 30] [--preview-steps 10] [--size 1024]
+                                [--scheduler euler-a --step-noise seed]
 
 Launch under torch.distributed.run with N ranks to shard the seeds over N GPUs (one process per GPU, RCCL).
 """
@@ -29,7 +30,7 @@ SCHEDULERS = {
     "euler": hs.EulerDiscreteScheduler,
     "dpmpp2m": hs.DPMSolverMultistepScheduler,
     "dpmpp2m-karras": lambda: hs.DPMSolverMultistepScheduler(use_karras_sigmas=True),
-    "euler-a": hs.EulerAncestralDiscreteScheduler,           # stochastic: each denoise draws its per-step noise (torch's global generator)
+    "euler-a": hs.EulerAncestralDiscreteScheduler,           # stochastic: reads noise at every step (--step-noise says from where)
 }
 
 
@@ -37,6 +38,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheduler", choices=sorted(SCHEDULERS), default="ddim",
                     help="sampler of the preview and the final denoise (dpmpp2m-karras at 20-25 steps is the usual SDXL choice)")
+    ap.add_argument("--step-noise", choices=("global", "seed"), default="global",
+                    help="per-step noise of a stochastic scheduler (euler-a): global = drawn from torch's global generator per denoise (a seed "
+                         "fixes the initial noise only); seed = generated on the device from each candidate's seed, so the same command "
+                         "prints the same winner and writes the same image twice.  Deterministic schedulers draw none")
     ap.add_argument("--out", default="out.png")
     ap.add_argument("--unet"); ap.add_argument("--vae"); ap.add_argument("--ip-ckpt")
     ap.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
@@ -57,6 +62,7 @@ def main():
         torch.distributed.init_process_group("nccl")
     dev, dtype = torch.device(f"cuda:{local}"), torch.bfloat16
     torch.cuda.set_device(dev)
+    torch.manual_seed(0)                                                  # the stand-in weights below: the same on every rank and in every run
 
     if a.unet:
         unet = UNet2DConditionModel.from_safetensors(a.unet, UNetConfig()).to(dev, dtype)
@@ -105,13 +111,9 @@ def main():
     eng = pipe.engine
     eng.set_conditioning(pe, ne, prompt[2].to(dev, dtype), prompt[3].to(dev, dtype), a.size, a.size, guidance_scale=a.guidance)
 
-    def denoise(steps):
-        def f(noise):
-            eng.set_schedule(pipe.scheduler, steps)
-            return eng.denoise(noise).clone()
-        return f
-
-    r = pns.run_pns(denoise(a.preview_steps), a.seeds, (1, 4, a.size // 8, a.size // 8), device=dev, final_fn=denoise(a.steps))
+    by_seed = a.step_noise == "seed" and getattr(pipe.scheduler, "stochastic", False)
+    preview, final = pns.two_stage_fns(eng, pipe.scheduler, a.preview_steps, a.steps, step_noise="seed" if by_seed else "global")
+    r = pns.run_pns(preview, a.seeds, (1, 4, a.size // 8, a.size // 8), device=dev, final_fn=final, pass_seeds=by_seed)
     if int(os.environ.get("RANK", "0")) == 0:
         img = postprocess(decode_latents(vae, r["latents"]), "pil")[0]
         img.save(a.out)

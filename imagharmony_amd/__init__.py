@@ -18,6 +18,8 @@ _CLIP_TEXT = ("CLIPTextEncoder", "CLIPTextEncoderConfig")
 _PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline")
 # the schedulers of the device-resident loop (schedulers.py): the two linear ones and the multistep / ancestral ones
 _SCHEDULERS = ("DDIMScheduler", "EulerDiscreteScheduler", "DPMSolverMultistepScheduler", "EulerAncestralDiscreteScheduler")
+# the seeded step noise restated in numpy (noise.py): seeded_randn / seed_rows, the yardstick of the device generator
+_NOISE = ("seeded_randn", "seed_rows")
 
 
 def __getattr__(name):
@@ -36,4 +38,7 @@ def __getattr__(name):
     if name in _SCHEDULERS:
         from . import schedulers
         return getattr(schedulers, name)
+    if name in _NOISE:
+        from . import noise
+        return getattr(noise, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -218,6 +218,37 @@ static int do_ew(int op, const imh_ew_args* a, hipStream_t s) {
     return ew_launch(op, p, a->dtype, s);
 }
 
+// imh_step_seeded: IMH_EW_CFG_MSTEP's launch with the noise generated from the seed rows (elementwise.hip cfg_mstep_kernel<.., SEEDED>)
+static int do_step_seeded(const imh_seeded_args* a, hipStream_t s) {
+    if (!a || !a->ew.y) { set_error("imh_step_seeded: null pointer argument"); return IMH_ERR_ARG; }
+    if (!a->seeds) { set_error("imh_step_seeded: null seeds (one uint32 row (k0, k1, lane, 0) per sample)"); return IMH_ERR_ARG; }
+    if (a->ew.bias) { set_error("imh_step_seeded: bias (the noise bank of IMH_EW_CFG_MSTEP) must be NULL: the noise comes from seeds"); return IMH_ERR_ARG; }
+    if ((uintptr_t)a->seeds & 3) { set_error("imh_step_seeded: seeds must be 4-byte aligned"); return IMH_ERR_ARG; }
+    const imh_ew_args* e = &a->ew;
+    EwParams p;
+    p.a = e->a; p.b = e->b; p.y = e->y; p.w = e->w; p.bias = nullptr; p.tab = e->tab; p.step = e->step; p.n = e->n;
+    p.i0 = e->i0; p.i1 = e->i1; p.i2 = e->i2; p.i3 = e->i3; p.i4 = e->i4; p.i5 = e->i5;
+    p.f0 = e->f0; p.f1 = e->f1; p.f2 = e->f2; p.f3 = e->f3;
+    p.x2 = e->x2; p.noise = e->noise; p.mask = e->mask; p.blend_tab = e->blend_tab;
+    p.seeds = a->seeds; p.noise_stream = a->stream;
+    return ew_launch(IMH_EW_CFG_MSTEP, p, e->dtype, s);
+}
+
+static int to_randn(const imh_randn_args* a, const char* who, RandnParams* p) {
+    if (!a || !a->y) { set_error("%s: null pointer argument", who); return IMH_ERR_ARG; }
+    if (!a->seeds) { set_error("%s: null seeds (one uint32 row (k0, k1, lane, 0) per sample)", who); return IMH_ERR_ARG; }
+    if (a->S <= 0 || a->HW <= 0 || (long long)a->S * a->HW > 0x7fffffffLL / 4) { set_error("%s: S=%d HW=%d (both > 0, S * 4 * HW < 2^31)", who, a->S, a->HW); return IMH_ERR_SHAPE; }
+    if (((uintptr_t)a->seeds | (uintptr_t)a->y | (uintptr_t)a->step) & 3) { set_error("%s: y, seeds and step must be 4-byte aligned", who); return IMH_ERR_ARG; }
+    p->y = a->y; p->seeds = a->seeds; p->step = a->step; p->S = a->S; p->HW = a->HW; p->row = a->row; p->noise_stream = a->stream; p->raw = a->raw; p->quad0 = a->quad0;
+    return IMH_OK;
+}
+
+static int do_randn_seeded(const imh_randn_args* a, hipStream_t s) {
+    RandnParams p;
+    const int rc = to_randn(a, "imh_randn_seeded", &p);
+    return rc != IMH_OK ? rc : randn_seeded_launch(p, s);
+}
+
 }  // namespace imh
 
 using namespace imh;
@@ -235,6 +266,8 @@ struct imh_op {
         imh_gemm_args gemm2[2];
         imh_xattn_args xattn;
         imh_enc_attn_args eattn;
+        imh_seeded_args seeded;
+        imh_randn_args randn;
     } u;
 };
 
@@ -259,6 +292,8 @@ static int run_op(const imh_op& o, hipStream_t s) {
         case IMH_OP_XATTN: return do_xattn(&o.u.xattn, s);
         case IMH_OP_ATTN_ENC: return do_attn_enc(&o.u.eattn, s);
         case IMH_OP_ATTN_ENC_CAUSAL: return do_attn_enc(&o.u.eattn, s, 1);
+        case IMH_OP_STEP_SEEDED: return do_step_seeded(&o.u.seeded, s);
+        case IMH_OP_RANDN_SEEDED: return do_randn_seeded(&o.u.randn, s);
     }
     set_error("plan: unknown op kind %d", o.kind);
     return IMH_ERR_ARG;
@@ -281,6 +316,8 @@ static size_t args_size(int kind) {
         case IMH_OP_XATTN: return sizeof(imh_xattn_args);
         case IMH_OP_ATTN_ENC:
         case IMH_OP_ATTN_ENC_CAUSAL: return sizeof(imh_enc_attn_args);
+        case IMH_OP_STEP_SEEDED: return sizeof(imh_seeded_args);
+        case IMH_OP_RANDN_SEEDED: return sizeof(imh_randn_args);
     }
     return 0;
 }
@@ -370,6 +407,14 @@ int imh_layernorm(const imh_norm_args* a, void* stream) {
 }
 
 int imh_elementwise(int op, const imh_ew_args* a, void* stream) { return do_ew(op, a, (hipStream_t)stream); }
+
+int imh_step_seeded(const imh_seeded_args* a, void* stream) { return do_step_seeded(a, (hipStream_t)stream); }
+int imh_randn_seeded(const imh_randn_args* a, void* stream) { return do_randn_seeded(a, (hipStream_t)stream); }
+int imh_randn_seeded_host(const imh_randn_args* a) {
+    RandnParams p;
+    const int rc = to_randn(a, "imh_randn_seeded_host", &p);
+    return rc != IMH_OK ? rc : randn_seeded_host(p);
+}
 
 int imh_f32(int op, const imh_f32_args* a, void* stream) {
     if (!a) { set_error("imh_f32: null args"); return IMH_ERR_ARG; }

@@ -11,7 +11,9 @@
 //                 masked blend of SDXL inpainting on a 4-channel UNet
 //   EW_CFG_MSTEP  the same launch for the multistep and ancestral samplers (DPM-Solver++ 2M, its SDE variant, Euler ancestral):
 //                 x' = cx*x + ce*eps + ch*h + cn*z and h' = hx*x + he*eps from one six-column table row, h a history slot,
-//                 z the step's row of a host-filled noise bank
+//                 z the step's row of a host-filled noise bank -- or, in the seeded form (imh_step_seeded), generated in the launch by
+//                 Philox4x32-10 from the sample's seed row, the table row and the element index (imh_philox.h): no bank, no host draw
+//   randn_seeded  the generator's rows by themselves (imh_randn_seeded): normals or raw words, for tests and oracle comparisons
 //   EW_CFG_RESCALE per-sample factor of rescale_noise_cfg (custom_pipelines.py:351-354; arXiv 2305.08891 3.4):
 //                 phi * std(eps_text) / std(eps_cfg) + (1 - phi), consumed by EW_CFG_STEP through `w`
 //   EW_SOFTMAX    row softmax of fp32 scores -> T probabilities (the VAE mid-block attention: one head of width
@@ -28,6 +30,7 @@
 
 #include "imh_common.h"
 #include "imh_kernels.h"
+#include "imh_philox.h"
 
 namespace imh {
 
@@ -214,7 +217,13 @@ __global__ void cfg_step_kernel(const EwParams p) {
 // h = p.b, fp32 [S, 4, HW], one history slot (the previous step's data prediction), read then overwritten by the same thread; z = row
 // *step of the noise bank p.bias, fp32 [n, S, 4, HW].  Either may be NULL: the term is absent and h is not written.  All fp32; the
 // first two terms are written as cfg_step_kernel writes them, so that with ch = cn = 0 and no h / bank the result has the same bits.
-template <typename T, bool BLEND>
+// SEEDED (imh.h imh_step_seeded): z is not read from a bank but generated here, a pure function of (seed row of the sample, table row,
+// element): one Philox4x32-10 call (imh_philox.h) gives the normals of four consecutive elements of a sample, so the loop runs over quads
+// of elements, e = 4 q .. 4 q + 3 of sample s (4 HW is a multiple of 4: a quad never leaves its sample; it may straddle a channel boundary
+// when HW % 4 != 0).  The update is the expression of the bank form, term for term, so that fed the same z the bits are the same; a row
+// with cn == 0 (every row of a deterministic sampler, the last row of Euler ancestral) generates nothing.  The SEEDED = false
+// instantiations are the kernels as they were.
+template <typename T, bool BLEND, bool SEEDED = false>
 __global__ void cfg_mstep_kernel(const EwParams p) {
     const int S = p.i0, HW = p.i1;
     const long long total = (long long)S * HW * 4;
@@ -227,6 +236,44 @@ __global__ void cfg_mstep_kernel(const EwParams p) {
     const float* z = p.bias ? (const float*)p.bias + (size_t)row * (size_t)total : nullptr;
     float ba = 0.f, bb = 0.f;
     if constexpr (BLEND) { ba = p.blend_tab[row * 2]; bb = p.blend_tab[row * 2 + 1]; }
+    if constexpr (SEEDED) {
+        const bool gen = cn != 0.f;
+        const long long quads = (long long)S * HW;
+        for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
+            const int s = (int)(q / HW);
+            PhiloxNormals zn = {{0.f, 0.f, 0.f, 0.f}};
+            if (gen) zn = seeded_normals(p.seeds + (size_t)s * 4, (uint32_t)(q - (long long)s * HW), (uint32_t)row, p.noise_stream);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const long long i = q * 4 + k;
+                const int pix = (int)(i % HW);
+                const int chn = (int)((i / HW) % 4);
+                float eps;
+                if (p.i3) {
+                    const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
+                    const float cnd = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + chn]);
+                    eps = u + p.f2 * (cnd - u);
+                } else {
+                    eps = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
+                }
+                if (p.w) eps *= ((const float*)p.w)[s];
+                const float x = lat[i];
+                float y = cx * x + ce * eps;
+                if (hist) {
+                    y += ch * hist[i];
+                    hist[i] = hx * x + he * eps;
+                }
+                if (gen) y += cn * zn.z[k];
+                if constexpr (BLEND) {
+                    const float m = p.mask[(size_t)(s % p.i4) * HW + pix];
+                    const float pv = ba * p.x2[i] + bb * p.noise[i];
+                    y = (1.0f - m) * pv + m * y;
+                }
+                lat[i] = y;
+            }
+        }
+        return;
+    }
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int pix = (int)(i % HW);
         const int chn = (int)((i / HW) % 4);
@@ -253,6 +300,29 @@ __global__ void cfg_mstep_kernel(const EwParams p) {
             y = (1.0f - m) * pv + m * y;
         }
         lat[i] = y;
+    }
+}
+
+// imh_randn_seeded: the generator's rows by themselves, y[s, e] = z_{e & 3}(seed row s, quad e >> 2, row, stream) (raw: the uint32 words
+// instead), fp32 [S, 4, HW]; one quad per thread and step.  For tests and for callers that want the rows (an oracle comparison).
+__global__ void randn_seeded_kernel(const RandnParams p) {
+    const int HW = p.HW;
+    const uint32_t row = p.step ? (uint32_t)*p.step : p.row;
+    const long long quads = (long long)p.S * HW;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
+        const int s = (int)(q / HW);
+        const uint32_t qs = p.quad0 + (uint32_t)(q - (long long)s * HW);
+        if (p.raw) {
+            const PhiloxWords w = seeded_words(p.seeds + (size_t)s * 4, qs, row, p.noise_stream);
+            uint32_t* y = (uint32_t*)p.y + q * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) y[k] = w.w[k];
+        } else {
+            const PhiloxNormals n = seeded_normals(p.seeds + (size_t)s * 4, qs, row, p.noise_stream);
+            float* y = (float*)p.y + q * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) y[k] = n.z[k];
+        }
     }
 }
 
@@ -464,10 +534,12 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
                     set_error("cfg_mstep: the masked blend needs x2 (image latents), noise, blend_tab and i4 = mask batch >= 1");
                     return IMH_ERR_ARG;
                 }
-                hipLaunchKernelGGL((cfg_mstep_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+                if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, true, true>), dim3(grid_for((long long)p.i0 * p.i1, 256)), dim3(256), 0, stream, p);
+                else hipLaunchKernelGGL((cfg_mstep_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
                 break;
             }
-            hipLaunchKernelGGL((cfg_mstep_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+            if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, false, true>), dim3(grid_for((long long)p.i0 * p.i1, 256)), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((cfg_mstep_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
             break;
         case EW_CFG_RESCALE:
             if (p.i0 <= 0 || p.i1 <= 0) { set_error("cfg_rescale: empty problem"); return IMH_ERR_SHAPE; }
@@ -511,6 +583,27 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
             return IMH_ERR_ARG;
     }
     return check_launch("elementwise");
+}
+
+int randn_seeded_launch(const RandnParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL(randn_seeded_kernel, dim3(grid_for((long long)p.S * p.HW, 256)), dim3(256), 0, stream, p);
+    return check_launch("randn_seeded");
+}
+
+int randn_seeded_host(const RandnParams& p) {
+    const uint32_t row = p.step ? (uint32_t)*p.step : p.row;
+    for (int s = 0; s < p.S; ++s)
+        for (int q = 0; q < p.HW; ++q) {
+            const size_t o = ((size_t)s * p.HW + q) * 4;
+            if (p.raw) {
+                const PhiloxWords w = seeded_words(p.seeds + (size_t)s * 4, p.quad0 + (uint32_t)q, row, p.noise_stream);
+                for (int k = 0; k < 4; ++k) ((uint32_t*)p.y)[o + k] = w.w[k];
+            } else {
+                const PhiloxNormals n = seeded_normals(p.seeds + (size_t)s * 4, p.quad0 + (uint32_t)q, row, p.noise_stream);
+                for (int k = 0; k < 4; ++k) ((float*)p.y)[o + k] = n.z[k];
+            }
+        }
+    return IMH_OK;
 }
 
 int ew_launch(int op, const EwParams& p, int dtype, hipStream_t stream) {

@@ -193,7 +193,22 @@ struct EwParams {
     const float* noise;      // cfg_step blend: add-noise noise
     const float* mask;       // cfg_step blend: latent mask (selects the blend)
     const float* blend_tab;  // cfg_step blend: (a, b) rows indexed by *step
+    const unsigned* seeds = nullptr;   // seeded step (imh_step_seeded): [i0][4] = (k0, k1, lane, 0) per sample; null: cfg_mstep as it was
+    unsigned noise_stream = 0;         // ... and the generator's stream word
 };
 int ew_launch(int op, const EwParams& p, int dtype, hipStream_t stream);
+
+// the stand-alone fill of the seeded generator (imh_philox.h; imh_randn_seeded): y fp32 (raw: uint32 words) [S, 4, HW]
+struct RandnParams {
+    void* y;
+    const unsigned* seeds;   // [S][4]
+    const int* step;         // row = *step when set, else `row`
+    int S, HW;
+    unsigned row, noise_stream;
+    int raw;
+    unsigned quad0;          // counter word 0 of y's first quad
+};
+int randn_seeded_launch(const RandnParams& p, hipStream_t stream);
+int randn_seeded_host(const RandnParams& p);       // the same functions on the host, into caller memory (seeds / step / y host pointers)
 
 }  // namespace imh

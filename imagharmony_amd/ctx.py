@@ -219,6 +219,10 @@ class Ctx:
             rc = self.lib.imh_attention_enc(C.byref(args), s)
         elif kind == L.OP_ATTN_ENC_CAUSAL:
             rc = self.lib.imh_attention_enc_causal(C.byref(args), s)
+        elif kind == L.OP_STEP_SEEDED:
+            rc = self.lib.imh_step_seeded(C.byref(args), s)
+        elif kind == L.OP_RANDN_SEEDED:
+            rc = self.lib.imh_randn_seeded(C.byref(args), s)
         else:
             rc = self.lib.imh_elementwise(ew_op, C.byref(args), s)
         L.check(rc, descr or f"op kind {kind}")
@@ -944,10 +948,19 @@ class Ctx:
 
     # ------------------------------------------------------------------ elementwise
     def ew(self, op, y, a=None, b=None, w=None, bias=None, tab=None, step=None, n=0, i=(0, 0, 0, 0, 0, 0),
-           f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0, x2=None, noise=None, mask=None, blend_tab=None, hist=None, bank=None):
+           f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0, x2=None, noise=None, mask=None, blend_tab=None, hist=None, bank=None,
+           seeds=None, noise_stream=0):
         """x2 / noise / mask / blend_tab (fp32, imh.h ABI 11): conv_in's second source, the masked blend behind the CFG step.
         hist / bank (fp32, IMH_EW_CFG_MSTEP only): the history slot the step reads and rewrites in place and the per-step noise bank;
-        they travel in the fields `b` and `bias` (imh_ew_args does not grow), so they exclude b= / bias="""
+        they travel in the fields `b` and `bias` (imh_ew_args does not grow), so they exclude b= / bias=
+        seeds (IMH_EW_CFG_MSTEP only; noise.seed_rows on the device, int32 view of uint32 [S, 4]): the seeded step, imh_step_seeded --
+        the step's noise is generated in the launch from the samples' seed rows instead of read from a bank (bank= is then refused)"""
+        if seeds is not None:
+            if op != L.EW_CFG_MSTEP or bank is not None or bias is not None:
+                raise L.ImhError(f"{descr}: seeds belong to EW_CFG_MSTEP and take the place of the noise bank")
+            self._chk(seeds, f"{descr}.seeds", torch.int32)
+            if tuple(seeds.shape) != (int(i[0]), 4) or not seeds.is_contiguous():
+                raise L.ImhError(f"{descr}: seeds {tuple(seeds.shape)} must be a dense [{int(i[0])}, 4] table (noise.seed_rows)")
         if hist is not None or bank is not None:
             if op != L.EW_CFG_MSTEP or b is not None or bias is not None:
                 raise L.ImhError(f"{descr}: hist / bank belong to EW_CFG_MSTEP and take the place of b / bias")
@@ -970,8 +983,34 @@ class Ctx:
         e.i0, e.i1, e.i2, e.i3, e.i4, e.i5 = i
         e.f0, e.f1, e.f2, e.f3 = f
         e.dtype = self.dt
+        if seeds is not None:
+            sa = L.SeededArgs()
+            sa.ew, sa.seeds, sa.stream = e, seeds.data_ptr(), int(noise_stream)
+            self._emit(L.OP_STEP_SEEDED, sa, descr=descr, nbytes=nbytes, keep=(a, b, y, w, tab, step, x2, noise, mask, blend_tab, seeds))
+            return y
         self._emit(L.OP_EW, e, ew_op=op, descr=descr, nbytes=nbytes, keep=(a, b, y, w, bias, tab, step, x2, noise, mask, blend_tab))
         return y
+
+    def randn_seeded(self, seeds, HW, row=0, step=None, noise_stream=0, raw=False, out=None, descr="randn_seeded"):
+        """the seeded generator's rows by themselves (imh_randn_seeded; imagharmony_amd/noise.py states what they are): fp32 [S, 4, HW]
+        normals of (seeds[s], row, noise_stream), or with raw the int32-viewed uint32 words.  seeds: noise.seed_rows on the device
+        (int32 [S, 4]); the row is the immediate ``row`` or, with ``step`` (device int32), *step."""
+        self._chk(seeds, descr + ".seeds", torch.int32); self._chk(step, descr + ".step", torch.int32)
+        if seeds.dim() != 2 or seeds.shape[1] != 4 or not seeds.is_contiguous():
+            raise L.ImhError(f"{descr}: seeds {tuple(seeds.shape)} must be a dense [S, 4] table (noise.seed_rows)")
+        S, HW = int(seeds.shape[0]), int(HW)
+        dt = torch.int32 if raw else torch.float32
+        if out is None:
+            out = self.new(S, 4, HW, dtype=dt)
+        self._chk(out, descr + ".out", dt)
+        if tuple(out.shape) != (S, 4, HW) or not out.is_contiguous():
+            raise L.ImhError(f"{descr}: out {tuple(out.shape)} must be dense [{S}, 4, {HW}]")
+        if not 0 <= int(row) < 2 ** 32:
+            raise L.ImhError(f"{descr}: row {row} outside [0, 2**32)")
+        a = L.RandnArgs()
+        a.y, a.seeds, a.step, a.S, a.HW, a.row, a.stream, a.raw = out.data_ptr(), seeds.data_ptr(), self._p(step), S, HW, int(row), int(noise_stream), int(bool(raw))
+        self._emit(L.OP_RANDN_SEEDED, a, descr=descr, nbytes=16.0 * S * HW, keep=(seeds, step, out))
+        return out
 
     def gather_rows(self, table, idx, add=None, out=None, descr="gather_rows"):
         """out[r] = table[idx[r]] (+ add[r % P]) (IMH_EW_GATHER_ROWS): table [rows, C] and add [P, C] row-major in the compute dtype, idx

@@ -46,6 +46,7 @@ class DenoiseEngine:
         self.inpaint = None      # None | "blend" (4-channel UNet: masked blend in the step) | "concat" (9-channel UNet: conv_in reads the mask)
         self.general = False     # the schedule steps through the six-column table (EW_CFG_MSTEP): multistep / ancestral samplers (set_schedule)
         self.stochastic = False  # ... and reads a noise row per step
+        self.seeded = False      # ... which the step generates from st.seed_rows instead of reading a bank (set_schedule(seeded_noise=True))
 
     # -- conditioning (once per image / per PNS run; shared by every candidate seed) --
     @torch.no_grad()
@@ -95,12 +96,13 @@ class DenoiseEngine:
 
     # inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
     _INPAINT_BUFFERS = ("inp_z", "inp_noise", "inp_mask", "conv_in_extra")
-    # what a plan that ends with the general step (EW_CFG_MSTEP) points at besides: the six-column table, the history slot and the noise bank
-    _GENERAL_STEP = ("coef6_tab", "hist", "noise_bank")
+    # what a plan that ends with the general step (EW_CFG_MSTEP) points at besides: the six-column table, the history slot and the noise
+    # bank -- or, under a seeded schedule, the samples' seed rows
+    _GENERAL_STEP = ("coef6_tab", "hist", "noise_bank", "seed_rows")
 
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
-                     denoising_end=None, t_start=0, inpaint=False):
+                     denoising_end=None, t_start=0, inpaint=False, seeded_noise=False):
         """inpaint: the schedule of an inpainting call (prepare_inpaint).  On a 4-channel UNet every step then ends with upstream's masked
         blend, latents = (1 - m) * add_noise(z, n, timesteps[i + 1]) + m * latents, whose add_noise pair comes from blend_tab: row r holds
         scheduler.add_noise_coefficients(r + 1), the last row that runs (1, 0) -- the image latents themselves.  On a 9-channel UNet there is
@@ -115,7 +117,12 @@ class DenoiseEngine:
         exactly where the rows differ.  Allocated here for such a schedule: st.hist, fp32 [S, 4, H, W] (the previous data prediction, when
         the scheduler needs one), and st.noise_bank, fp32 [num_inference_steps, S, 4, H, W], for a stochastic scheduler: row r is the
         noise of step r, filled by denoise() before the loop.  At 1024^2 the bank is 4 * 128 * 128 * 4 B = 256 KiB per step and sample,
-        about 8 MB per sample for 30 steps."""
+        about 8 MB per sample for 30 steps.
+        seeded_noise=True (a stochastic scheduler; ignored by a deterministic one, whose plan is what it was): no bank.  The plan ends
+        with the seeded step (imh.h imh_step_seeded, same launch count), which generates row *step's noise from st.seed_rows, int32 bits of
+        uint32 [S, 4] = (seed low, seed high, lane, 0) per sample (noise.seed_rows) -- 16 bytes per sample that denoise(step_seeds=...)
+        fills before the loop.  The noise is then a pure function of (seed, lane, table row, element): the same on any rank, alone or
+        stacked, eager or graph.  The flag is part of the plan key; the bank plan and the seeded plan of one schedule coexist."""
         st, dev = self.st, self.device
         t_start = int(t_start)
         if not 0 <= t_start < int(num_inference_steps):
@@ -148,11 +155,14 @@ class DenoiseEngine:
         mode = None
         if inpaint:
             mode = "concat" if self.unet.config.in_channels == 9 else "blend"
-        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), mode)
+        stochastic = general and bool(getattr(scheduler, "stochastic", False))
+        seeded = bool(seeded_noise) and stochastic
+        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), mode, seeded)
         self.t_start = t_start
         self.inpaint = mode
         self.general = general
-        self.stochastic = general and bool(getattr(scheduler, "stochastic", False))
+        self.stochastic = stochastic
+        self.seeded = seeded
         hit = self._plans.get(key)
         if hit is not None:
             # a schedule this engine has run under this conditioning: its tables, time-embedding rows and recorded plan are still there
@@ -166,14 +176,16 @@ class DenoiseEngine:
             return
         st.t_table = tab["timesteps"].to(dev)
         st.coef_tab = tab["coef"].contiguous().to(dev) if tab.get("coef") is not None else None
-        st.coef6_tab = st.hist = st.noise_bank = None
+        st.coef6_tab = st.hist = st.noise_bank = st.seed_rows = None
         if general:
             if tuple(tab["coef6"].shape) != (int(num_inference_steps), 6):
                 raise L.ImhError(f"the scheduler's coef6 table is {tuple(tab['coef6'].shape)}, expected ({int(num_inference_steps)}, 6)")
             st.coef6_tab = tab["coef6"].to(torch.float32).contiguous().to(dev)
             if getattr(scheduler, "needs_history", False):
                 st.hist = torch.zeros(self.S, 4, self.H, self.W, dtype=torch.float32, device=dev)
-            if self.stochastic:
+            if self.seeded:
+                st.seed_rows = torch.zeros(self.S, 4, dtype=torch.int32, device=dev)
+            elif self.stochastic:
                 st.noise_bank = torch.zeros(int(num_inference_steps), self.S, 4, self.H, self.W, dtype=torch.float32, device=dev)
         st.in_scale_tab = tab["in_scale"].to(dev) if tab["in_scale"] is not None else None
         st.ip_scale_tab = torch.tensor(gate, dtype=torch.float32, device=dev)
@@ -203,14 +215,14 @@ class DenoiseEngine:
         for k in ("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
                   "xcd_candidates", "xcd_cells", "t_start", "inpaint"):
             setattr(e, k, getattr(self, k))
-        e.general, e.stochastic = self.general, self.stochastic
+        e.general, e.stochastic, e.seeded = self.general, self.stochastic, self.seeded
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
         st.t_table, st.coef_tab, st.in_scale_tab, st.ip_scale_tab = src.t_table, src.coef_tab, src.in_scale_tab, src.ip_scale_tab
         st.blend_tab = getattr(src, "blend_tab", None)               # (the mask, image latents and noise are the fork's own: _record)
         st.coef6_tab = getattr(src, "coef6_tab", None)
-        for k in ("hist", "noise_bank"):                             # the general step's state is the fork's own, like its latents
+        for k in ("hist", "noise_bank", "seed_rows"):                # the general step's state is the fork's own, like its latents
             v = getattr(src, k, None)
             setattr(st, k, None if v is None else torch.zeros_like(v))
         st.step = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -258,7 +270,8 @@ class DenoiseEngine:
                         f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
             if self.general:
                 tail.ew(L.EW_CFG_MSTEP, st.latents, a=self.np_full, w=fac, tab=st.coef6_tab, step=st.step, hist=st.hist, bank=st.noise_bank,
-                        i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+mstep")
+                        seeds=st.seed_rows if self.seeded else None,
+                        i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+mstep+seeded" if self.seeded else "cfg+mstep")
             else:
                 tail.ew(L.EW_CFG_STEP, st.latents, a=self.np_full, w=fac, tab=st.coef_tab, step=st.step,
                         i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
@@ -278,9 +291,11 @@ class DenoiseEngine:
             # the multistep / ancestral samplers: the same launch with the six-column row, the history slot and the step's noise row
             # (imh.h IMH_EW_CFG_MSTEP); the blend rides in it as it rides in EW_CFG_STEP
             kw = dict(x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab) if self.inpaint == "blend" else {}
+            # a seeded schedule: no bank, the launch generates the row from the samples' seed rows (imh.h imh_step_seeded)
             rec.ew(L.EW_CFG_MSTEP, st.latents, a=out, w=fac, tab=st.coef6_tab, step=st.step, hist=st.hist, bank=st.noise_bank,
+                   seeds=st.seed_rows if self.seeded else None,
                    i=(self.S, self.H * self.W, 0, int(self.do_cfg), self.S if kw else 0, 0), f=(0.0, 0.0, self.guidance, 0.0),
-                   descr="cfg+mstep+blend" if kw else "cfg+mstep", **kw)
+                   descr=("cfg+mstep+seeded" if self.seeded else "cfg+mstep") + ("+blend" if kw else ""), **kw)
         elif self.inpaint == "blend":
             # ... and upstream's masked blend in the same launch (imh.h IMH_EW_CFG_STEP): no extra launch, no extra pass over the latents
             rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
@@ -342,13 +357,29 @@ class DenoiseEngine:
         from .pipeline import randn_latents
         return torch.stack([randn_latents(tuple(shape), generator) for _ in range(int(steps))], 0)
 
-    def _start_general_step(self, generator=None, step_noise=None):
+    def _start_general_step(self, generator=None, step_noise=None, step_seeds=None, step_lanes=None):
         """before the loop of a plan that ends with EW_CFG_MSTEP: the history slot is zeroed (the first row that runs is first order and
         has ch = 0, but 0 * NaN is NaN: stale contents must not be relied on to be finite), and a stochastic scheduler's noise goes into
-        rows t_start .. steps - 1 of the bank, so that the loop itself stays graph replays with no host work in between"""
+        rows t_start .. steps - 1 of the bank, so that the loop itself stays graph replays with no host work in between.  Under a seeded
+        schedule there is no bank: the samples' seed rows (16 bytes each) are copied instead, and generator / step_noise are refused."""
         st = self.st
+        if not self.seeded and (step_seeds is not None or step_lanes is not None):
+            raise L.ImhError("step_seeds= / step_lanes= need a seeded schedule: set_schedule(..., seeded_noise=True) with a stochastic scheduler")
+        if self.seeded:
+            if generator is not None or step_noise is not None:
+                raise L.ImhError("a seeded schedule takes its step noise from step_seeds=: generator= / step_noise= are refused")
+            if step_seeds is None:
+                raise L.ImhError("a seeded schedule needs step_seeds= (one 64-bit seed per sample)")
+            from .noise import seed_rows
+            step_seeds = list(step_seeds) if isinstance(step_seeds, (list, tuple)) else [step_seeds]
+            if len(step_seeds) != self.S:
+                raise L.ImhError(f"{len(step_seeds)} step_seeds for {self.S} samples")
+            rows = seed_rows(step_seeds, step_lanes)                     # ValueError: a seed outside [0, 2**64)
+            st.seed_rows.copy_(torch.from_numpy(rows.view("int32")))
         if st.hist is not None:
             st.hist.zero_()
+        if self.seeded:
+            return
         if not self.stochastic:
             if step_noise is not None:
                 raise L.ImhError("step_noise= is for stochastic schedulers; this schedule draws no noise")
@@ -362,18 +393,21 @@ class DenoiseEngine:
         st.noise_bank[self.t_start:self.steps].copy_(step_noise.to(self.device, torch.float32))
 
     @torch.no_grad()
-    def denoise_cfg_split(self, latents, exchange):
+    def denoise_cfg_split(self, latents, exchange, step_seeds=None, step_lanes=None):
         """One candidate's denoise shared by TWO ranks (engines with cfg_role 0 and 1 on the same conditioning and noise): per step
         each runs the UNet on its half of the CFG pair, `exchange(mine [S*HW*4...]) -> (uncond, cond)` swaps the halves (pns.
         pair_exchange: one all_gather of [S, HW, 4] values over xGMI), and both apply the identical combine + scheduler step, so
         the latents stay bit-equal on the two ranks without further traffic.  The two-stage PNS tail (assets/1.png: the judged-best
         noise x the full denoise) is then `steps` batch-S forwards deep instead of batch-2S ones.
         A multistep scheduler's tail plan ends with the same EW_CFG_MSTEP as the one-rank plan.  Stochastic schedulers (SDE-DPM-Solver++,
-        Euler ancestral) are refused here: the two ranks would have to fill identical noise banks."""
+        Euler ancestral) are refused here under a bank schedule: the two ranks would have to fill identical noise banks.  Under a seeded
+        schedule (set_schedule(..., seeded_noise=True)) with ``step_seeds`` they run: the tail plan ends with the seeded step on both
+        ranks, and each generates the identical noise from the seeds without talking."""
         if getattr(self, "cfg_role", None) is None or not self.do_cfg:
             raise L.ImhError("denoise_cfg_split needs an engine whose conditioning was set with cfg_role = 0 / 1 and guidance > 1")
-        if self.stochastic:
-            raise NotImplementedError("denoise_cfg_split does not run stochastic schedulers: both ranks would need identical noise banks")
+        if self.stochastic and not (self.seeded and step_seeds is not None):
+            raise NotImplementedError("denoise_cfg_split does not run stochastic schedulers: both ranks would need identical noise banks "
+                                      "(a seeded schedule with step_seeds= needs none)")
         if self.t_start or self.inpaint:
             raise NotImplementedError("denoise_cfg_split runs whole text-to-image schedules (t_start = 0, no inpainting)")
         if self.plan is None:
@@ -381,7 +415,9 @@ class DenoiseEngine:
         st = self.st
         st.latents.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)
         if self.general:
-            self._start_general_step()
+            self._start_general_step(step_seeds=step_seeds, step_lanes=step_lanes)
+        elif step_seeds is not None:
+            raise L.ImhError("step_seeds= need a seeded schedule: set_schedule(..., seeded_noise=True) with a stochastic scheduler")
         self.eager.ew(L.EW_STEP_SET, st.step, i=(0, 1, 0, 0, 0, 0), descr="step=0")
         for _ in range(self.steps):
             self.plan.replay()
@@ -443,7 +479,7 @@ class DenoiseEngine:
         return st.latents
 
     @torch.no_grad()
-    def denoise(self, latents, callback=None, callback_steps=1, generator=None, step_noise=None):
+    def denoise(self, latents, callback=None, callback_steps=1, generator=None, step_noise=None, step_seeds=None, step_lanes=None):
         """latents: [S, 4, H/8, W/8] unit-variance noise (CPU or device), or None: the latent buffer already holds the initial latents
         (prepare_img2img).  Runs the steps t_start .. steps - 1 of the schedule (t_start = 0 unless set_schedule was given one).  Returns
         final fp32 latents (output_type='latent' of custom_pipelines.py:365-379).  callback(i, t, latents) every ``callback_steps``
@@ -451,7 +487,10 @@ class DenoiseEngine:
         A stochastic scheduler (SDE-DPM-Solver++, Euler ancestral) reads one noise row per step: ``step_noise``, fp32 [steps that run,
         S, 4, H/8, W/8], or drawn here from ``generator`` (draw_step_noise: one randn_latents call per step, in step order, after the
         caller's initial-latents draws -- diffusers' order; None: torch's global generator, as diffusers).  It is copied into the
-        device noise bank BEFORE the loop (about 8 MB per sample for 30 steps at 1024^2), so the loop is still graph replays only."""
+        device noise bank BEFORE the loop (about 8 MB per sample for 30 steps at 1024^2), so the loop is still graph replays only.
+        Under a seeded schedule (set_schedule(..., seeded_noise=True)) ``step_seeds`` is required instead: one integer in [0, 2**64) per
+        sample, with ``step_lanes`` (default 0 each; the sample indices where one seed serves the batch).  16 bytes per sample are copied,
+        nothing is drawn; generator= / step_noise= are refused there, and step_seeds= anywhere else."""
         if getattr(self, "cfg_role", None) is not None and self.do_cfg:
             raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
         if self.inpaint and latents is not None:
@@ -465,9 +504,11 @@ class DenoiseEngine:
             st.latents.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)     # prepare_latents :255-265
         t0 = self.t_start
         if self.general:
-            self._start_general_step(generator, step_noise)
+            self._start_general_step(generator, step_noise, step_seeds, step_lanes)
         elif step_noise is not None:
             raise L.ImhError("step_noise= is for stochastic schedulers; this schedule draws no noise")
+        elif step_seeds is not None or step_lanes is not None:
+            raise L.ImhError("step_seeds= / step_lanes= need a seeded schedule: set_schedule(..., seeded_noise=True) with a stochastic scheduler")
         self.eager.ew(L.EW_STEP_SET, st.step, i=(t0, 1, 0, 0, 0, 0), descr="step=t_start")
         for i in range(t0, self.steps):                                     # :325 -- no host work per step
             self.plan.replay()

@@ -254,7 +254,7 @@ class IPAdapterXL(IPAdapter):
     def generate_pns(self, seeds, pil_image=None, prompt=None, negative_prompt=None, extra_text=None, scale=1.0,
                      preview_steps=10, num_inference_steps=30, guidance_scale=5.0, scorer=None, batch=None,
                      clip_image_embeds=None, prompt_embeds=None, extra_prompt_embeds=None, height=None, width=None,
-                     output_type="pil", **schedule_kw):
+                     output_type="pil", step_noise="global", **schedule_kw):
         """Preference-guided noise selection (README.md:27, assets/1.png) around ``generate``: every candidate seed gets
         a ``preview_steps`` denoise, a judge scores the previews, the best NOISE gets the full ``num_inference_steps``
         denoise.  Candidates are sharded over the ranks of an initialised torch.distributed group (one process per
@@ -263,8 +263,10 @@ class IPAdapterXL(IPAdapter):
         ``batch`` = preview candidates stacked per UNet forward on a rank; None (default) = as many as the rank holds, up
         to 4 (BASELINE.json configs[4] runs 4 per GPU): a stacked forward costs 1.27x less per candidate than one at a
         time on MI355X (bench.py ``stacked_candidates`` / ``pns_two_stage``); the final denoise is batch 1 either way.
-        Under a stochastic scheduler on the pipe (SDE-DPM-Solver++, Euler ancestral) the per-step noise of every preview and of the
-        final denoise comes from torch's global generator (pns.two_stage_fns has the details): a seed then fixes the initial noise only.
+        Under a stochastic scheduler on the pipe (SDE-DPM-Solver++, Euler ancestral) ``step_noise`` chooses the per-step noise of the
+        previews and the final denoise (pns.two_stage_fns has the details): "global" (default) takes it from torch's global generator, so a
+        seed fixes the initial noise only; "seed" generates it on the device from each candidate's own seed (lane 0), so a seed fixes
+        its whole trajectory, stacked or alone, on any rank.
         Returns dict(images, best_seed, scores, latents).  Text-to-image only: an image-to-image or inpainting pipeline raises NotImplementedError."""
         from . import pns
         from .pipeline import StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline
@@ -309,20 +311,22 @@ class IPAdapterXL(IPAdapter):
                                  guidance_scale=guidance_scale)
 
         state = {"n": None}
+        if step_noise not in ("global", "seed"):
+            raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
+        by_seed = step_noise == "seed"
+        stage_pre, stage_fin = pns.two_stage_fns(eng, pipe.scheduler, preview_steps, num_inference_steps, step_noise=step_noise, **schedule_kw)
 
-        def preview(noise):
+        def preview(noise, **kw):
             if state["n"] != noise.shape[0]:
                 cond(noise.shape[0]); state["n"] = noise.shape[0]
-            eng.set_schedule(pipe.scheduler, preview_steps, **schedule_kw)
-            return eng.denoise(noise).clone()
+            return stage_pre(noise, **kw)
 
-        def final(noise):
+        def final(noise, **kw):
             if state["n"] != noise.shape[0]:
                 cond(noise.shape[0]); state["n"] = noise.shape[0]
-            eng.set_schedule(pipe.scheduler, num_inference_steps, **schedule_kw)
-            return eng.denoise(noise).clone()
+            return stage_fin(noise, **kw)
 
-        r = pns.run_pns(preview, list(seeds), shape, scorer=scorer, device=self.device, final_fn=final, batch=S)
+        r = pns.run_pns(preview, list(seeds), shape, scorer=scorer, device=self.device, final_fn=final, batch=S, **({"pass_seeds": True} if by_seed else {}))
         out = r["latents"]
         if output_type != "latent":
             if pipe.vae is None and pipe.vae_decode is None:

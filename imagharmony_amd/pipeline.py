@@ -85,13 +85,18 @@ class StableDiffusionXLCustomPipeline:
                  negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, denoising_end: Optional[float] = None, **kwargs):
+                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator", **kwargs):
         """``output_type`` defaults to "pil" as the reference does (custom_pipelines.py:42), so ``test.py:43``'s
         ``images[0].save(...)`` works; that needs a VAE (``vae=`` / ``vae_decode=``) -- without one the call fails
         BEFORE denoising with a clear error (pass output_type="latent" for latents).  The default scheduler is
         DDIM (BASELINE.json's metric; IP-Adapter convention) -- stock SDXL ships EulerDiscrete: pass
-        ``scheduler=EulerDiscreteScheduler()`` for that."""
+        ``scheduler=EulerDiscreteScheduler()`` for that.
+        ``step_noise`` (stochastic schedulers: SDE-DPM-Solver++, Euler ancestral): "generator" (default) draws the per-step noise from
+        ``generator`` on the host, in diffusers' order; "seeded" generates it on the device from the generators' seeds (step_seed_table:
+        one generator -> its initial_seed() with lane = sample index, a list -> each generator's own seed with lane 0), so that a seed
+        reproduces its image whatever the batch -- it needs a generator (ValueError without one)."""
         self._refuse(output_type, eta, kwargs)
+        seed_tab = self.step_seed_table(step_noise, generator, None)
         height = height or self.default_sample_size * self.vae_scale_factor      # :189-190
         width = width or self.default_sample_size * self.vae_scale_factor
         if prompt_embeds is None:
@@ -104,13 +109,41 @@ class StableDiffusionXLCustomPipeline:
         eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
                              height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
                              crops_coords_top_left=crops_coords_top_left, target_size=target_size)
+        seed_tab = self.step_seed_table(step_noise, generator, S)
         eng.set_schedule(self.scheduler, num_inference_steps, control_guidance_start, control_guidance_end,
-                         denoising_end=denoising_end)
+                         denoising_end=denoising_end, **({"seeded_noise": True} if seed_tab else {}))
         if latents is None:
             latents = randn_latents((S, 4, height // 8, width // 8), generator)       # prepare_latents :255-265
-        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps, generator=generator).clone()
+        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+
+    @staticmethod
+    def step_seed_table(step_noise, generator, S):
+        """step_noise = "generator": None.  "seeded": (seeds, lanes) for DenoiseEngine.denoise(step_seeds=, step_lanes=) -- one generator:
+        its initial_seed() for every sample with lanes 0 .. S - 1; a list of S generators: each one's own initial_seed(), lane 0.
+        S = None only validates (before any GPU work).  ValueError: another value, or "seeded" without a generator."""
+        if step_noise not in ("generator", "seeded"):
+            raise ValueError(f'step_noise must be "generator" or "seeded", not {step_noise!r}')
+        if step_noise == "generator":
+            return None
+        if generator is None:
+            raise ValueError('step_noise="seeded" derives the step noise from the generator\'s seed: pass generator=')
+        if S is None:
+            return ()
+        if isinstance(generator, (list, tuple)):
+            if len(generator) != S:
+                raise ValueError(f"got {len(generator)} generators for a batch of {S}")
+            return [int(g.initial_seed()) for g in generator], [0] * S
+        return [int(generator.initial_seed())] * S, list(range(S))
+
+    @staticmethod
+    def _noise_kw(eng, seed_tab, generator):
+        """denoise()'s noise arguments: the seed table under a seeded schedule (a deterministic scheduler ignores the flag and draws
+        nothing), else the generator as before"""
+        if seed_tab and eng.seeded:
+            return dict(step_seeds=seed_tab[0], step_lanes=seed_tab[1])
+        return dict(generator=generator)
 
     def _refuse(self, output_type, eta, kwargs):
         if output_type != "latent" and self.vae is None and self.vae_decode is None:
@@ -155,13 +188,16 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
                  negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, **kwargs):
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
         """aesthetic_score / negative_aesthetic_score are accepted and unused: SDXL base has requires_aesthetics_score=False.
+        step_noise: as the text-to-image call ("seeded": the step noise of a stochastic scheduler from the generators' seeds; the rows
+        read are the schedule's rows t_start .. -- the device step counter, not the count of steps that ran).
         Refused: denoising_start (refiner hand-off), a 4-channel latent ``image``, ``latents=``, eta != 0 (NotImplementedError);
         strength outside [0, 1] or a schedule that truncates to no step (ValueError)."""
         if denoising_start is not None:
             raise NotImplementedError("denoising_start (the refiner hand-off) is not supported on this path")
         self._refuse(output_type, eta, kwargs)
+        self.step_seed_table(step_noise, generator, None)
         if latents is not None:
             raise NotImplementedError("latents= is not supported by the image-to-image path: the initial latents come from `image`")
         if image is None:
@@ -193,8 +229,9 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
         eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
                              height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
                              crops_coords_top_left=crops_coords_top_left, target_size=target_size)
+        seed_tab = self.step_seed_table(step_noise, generator, S)
         eng.set_schedule(sch, num_inference_steps, control_guidance_start, control_guidance_end, denoising_end=denoising_end,
-                         t_start=t_start)
+                         t_start=t_start, **({"seeded_noise": True} if seed_tab else {}))
         # prepare_latents: the posterior sample of every sample's image, then the add-noise noise, drawn in diffusers' order
         h, w = height // 8, width // 8
         vae = self.vae
@@ -209,7 +246,7 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
         n2 = randn_latents((S, 4, h, w), generator)
         a, b = sch.add_noise_coefficients(t_start)
         eng.prepare_img2img(moments, n1, n2, vae.config.scaling_factor, a, b)
-        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, generator=generator).clone()
+        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
 
@@ -245,9 +282,9 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
                  negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, **kwargs):
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
         """height / width default to the preprocessed image's size (anything else is refused: resize the image first).
-        aesthetic_score / negative_aesthetic_score are accepted and unused, as for image-to-image.
+        aesthetic_score / negative_aesthetic_score are accepted and unused, as for image-to-image; step_noise as there.
         Refused before any GPU work -- NotImplementedError: padding_mask_crop, masked_image_latents=, a 4-channel latent ``image``,
         latents=, denoising_start, eta != 0; ValueError: no image, no mask_image, a mask that cannot be brought to the image's size and
         batch, strength outside [0, 1] or a schedule that truncates to no step."""
@@ -258,6 +295,7 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
         if masked_image_latents is not None:
             raise NotImplementedError("masked_image_latents= is not supported: the masked image is encoded from `image` and `mask_image`")
         self._refuse(output_type, eta, kwargs)
+        self.step_seed_table(step_noise, generator, None)
         if latents is not None:
             raise NotImplementedError("latents= is not supported by the inpainting path: the initial latents come from `image`")
         if image is None:
@@ -298,8 +336,9 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
         eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
                              height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
                              crops_coords_top_left=crops_coords_top_left, target_size=target_size)
+        seed_tab = self.step_seed_table(step_noise, generator, S)
         eng.set_schedule(sch, num_inference_steps, control_guidance_start, control_guidance_end, denoising_end=denoising_end,
-                         t_start=t_start, inpaint=True)
+                         t_start=t_start, inpaint=True, **({"seeded_noise": True} if seed_tab else {}))
         h, w = height // 8, width // 8
         vae = self.vae
         per_sample = isinstance(generator, (list, tuple))
@@ -323,6 +362,6 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
         a, b = sch.add_noise_coefficients(t_start)
         eng.prepare_inpaint(moments, n1, n2, vae.config.scaling_factor, a, b, latent_mask(mask, h, w), strength_max=strength_max,
                             masked_moments=masked_moments, n3=n3)
-        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, generator=generator).clone()
+        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)

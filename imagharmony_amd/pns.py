@@ -133,22 +133,39 @@ class ClipPreferenceJudge:
         return (emb * self.target.to(emb.device)).sum(-1)
 
 
-def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, **schedule_kw):
+def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, step_noise="global", **schedule_kw):
     """The two-stage schedule of assets/1.png on a ``DenoiseEngine`` whose conditioning is set: every candidate seed
     gets a ``preview_steps`` denoise ("+10 steps"), the judged-best noise the full ``final_steps`` one ("+30 steps").
     Returns (preview_fn, final_fn) for ``run_pns``.
-    Under a stochastic scheduler (SDE-DPM-Solver++, Euler ancestral) these functions hand the engine no generator: each denoise draws
-    its per-step noise from torch's global generator, so a candidate seed fixes the initial noise only -- the preview and the final
-    run of the chosen seed use unrelated step noise, a seed does not reproduce its latent, and ranks differ.  Pass
-    ``engine.denoise(noise, generator=...)`` / ``step_noise=`` yourself where that matters; the deterministic samplers (DDIM, Euler,
-    DPM++ 2M with or without Karras sigmas) are unaffected."""
-    def preview(noise):
-        engine.set_schedule(scheduler, preview_steps, **schedule_kw)
+    Under a stochastic scheduler (SDE-DPM-Solver++, Euler ancestral) ``step_noise`` says where the per-step noise comes from:
+    "global" (the default, today's behaviour): the engine is handed no generator, each denoise draws its noise bank from torch's global
+    generator, so a candidate seed fixes the initial noise only -- the preview and the final run of the chosen seed use unrelated step
+    noise, a seed does not reproduce its latent, and ranks differ;
+    "seed": the schedules are seeded (DenoiseEngine.set_schedule(seeded_noise=True)) and every candidate's step noise is generated on
+    the device from its own seed with lane 0 -- a seed then reproduces its latent alone or stacked, on any rank, and its preview and
+    final run read the same noise rows 0 .. preview_steps - 1 (at different sigmas).  The functions then take ``seeds=`` (the
+    candidates' seeds in stacking order): use ``run_pns(..., pass_seeds=True)``.
+    The deterministic samplers (DDIM, Euler, DPM++ 2M with or without Karras sigmas) draw no noise and are unaffected either way."""
+    if step_noise not in ("global", "seed"):
+        raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
+    seeded = step_noise == "seed"
+
+    def run(steps, noise, seeds):
+        if not seeded:                                   # today's calls, unchanged
+            engine.set_schedule(scheduler, steps, **schedule_kw)
+            return engine.denoise(noise).clone()
+        engine.set_schedule(scheduler, steps, seeded_noise=True, **schedule_kw)
+        if engine.seeded:                                # (a deterministic sampler ignores the flag: it draws no noise)
+            if seeds is None:
+                raise ValueError('step_noise="seed" needs the candidates\' seeds: run_pns(..., pass_seeds=True)')
+            return engine.denoise(noise, step_seeds=list(seeds)).clone()
         return engine.denoise(noise).clone()
 
-    def final(noise):
-        engine.set_schedule(scheduler, final_steps, **schedule_kw)
-        return engine.denoise(noise).clone()
+    def preview(noise, seeds=None):
+        return run(preview_steps, noise, seeds)
+
+    def final(noise, seeds=None):
+        return run(final_steps, noise, seeds)
 
     return preview, final
 
@@ -185,7 +202,7 @@ def pair_exchange(group, role):
 def run_pns(denoise_fn: Callable[[torch.Tensor], torch.Tensor], seeds: Sequence[int], latent_shape,
             scorer: Callable[[torch.Tensor], torch.Tensor] = default_scorer, device="cpu",
             final_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, batch: int = 1,
-            final_split_fn: Optional[Callable] = None, pairs=None):
+            final_split_fn: Optional[Callable] = None, pairs=None, pass_seeds: bool = False):
     """Each rank runs ``denoise_fn(noise [S,4,h,w]) -> latents [S,4,h,w]`` for its share of ``seeds`` (the preview,
     or the full denoise when ``final_fn`` is None), scores them, and the group agrees on the winner.
     ``batch`` = candidates per denoise call (S <= batch): with N > world seeds a rank stacks its candidates into one
@@ -196,6 +213,10 @@ def run_pns(denoise_fn: Callable[[torch.Tensor], torch.Tensor], seeds: Sequence[
     by its owner rank and the next rank -- each computes one half of the CFG pair per step and ``exchange`` swaps them
     (DenoiseEngine.denoise_cfg_split) -- so the serial tail of the two-stage schedule runs on half-size UNet batches; the other
     ranks idle at the winner broadcast as before.  Falls back to ``final_fn`` at world 1.
+
+    ``pass_seeds=True``: ``denoise_fn``, ``final_fn`` and ``final_split_fn`` are also given ``seeds=<the seeds of the candidates in the
+    call, in stacking order>`` as a keyword, for functions that derive the per-step noise of a stochastic sampler from the candidate
+    seed (two_stage_fns(step_noise="seed")).  The default calls them exactly as before.
 
     Returns dict(best_seed, best_score, scores [N], latents = the winner's latents on every rank;
     with ``final_fn`` the winner's noise is re-denoised by its owner rank and that result is returned)."""
@@ -208,7 +229,7 @@ def run_pns(denoise_fn: Callable[[torch.Tensor], torch.Tensor], seeds: Sequence[
     local_lat = {}
     for j0 in range(0, len(mine), max(1, int(batch))):
         group = mine[j0:j0 + max(1, int(batch))]
-        lat = denoise_fn(torch.cat([seed_latents(s, latent_shape) for s in group], 0))
+        lat = denoise_fn(torch.cat([seed_latents(s, latent_shape) for s in group], 0), **(dict(seeds=list(group)) if pass_seeds else {}))
         sc = scorer(lat)
         for k, s in enumerate(group):
             local_scores[j0 + k] = sc[k].to(device)
@@ -225,17 +246,18 @@ def run_pns(denoise_fn: Callable[[torch.Tensor], torch.Tensor], seeds: Sequence[
     best = int(torch.argmax(scores))            # ties -> lowest index: identical on every rank
     owner = best % world
     best_seed = seeds[best]
+    skw = dict(seeds=[best_seed]) if pass_seeds else {}
     split = final_split_fn is not None and pairs and world > 1
     helper = pairs[owner][1] if split else None
     if split and rank in (owner, helper):
         group = pairs[owner][0]
         role = sorted((owner, helper)).index(rank)          # group rank 0 = the unconditional half
-        out = final_split_fn(seed_latents(best_seed, latent_shape), pair_exchange(group, role), role).detach().clone()
+        out = final_split_fn(seed_latents(best_seed, latent_shape), pair_exchange(group, role), role, **skw).detach().clone()
         out = out.to(device=device, dtype=torch.float32).contiguous()
     elif rank == owner:
         out = local_lat[best_seed]
         if final_fn is not None:
-            out = final_fn(seed_latents(best_seed, latent_shape)).detach().clone()
+            out = final_fn(seed_latents(best_seed, latent_shape), **skw).detach().clone()
         out = out.to(device=device, dtype=torch.float32).contiguous()
     else:
         out = torch.empty((1,) + tuple(latent_shape[1:]), dtype=torch.float32, device=device)

@@ -513,6 +513,7 @@ class StepState:
         self.coef6_tab = None      # fp32 [steps, 6] (cx, ce, ch, cn, hx, he) of the general step (multistep / ancestral schedulers), or None
         self.hist = None           # fp32 [S, 4, H, W] its history slot: the previous step's data prediction, or None
         self.noise_bank = None     # fp32 [steps, S, 4, H, W] its per-step noise (stochastic schedulers), or None
+        self.seed_rows = None      # int32 bits of uint32 [S, 4] (seed low, seed high, lane, 0): a seeded schedule's step noise comes from these, or None
         self.t_table = None        # fp32 [steps] timesteps
         self.step = None           # int32 [1] device step counter
         self.in_scale_tab = None   # fp32 [steps] scale_model_input factor (Euler) or None

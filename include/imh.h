@@ -42,7 +42,9 @@ extern "C" {
  * (IMH_OP_ATTN_ENC_CAUSAL = 9), one imh_gemm flag bit (IMH_GF_ACT_QGELU = 128) and one elementwise op (IMH_EW_GATHER_ROWS, 12); no
  * struct changed, and a caller written against the first version 13 cannot observe any of it.  The same holds for the general
  * CFG + scheduler step of the multistep and ancestral samplers, IMH_EW_CFG_MSTEP (13): one more elementwise op on imh_ew_args as it is,
- * and for the two query entries of the dispatch contract, imh_conv_halo_lds_bytes and imh_gemm_check. */
+ * and for the two query entries of the dispatch contract, imh_conv_halo_lds_bytes and imh_gemm_check, and for the seeded step noise:
+ * three entries (imh_step_seeded, imh_randn_seeded, imh_randn_seeded_host) with argument structs of their own and two plan kinds
+ * (IMH_OP_STEP_SEEDED = 10, IMH_OP_RANDN_SEEDED = 11); enum imh_ew_op and imh_ew_args are as they were. */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
@@ -489,6 +491,44 @@ typedef struct imh_ew_args {
  * i0 * 4 * i1 elements of y and of the history buffer `b`. */
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 
+/* ---- seeded step noise: the noise of the stochastic samplers as a pure function of (seed, lane, table row, element) --------------
+ * Philox4x32-10 as published (Salmon et al. 2011, Random123: multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85, ten
+ * rounds).  Sample s owns one 16-byte row of `seeds`, uint32 (k0, k1, lane, 0): k0 / k1 = the low / high word of a 64-bit seed, lane = 0
+ * where every sample has a seed of its own, the sample index where one seed serves a batch.  For element e in [0, 4 HW) of the sample's
+ * NCHW latent (e = ch * HW + pix), table row r and stream word t:
+ *   w0..w3 = philox4x32_10(counter = (e >> 2, r, t, lane), key = (k0, k1)),      u_j = ((w_j >> 9) + 0.5) * 2^-23   (exact in fp32),
+ *   (z0, z1) = sqrt(-2 ln u0) * (cos, sin)(2 pi u1),  (z2, z3) likewise from (u2, u3);  element e takes z_(e & 3);  |z| <= 5.77.
+ * Nothing else enters: not the batch size, the sample's position, the device, eager or graph.  Stream 0 is the step noise; other
+ * values are reserved.  imagharmony_amd/noise.py restates this in numpy (words exact, normals in float64).
+ *
+ * imh_step_seeded: IMH_EW_CFG_MSTEP (every field of `ew` as there, ew.bias -- the bank -- must be NULL) with z generated in the launch
+ * from seeds[s], r = *ew.step and `stream`; a row whose cn is 0 generates nothing.  Fed the same z through a bank, IMH_EW_CFG_MSTEP gives
+ * the same bits.  In a plan: kind IMH_OP_STEP_SEEDED.
+ * Memory: as IMH_EW_CFG_MSTEP without the bank, plus the i0 * 4 uint32 of `seeds`, read only. */
+typedef struct imh_seeded_args {
+    imh_ew_args ew;
+    const uint32_t* seeds;    /* device, [ew.i0][4] */
+    uint32_t stream;
+} imh_seeded_args;
+int imh_step_seeded(const imh_seeded_args* a, void* stream);
+
+/* imh_randn_seeded: the rows by themselves.  y[s, e] = z_(e & 3) of (seeds[s], r, stream), fp32 [S, 4, HW] dense; raw != 0: the uint32
+ * words w_(e & 3) instead.  With quad0 != 0 y is a slice of the row: counter word 0 is quad0 + (e >> 2), modulo 2^32.  r = *step when step is set (device int32, read as uint32), else `row`.  In a plan: kind IMH_OP_RANDN_SEEDED.
+ * imh_randn_seeded_host: the same functions compiled for the host -- y, seeds and step are HOST pointers, nothing is launched (the
+ * integer path is bit-equal to the device's; the normals are float64 rounded once, within an fp32 ulp of the device's few).
+ * Memory: reads the S * 4 uint32 of seeds (and the one int32 at step), writes exactly the S * 4 * HW elements of y. */
+typedef struct imh_randn_args {
+    void* y;
+    const uint32_t* seeds;    /* [S][4] */
+    const int32_t* step;
+    int32_t S, HW;
+    uint32_t row, stream;
+    int32_t raw;
+    uint32_t quad0;           /* first quad: y holds elements [4 quad0, 4 quad0 + 4 HW) of every sample's row (0: the row from its start) */
+} imh_randn_args;
+int imh_randn_seeded(const imh_randn_args* a, void* stream);
+int imh_randn_seeded_host(const imh_randn_args* a);
+
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
  * ip_adapter/custom_pipelines.py:365-377 upcasts the SDXL VAE to fp32 before `vae.decode` (it overflows in fp16): this entry keeps
  * fp32 activations, fp32 weights and fp32 arithmetic (v_mfma_f32_32x32x2_f32: exact products, fp32 accumulate).  All pointers fp32.
@@ -536,7 +576,8 @@ int imh_f32(int op, const imh_f32_args* a, void* stream);
 /* ---- plans: a recorded sequence of the calls above, replayed from C++ (one UNet forward is
  * ~1000 launches; Python would be the bottleneck) and optionally captured into a hipGraph. ---- */
 enum imh_op_kind { IMH_OP_GEMM = 0, IMH_OP_ATTN = 1, IMH_OP_GROUPNORM = 2, IMH_OP_LAYERNORM = 3, IMH_OP_EW = 4,
-                   IMH_OP_ATTN_SMALL = 5, IMH_OP_GEMM_DUAL = 6, IMH_OP_XATTN = 7, IMH_OP_ATTN_ENC = 8, IMH_OP_ATTN_ENC_CAUSAL = 9 };
+                   IMH_OP_ATTN_SMALL = 5, IMH_OP_GEMM_DUAL = 6, IMH_OP_XATTN = 7, IMH_OP_ATTN_ENC = 8, IMH_OP_ATTN_ENC_CAUSAL = 9,
+                   IMH_OP_STEP_SEEDED = 10, IMH_OP_RANDN_SEEDED = 11 };
 
 typedef struct imh_plan imh_plan;
 
