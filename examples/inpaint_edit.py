@@ -6,6 +6,10 @@ and the masked image's latents).
 
     python examples/inpaint_edit.py --out out.png [--image in.png] [--mask mask.png] [--unet unet.safetensors] [--vae vae.safetensors]
                                     [--ip-ckpt ip_adapter.bin] [--in-channels 4] [--strength 0.9999] [--steps 30] [--seed 0] [--size 1024]
+                                    [--seeds 0 1 2 3 --preview-steps 10]
+
+With --seeds the edit runs preference-guided noise selection over them (IPAdapterXL.generate_pns(image=, mask_image=)): every seed gets a
+short preview edit, the judged-best one the full edit; seed s stands for the draws of torch.Generator("cpu").manual_seed(s).
 """
 import argparse
 import os
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--strength", type=float, default=0.9999)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--seeds", type=int, nargs="+", help="several candidate seeds: noise selection (PNS) over them instead of the one --seed")
+    ap.add_argument("--preview-steps", type=int, default=10)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--guidance", type=float, default=5.0)
@@ -68,6 +74,14 @@ def main():
     prompt = (torch.randn(1, 77, 2048, generator=g), torch.randn(1, 77, 2048, generator=g),
               torch.randn(1, 1280, generator=g), torch.randn(1, 1280, generator=g))
     extra = torch.randn(1, 77, 2048, generator=g)
+    if a.seeds:
+        r = ip.generate_pns(a.seeds, clip_image_embeds=clip_embeds, prompt_embeds=prompt, extra_prompt_embeds=extra, scale=a.scale,
+                            preview_steps=a.preview_steps, num_inference_steps=a.steps, guidance_scale=a.guidance, image=image, mask_image=mask,
+                            strength=a.strength)
+        r["images"][0].save(a.out)
+        print(f"inpainted {r['images'][0].size} with in_channels={a.in_channels}, strength {a.strength}; seeds {a.seeds} -> scores "
+              f"{[round(float(s), 4) for s in r['scores']]}, best seed {r['best_seed']}; wrote {a.out}")
+        return
     out = ip.generate(clip_image_embeds=clip_embeds, prompt_embeds=prompt, extra_prompt_embeds=extra, scale=a.scale, num_samples=1,
                       seed=a.seed, num_inference_steps=a.steps, guidance_scale=a.guidance, image=image, mask_image=mask,
                       strength=a.strength)[0]

@@ -6,6 +6,11 @@ whole path (PIL in -> CLIP-shaped embeddings -> HarmonyAttention + ImageProjMode
     python examples/pns_edit.py --out out.png [--unet unet.safetensors] [--vae vae.safetensors] [--ip-ckpt ip_adapter.bin]
                                 [--seeds 0 1 2 3] [--steps 30] [--preview-steps 10] [--size 1024]
                                 [--scheduler euler-a --step-noise seed]
+                                [--init-image in.png --strength 0.6] [--clip-backend hip --judge-preprocess hip]
+
+With --init-image the candidates are image-to-image EDITS of that image (IPAdapterXL.generate_pns(image=, strength=)): every seed fixes its
+posterior and add-noise draws, the previews are decoded and scored by the CLIP judge when a tower is attached (--clip-backend), and
+--judge-preprocess hip takes the decoded previews to the HIP tower's patch rows in one launch.
 
 Launch under torch.distributed.run with N ranks to shard the seeds over N GPUs (one process per GPU, RCCL).
 """
@@ -19,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from imagharmony_amd import pns                                           # noqa: E402
 from imagharmony_amd.ip_adapter import IPAdapterXL                        # noqa: E402
 from imagharmony_amd.modules import HarmonyAttention                      # noqa: E402
-from imagharmony_amd.pipeline import StableDiffusionXLCustomPipeline      # noqa: E402
+from imagharmony_amd.pipeline import StableDiffusionXLCustomPipeline, StableDiffusionXLImg2ImgCustomPipeline      # noqa: E402
 from imagharmony_amd import schedulers as hs                              # noqa: E402
 from imagharmony_amd.unet import UNet2DConditionModel, UNetConfig         # noqa: E402
 from imagharmony_amd.vae import AutoencoderKL, decode_latents, postprocess   # noqa: E402
@@ -54,6 +59,10 @@ def main():
                     help="CLIP vision tower behind the image prompt: none = stand-in embeddings (default); hip = imagharmony_amd's "
                          "CLIPVisionEncoder; transformers = the stock module.  --clip DIR loads a saved tower, else seeded random weights at ViT-bigG/14 size")
     ap.add_argument("--clip")
+    ap.add_argument("--init-image", help="edit this image (image-to-image PNS) instead of generating from noise")
+    ap.add_argument("--strength", type=float, default=0.6, help="with --init-image: how far the edit departs from the image (0 .. 1)")
+    ap.add_argument("--judge-preprocess", choices=("torch", "hip"), default="torch",
+                    help="with --init-image and a CLIP tower: how the judge gets from decoded previews to the tower's input (hip needs --clip-backend hip)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -70,9 +79,11 @@ def main():
         with torch.device(dev):                                            # 2.6 B parameters: create them on the GPU
             unet = UNet2DConditionModel(UNetConfig())
         unet = unet.init_random_(1234).to(dtype)
-    vae = AutoencoderKL.from_safetensors(a.vae, device=dev, dtype=dtype) if a.vae else AutoencoderKL().init_random_(1).to(dev, dtype)
+    enc_kw = {"with_encoder": True} if a.init_image else {}
+    vae = AutoencoderKL.from_safetensors(a.vae, device=dev, dtype=dtype, **enc_kw) if a.vae else AutoencoderKL(**enc_kw).init_random_(1).to(dev, dtype)
     pns.broadcast_module_(unet)                                           # identical replicas on every rank
-    pipe = StableDiffusionXLCustomPipeline(unet, scheduler=SCHEDULERS[a.scheduler](), device=dev, dtype=dtype, vae=vae)
+    pipe_cls = StableDiffusionXLImg2ImgCustomPipeline if a.init_image else StableDiffusionXLCustomPipeline
+    pipe = pipe_cls(unet, scheduler=SCHEDULERS[a.scheduler](), device=dev, dtype=dtype, vae=vae)
     pipe.enable_vae_tiling()                                              # test.py:73
     ha = HarmonyAttention(image_hidden_size=1280, text_context_dim=2048, inter_dim=2560, cross_heads=8, reshape_blocks=8,
                           cross_value_dim=64, scale=1.0, fusion_method="cross_attention")     # test.py:82-91
@@ -81,6 +92,7 @@ def main():
     # encoders are outside the path (no tokenizer vocabulary / CLIP weights offline): stand-in embeddings of the right shape
     g = torch.Generator().manual_seed(0)
     clip_embeds = torch.randn(1, 1280, generator=g)
+    enc = None
     if a.clip_backend != "none":                                          # the image prompt through a real tower (random pixels stand in for the image)
         px = torch.randn(1, 3, 224, 224, generator=g).to(dev, dtype)
         if a.clip_backend == "hip":
@@ -104,6 +116,20 @@ def main():
     prompt = (torch.randn(1, 77, 2048, generator=g), torch.randn(1, 77, 2048, generator=g),
               torch.randn(1, 1280, generator=g), torch.randn(1, 1280, generator=g))
     extra = torch.randn(1, 77, 2048, generator=g)
+    if a.init_image:
+        from PIL import Image
+        ip.image_encoder = enc                                            # the judge's tower (None: the latent-statistic scorer)
+        init = Image.open(a.init_image).convert("RGB").resize((a.size, a.size))
+        r = ip.generate_pns(a.seeds, clip_image_embeds=clip_embeds, prompt_embeds=prompt, extra_prompt_embeds=extra, scale=a.scale,
+                            preview_steps=a.preview_steps, num_inference_steps=a.steps, guidance_scale=a.guidance, image=init,
+                            strength=a.strength, step_noise=a.step_noise, judge_preprocess=a.judge_preprocess)
+        if int(os.environ.get("RANK", "0")) == 0:
+            r["images"][0].save(a.out)
+            print(f"seeds {a.seeds} -> scores {[round(float(s), 4) for s in r['scores']]}; best seed {r['best_seed']}; "
+                  f"edited {a.init_image} at strength {a.strength}; wrote {a.out} {r['images'][0].size}")
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     ipe, uipe = ip.get_image_embeds(clip_image_embeds=clip_embeds, extra_prompt_embeds=extra)
     ip.set_scale(a.scale)
     pe = torch.cat([prompt[0].to(dev, dtype), ipe], 1)

@@ -20,6 +20,8 @@ _PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustom
 _SCHEDULERS = ("DDIMScheduler", "EulerDiscreteScheduler", "DPMSolverMultistepScheduler", "EulerAncestralDiscreteScheduler")
 # the seeded step noise restated in numpy (noise.py): seeded_randn / seed_rows, the yardstick of the device generator
 _NOISE = ("seeded_randn", "seed_rows")
+# the CLIP judge's preprocessing restated in numpy (imageops.py): the yardstick of imh_clip_preprocess
+_IMAGEOPS = ("clip_preprocess_reference", "clip_geometry")
 
 
 def __getattr__(name):
@@ -41,4 +43,7 @@ def __getattr__(name):
     if name in _NOISE:
         from . import noise
         return getattr(noise, name)
+    if name in _IMAGEOPS:
+        from . import imageops
+        return getattr(imageops, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -284,3 +284,37 @@ class CLIPVisionEncoder(nn.Module):
             if output_hidden_states:
                 out.hidden_states = tuple(h.view(B, n, hid).clone() for h in plan["hidden"])
         return out
+
+    @torch.no_grad()
+    def embed_decoded(self, images, output_hidden_states=False):
+        """decoded images [S, 3, H, W] fp32 in [-1, 1] on the encoder's device (what ``vae.decode`` returns) -> the object ``forward``
+        returns for ``ClipPreferenceJudge.preprocess(images)``: one ``imh_clip_preprocess`` launch (Ctx.clip_preprocess: clamp, antialiased
+        bicubic to the shortest edge, centre crop, CLIP mean / std, one rounding to the run dtype) writes the patch rows straight into the
+        recorded plan's ``patches`` buffer, then the plan replays.  No torch op touches the pixels."""
+        from .imageops import CLIP_MEAN, CLIP_STD
+        cfg = self.config
+        if cfg.hidden_act != "gelu":
+            raise NotImplementedError(f"CLIPVisionEncoder: hidden_act={cfg.hidden_act!r} is not implemented (erf GELU only)")
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise NotImplementedError(f"CLIPVisionEncoder.embed_decoded: images {tuple(images.shape)} must be [S, 3, H, W]")
+        if images.device != self.device or images.dtype != torch.float32:
+            raise L.ImhError(f"CLIPVisionEncoder.embed_decoded: images on {images.device} / {images.dtype}, expected {self.device} / torch.float32")
+        B, n, hid = images.shape[0], self.num_positions, cfg.hidden_size
+        with torch.inference_mode(False):
+            key = self._weights_key()
+            self.derived(key)
+            plan = self._plans.get(B)
+            if plan is None or plan["key"] != key:
+                plan = self._plans[B] = self._record(B)
+            eager = self.__dict__.get("_eager")          # one eager context for the encoder's life, not one per preview group
+            if eager is None or eager.device != self.device or eager.dtype != self.dtype:
+                eager = self.__dict__["_eager"] = Ctx(self.device, self.dtype)
+            eager.clip_preprocess(images.detach().contiguous(), plan["patches"], cfg.image_size, cfg.patch_size, CLIP_MEAN, CLIP_STD,
+                                  descr="clip.preprocess")
+            plan["ctx"].replay()
+            out = SimpleNamespace(image_embeds=plan["embeds"].clone(),
+                                  last_hidden_state=plan["hidden"][-1].view(B, n, hid).clone(),
+                                  hidden_states=None, attentions=None)
+            if output_hidden_states:
+                out.hidden_states = tuple(h.view(B, n, hid).clone() for h in plan["hidden"])
+        return out

@@ -249,6 +249,35 @@ static int do_randn_seeded(const imh_randn_args* a, hipStream_t s) {
     return rc != IMH_OK ? rc : randn_seeded_launch(p, s);
 }
 
+static int do_clip_preprocess(const imh_clip_preprocess_args* a, hipStream_t s) {
+    const char* who = "imh_clip_preprocess";
+    if (!a || !a->x || !a->y) { set_error("%s: null pointer argument", who); return IMH_ERR_ARG; }
+    if (a->dtype != IMH_DT_BF16 && a->dtype != IMH_DT_F16 && a->dtype != IMH_CLIP_DT_F32) {
+        set_error("%s: dtype %d is none of IMH_DT_BF16, IMH_DT_F16, IMH_CLIP_DT_F32", who, a->dtype); return IMH_ERR_ARG;
+    }
+    if (((uintptr_t)a->x & 3) || ((uintptr_t)a->y & (a->dtype == IMH_CLIP_DT_F32 ? 3 : 1))) { set_error("%s: x / y must be aligned to their element size", who); return IMH_ERR_ARG; }
+    if (!(a->std0 > 0.f) || !(a->std1 > 0.f) || !(a->std2 > 0.f)) { set_error("%s: std must be positive", who); return IMH_ERR_ARG; }
+    if (a->S < 1 || a->H < 1 || a->W < 1) { set_error("%s: S=%d H=%d W=%d must be positive", who, a->S, a->H, a->W); return IMH_ERR_SHAPE; }
+    if (a->patch < 1 || a->patch > 32 || a->size < a->patch || a->size % a->patch) {
+        set_error("%s: size=%d must be a positive multiple of patch=%d (1 .. 32)", who, a->size, a->patch); return IMH_ERR_SHAPE;
+    }
+    if (a->nh < a->size || a->nw < a->size) { set_error("%s: the resized image %d x %d is smaller than the crop %d", who, a->nh, a->nw, a->size); return IMH_ERR_SHAPE; }
+    if (a->top < 0 || a->left < 0 || a->top > a->nh - a->size || a->left > a->nw - a->size) {
+        set_error("%s: crop (%d, %d) + %d lies outside the resized image %d x %d", who, a->top, a->left, a->size, a->nh, a->nw); return IMH_ERR_SHAPE;
+    }
+    if (a->ldp < 3 * a->patch * a->patch) { set_error("%s: ldp=%d is smaller than a row of 3 * %d * %d values", who, a->ldp, a->patch, a->patch); return IMH_ERR_SHAPE; }
+    const long long g = a->size / a->patch;
+    if ((long long)a->S * g * g * a->ldp > 0x7fffffffLL || (long long)a->S * 3 * a->H * a->W > 0x7fffffffLL || (long long)a->S * 3 * g * g > 0x7fffffffLL) {
+        set_error("%s: S=%d H=%d W=%d size=%d ldp=%d: an operand of 2^31 elements or more", who, a->S, a->H, a->W, a->size, a->ldp); return IMH_ERR_SHAPE;
+    }
+    ClipPreParams p;
+    p.x = a->x; p.y = a->y; p.S = a->S; p.H = a->H; p.W = a->W; p.nh = a->nh; p.nw = a->nw; p.top = a->top; p.left = a->left;
+    p.size = a->size; p.patch = a->patch; p.ldp = a->ldp;
+    p.mean[0] = a->mean0; p.mean[1] = a->mean1; p.mean[2] = a->mean2; p.std[0] = a->std0; p.std[1] = a->std1; p.std[2] = a->std2;
+    p.ncols = p.ntx = p.nty = p.RC = 0;
+    return clip_preprocess_launch(p, a->dtype, s);
+}
+
 }  // namespace imh
 
 using namespace imh;
@@ -268,6 +297,7 @@ struct imh_op {
         imh_enc_attn_args eattn;
         imh_seeded_args seeded;
         imh_randn_args randn;
+        imh_clip_preprocess_args clip;
     } u;
 };
 
@@ -294,6 +324,7 @@ static int run_op(const imh_op& o, hipStream_t s) {
         case IMH_OP_ATTN_ENC_CAUSAL: return do_attn_enc(&o.u.eattn, s, 1);
         case IMH_OP_STEP_SEEDED: return do_step_seeded(&o.u.seeded, s);
         case IMH_OP_RANDN_SEEDED: return do_randn_seeded(&o.u.randn, s);
+        case IMH_OP_CLIP_PREPROCESS: return do_clip_preprocess(&o.u.clip, s);
     }
     set_error("plan: unknown op kind %d", o.kind);
     return IMH_ERR_ARG;
@@ -318,6 +349,7 @@ static size_t args_size(int kind) {
         case IMH_OP_ATTN_ENC_CAUSAL: return sizeof(imh_enc_attn_args);
         case IMH_OP_STEP_SEEDED: return sizeof(imh_seeded_args);
         case IMH_OP_RANDN_SEEDED: return sizeof(imh_randn_args);
+        case IMH_OP_CLIP_PREPROCESS: return sizeof(imh_clip_preprocess_args);
     }
     return 0;
 }
@@ -410,6 +442,7 @@ int imh_elementwise(int op, const imh_ew_args* a, void* stream) { return do_ew(o
 
 int imh_step_seeded(const imh_seeded_args* a, void* stream) { return do_step_seeded(a, (hipStream_t)stream); }
 int imh_randn_seeded(const imh_randn_args* a, void* stream) { return do_randn_seeded(a, (hipStream_t)stream); }
+int imh_clip_preprocess(const imh_clip_preprocess_args* a, void* stream) { return do_clip_preprocess(a, (hipStream_t)stream); }
 int imh_randn_seeded_host(const imh_randn_args* a) {
     RandnParams p;
     const int rc = to_randn(a, "imh_randn_seeded_host", &p);

@@ -247,6 +247,7 @@ __device__ __forceinline__ float wave_max(float v) {
 
 #define IMH_DT_BF16 0
 #define IMH_DT_F16 1
+#define IMH_CLIP_DT_F32 2      // imh_clip_preprocess's fp32 rows only (include/imh.h)
 
 namespace imh {
 // Dynamic-LDS opt-in (> 64 KB) is a per-DEVICE function attribute: remember it per device ordinal, so a process that drives a

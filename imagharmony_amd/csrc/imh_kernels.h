@@ -211,4 +211,17 @@ struct RandnParams {
 int randn_seeded_launch(const RandnParams& p, hipStream_t stream);
 int randn_seeded_host(const RandnParams& p);       // the same functions on the host, into caller memory (seeds / step / y host pointers)
 
+// decoded image -> CLIP patch rows (image.hip; imh_clip_preprocess).  ncols / ntx / nty / RC are set by the launcher: the LDS extents of
+// the staged source chunk ([RC][ncols]) and of the two tap tables ([patch][ntx], [patch][nty])
+struct ClipPreParams {
+    const float* x;        // [S, 3, H, W]
+    void* y;               // [S g g, ldp] of T
+    int S, H, W;
+    int nh, nw, top, left; // resized extent and crop origin
+    int size, patch, ldp;
+    float mean[3], std[3];
+    int ncols, ntx, nty, RC;
+};
+int clip_preprocess_launch(ClipPreParams p, int dtype, hipStream_t stream);   // dtype: IMH_DT_BF16 / IMH_DT_F16 / IMH_CLIP_DT_F32
+
 }  // namespace imh

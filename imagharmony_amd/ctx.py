@@ -223,6 +223,8 @@ class Ctx:
             rc = self.lib.imh_step_seeded(C.byref(args), s)
         elif kind == L.OP_RANDN_SEEDED:
             rc = self.lib.imh_randn_seeded(C.byref(args), s)
+        elif kind == L.OP_CLIP_PREPROCESS:
+            rc = self.lib.imh_clip_preprocess(C.byref(args), s)
         else:
             rc = self.lib.imh_elementwise(ew_op, C.byref(args), s)
         L.check(rc, descr or f"op kind {kind}")
@@ -1010,6 +1012,35 @@ class Ctx:
         a = L.RandnArgs()
         a.y, a.seeds, a.step, a.S, a.HW, a.row, a.stream, a.raw = out.data_ptr(), seeds.data_ptr(), self._p(step), S, HW, int(row), int(noise_stream), int(bool(raw))
         self._emit(L.OP_RANDN_SEEDED, a, descr=descr, nbytes=16.0 * S * HW, keep=(seeds, step, out))
+        return out
+
+    def clip_preprocess(self, images, out, size, patch, mean, std, descr="clip_preprocess"):
+        """decoded images -> the CLIP tower's patch rows in one launch (imh_clip_preprocess; imagharmony_amd/imageops.py states what they
+        are): images fp32 [S, 3, H, W] in [-1, 1], dense; out [S g g, >= 3 patch patch] row-major (any row stride) in bfloat16, float16 or
+        float32 -- columns [0, 3 patch patch) of every row are written, the rest of the row is left alone.  The resized extent and the crop
+        origin are derived here (imageops.clip_geometry, as ClipPreferenceJudge.preprocess derives them)."""
+        from .imageops import clip_geometry
+        self._chk(images, descr + ".images", torch.float32)
+        if out.dtype not in _DT and out.dtype != torch.float32:
+            raise L.ImhError(f"{descr}: out dtype {out.dtype} (bfloat16, float16 or float32)")
+        self._chk(out, descr + ".out", out.dtype)
+        if images.dim() != 4 or images.shape[1] != 3 or not images.is_contiguous():
+            raise L.ImhError(f"{descr}: images {tuple(images.shape)} must be dense [S, 3, H, W]")
+        S, _, H, W = (int(v) for v in images.shape)
+        size, patch = int(size), int(patch)
+        if patch < 1 or size < patch or size % patch:
+            raise L.ImhError(f"{descr}: size {size} must be a positive multiple of patch {patch}")
+        g, k = size // patch, 3 * patch * patch
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != S * g * g or out.shape[1] < k or out.stride(0) < out.shape[1]:
+            raise L.ImhError(f"{descr}: out {tuple(out.shape)} must be row-major [{S * g * g}, >= {k}]")
+        nh, nw, top, left = clip_geometry(H, W, size)
+        a = L.ClipPreprocessArgs()
+        a.x, a.y, a.S, a.H, a.W = images.data_ptr(), out.data_ptr(), S, H, W
+        a.nh, a.nw, a.top, a.left, a.size, a.patch, a.ldp = nh, nw, top, left, size, patch, out.stride(0)
+        a.mean0, a.mean1, a.mean2 = (float(v) for v in mean)
+        a.std0, a.std1, a.std2 = (float(v) for v in std)
+        a.dtype = _DT.get(out.dtype, L.CLIP_DT_F32)
+        self._emit(L.OP_CLIP_PREPROCESS, a, descr=descr, nbytes=4.0 * images.numel() + float(out.element_size()) * S * g * g * k, keep=(images, out))
         return out
 
     def gather_rows(self, table, idx, add=None, out=None, descr="gather_rows"):

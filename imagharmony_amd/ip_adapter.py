@@ -254,7 +254,8 @@ class IPAdapterXL(IPAdapter):
     def generate_pns(self, seeds, pil_image=None, prompt=None, negative_prompt=None, extra_text=None, scale=1.0,
                      preview_steps=10, num_inference_steps=30, guidance_scale=5.0, scorer=None, batch=None,
                      clip_image_embeds=None, prompt_embeds=None, extra_prompt_embeds=None, height=None, width=None,
-                     output_type="pil", step_noise="global", **schedule_kw):
+                     output_type="pil", step_noise="global", image=None, mask_image=None, strength=None, judge_preprocess="torch",
+                     **schedule_kw):
         """Preference-guided noise selection (README.md:27, assets/1.png) around ``generate``: every candidate seed gets
         a ``preview_steps`` denoise, a judge scores the previews, the best NOISE gets the full ``num_inference_steps``
         denoise.  Candidates are sharded over the ranks of an initialised torch.distributed group (one process per
@@ -267,11 +268,31 @@ class IPAdapterXL(IPAdapter):
         previews and the final denoise (pns.two_stage_fns has the details): "global" (default) takes it from torch's global generator, so a
         seed fixes the initial noise only; "seed" generates it on the device from each candidate's own seed (lane 0), so a seed fixes
         its whole trajectory, stacked or alone, on any rank.
-        Returns dict(images, best_seed, scores, latents).  Text-to-image only: an image-to-image or inpainting pipeline raises NotImplementedError."""
+        ``judge_preprocess``: how the default CLIP judge gets from decoded previews to the encoder's input -- "torch" (default): the chain
+        of torch ops of ``pns.ClipPreferenceJudge.preprocess``; "hip": one imh_clip_preprocess launch straight into the HIP vision tower's
+        patch buffer (``CLIPVisionEncoder.embed_decoded``); it needs ``image_encoder_backend="hip"`` (ValueError before any GPU work).
+        On an image-to-image or inpainting pipe the candidates are EDITS of ``image`` (and, inpainting, ``mask_image``; white = repaint) at
+        ``strength`` (default: the pipe's own, 0.3 / 0.9999): the image -- and, for a 9-channel UNet, the masked image -- is encoded once,
+        and for candidate seed s every draw comes from ``torch.Generator("cpu").manual_seed(s)`` in the pipe's order (posterior noise of
+        the image, add-noise noise, 9 channels: posterior noise of the masked image; pns.edit_draws).  The winner's latents are therefore the
+        bits of ``pipe(image=, [mask_image=,] strength=, num_inference_steps=num_inference_steps, generator=[that generator],
+        output_type="latent")`` -- with ``step_noise="seed"`` under a stochastic scheduler, of that call with ``step_noise="seeded"``.
+        height / width follow the image there.
+        Returns dict(images, best_seed, scores, latents)."""
         from . import pns
         from .pipeline import StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline
+        seeds = list(seeds)                       # consumed more than once below: a generator passed as `seeds` must survive that
+        if judge_preprocess not in ("torch", "hip"):
+            raise ValueError(f"judge_preprocess={judge_preprocess!r}: 'torch' or 'hip'")
+        if judge_preprocess == "hip" and not hasattr(self.image_encoder, "embed_decoded"):
+            raise ValueError('judge_preprocess="hip" needs the HIP CLIP vision tower as the image encoder '
+                             '(image_encoder_backend="hip" / image_encoder=CLIPVisionEncoder)')
         if isinstance(self.pipe, (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline)):
-            raise NotImplementedError("generate_pns runs text-to-image schedules; image-to-image and inpainting PNS are not supported")
+            return self._generate_pns_edit(seeds, pil_image, prompt, negative_prompt, extra_text, scale, preview_steps, num_inference_steps,
+                                           guidance_scale, scorer, batch, clip_image_embeds, prompt_embeds, extra_prompt_embeds, output_type,
+                                           step_noise, image, mask_image, strength, judge_preprocess, schedule_kw)
+        if image is not None or mask_image is not None or strength is not None:
+            raise ValueError("image= / mask_image= / strength= belong to an image-to-image or inpainting pipeline")
         self.set_scale(scale)
         pipe = self.pipe
         prompt = prompt if prompt is not None else "best quality, high quality"
@@ -294,14 +315,15 @@ class IPAdapterXL(IPAdapter):
         if batch is None:
             import torch.distributed as dist
             world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-            batch = min(4, (len(list(seeds)) + world - 1) // world)
+            batch = min(4, (len(seeds) + world - 1) // world)
         S = max(1, int(batch))
         eng = pipe.engine
         rep = lambda t, n: t.repeat(*([n] + [1] * (t.ndim - 1)))
         if scorer is None:
             if pipe.vae is not None and self.image_encoder is not None:
                 from .vae import decode_latents
-                scorer = pns.ClipPreferenceJudge(lambda z: decode_latents(pipe.vae, z), self.image_encoder, fused)
+                scorer = pns.ClipPreferenceJudge(lambda z: decode_latents(pipe.vae, z), self.image_encoder, fused,
+                                                 **({"preprocess_backend": "hip"} if judge_preprocess == "hip" else {}))
             else:
                 scorer = pns.default_scorer
         shape = (1, 4, height // 8, width // 8)
@@ -326,11 +348,120 @@ class IPAdapterXL(IPAdapter):
                 cond(noise.shape[0]); state["n"] = noise.shape[0]
             return stage_fin(noise, **kw)
 
-        r = pns.run_pns(preview, list(seeds), shape, scorer=scorer, device=self.device, final_fn=final, batch=S, **({"pass_seeds": True} if by_seed else {}))
+        r = pns.run_pns(preview, seeds, shape, scorer=scorer, device=self.device, final_fn=final, batch=S, **({"pass_seeds": True} if by_seed else {}))
         out = r["latents"]
         if output_type != "latent":
             if pipe.vae is None and pipe.vae_decode is None:
                 raise NotImplementedError("output_type=%r needs a VAE on the pipeline; pass output_type='latent'" % (output_type,))
+            if pipe.vae is not None:
+                from .vae import decode_latents, postprocess
+                out = postprocess(decode_latents(pipe.vae, out), output_type)
+            else:
+                out = pipe.vae_decode(out)
+        return dict(images=out, best_seed=r["best_seed"], scores=r["scores"], latents=r["latents"])
+
+    def _generate_pns_edit(self, seeds, pil_image, prompt, negative_prompt, extra_text, scale, preview_steps, num_inference_steps,
+                           guidance_scale, scorer, batch, clip_image_embeds, prompt_embeds, extra_prompt_embeds, output_type, step_noise,
+                           image, mask_image, strength, judge_preprocess, schedule_kw):
+        """generate_pns on an image-to-image / inpainting pipe (its docstring states the contract): everything a candidate shares -- the
+        conditioning, the encoder moments of the image (and masked image), the latent mask -- is computed once; a candidate costs its
+        draws, one fused initial-latents launch (stacked ``batch`` per call) and the truncated denoise."""
+        from . import pns
+        from .pipeline import StableDiffusionXLInpaintCustomPipeline
+        from .schedulers import get_timesteps
+        from .vae import latent_mask, preprocess, preprocess_mask
+        pipe = self.pipe
+        inpaint = isinstance(pipe, StableDiffusionXLInpaintCustomPipeline)
+        # refusals first, before any GPU work
+        if step_noise not in ("global", "seed"):
+            raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
+        if image is None:
+            raise NotImplementedError("generate_pns on an image-to-image / inpainting pipe selects among EDITS of image= (PIL or a tensor "
+                                      "[1, 3, H, W]); text-to-image schedules on such a pipe are not supported")
+        if inpaint and mask_image is None:
+            raise ValueError("PNS on an inpainting pipe needs mask_image= (white = repaint)")
+        if not inpaint and mask_image is not None:
+            raise ValueError("mask_image= belongs to an inpainting pipeline")
+        if strength is None:
+            strength = 0.9999 if inpaint else 0.3
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
+        if output_type != "latent" and pipe.vae is None and pipe.vae_decode is None:
+            raise NotImplementedError("output_type=%r needs a VAE on the pipeline; pass output_type='latent'" % (output_type,))
+        if pipe.vae is None or not getattr(pipe.vae, "with_encoder", False):
+            raise NotImplementedError("an edit needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
+        for steps in (preview_steps, num_inference_steps):
+            pipe.scheduler.set_timesteps(steps)
+            get_timesteps(pipe.scheduler, steps, strength)       # a stage that truncates to no step: the pipelines' ValueError
+        img = preprocess(image)
+        if img.shape[0] != 1:
+            raise ValueError(f"PNS edits one image (the candidates are its seeds), got a batch of {img.shape[0]}")
+        height, width = int(img.shape[2]), int(img.shape[3])
+        h, w = height // 8, width // 8
+        mask = None
+        if inpaint:
+            mask = preprocess_mask(mask_image, height, width)
+            if mask.shape[0] != 1:
+                raise ValueError(f"PNS edits one image under one mask, got a mask batch of {mask.shape[0]}")
+        self.set_scale(scale)
+        prompt = prompt if prompt is not None else "best quality, high quality"
+        negative_prompt = negative_prompt if negative_prompt is not None else \
+            "monochrome, lowres, bad anatomy, worst quality, low quality"
+        if extra_prompt_embeds is None and extra_text is not None:
+            extra_prompt_embeds = pipe.encode_prompt(extra_text, num_images_per_prompt=1, do_classifier_free_guidance=True,
+                                                     negative_prompt=negative_prompt)[0]
+        fused = self.fused_clip_embeds(pil_image, clip_image_embeds, extra_prompt_embeds)
+        ipe = self._g(self.image_proj_model)(fused)
+        uipe = self._g(self.image_proj_model)(torch.zeros_like(fused))
+        if prompt_embeds is None:
+            prompt_embeds = pipe.encode_prompt(prompt, num_images_per_prompt=1, do_classifier_free_guidance=True,
+                                               negative_prompt=negative_prompt)
+        pe, ne, ppe, npe = prompt_embeds
+        pe = torch.cat([pe.to(ipe.device, self.dtype), ipe], dim=1)
+        ne = torch.cat([ne.to(ipe.device, self.dtype), uipe], dim=1)
+        if batch is None:
+            import torch.distributed as dist
+            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+            batch = min(4, (len(seeds) + world - 1) // world)
+        S = max(1, int(batch))
+        eng, vae = pipe.engine, pipe.vae
+        rep = lambda t, n: t.repeat(*([n] + [1] * (t.ndim - 1)))      # noqa: E731
+        # encoded once, at batch 1 as the pipelines encode a per-sample-generator call
+        concat = inpaint and pipe.unet.config.in_channels == 9
+        need_z = not concat or float(strength) != 1.0                # (9 channels at strength 1.0: nothing reads the image latents)
+        moments = vae.encode_moments(img).clone() if need_z else None
+        masked_moments = vae.encode_moments(img * (mask < 0.5)).clone() if concat else None
+        lmask = latent_mask(mask, h, w) if inpaint else None
+        if scorer is None:
+            if self.image_encoder is not None:
+                from .vae import decode_latents
+                scorer = pns.ClipPreferenceJudge(lambda z: decode_latents(vae, z), self.image_encoder, fused,
+                                                 **({"preprocess_backend": "hip"} if judge_preprocess == "hip" else {}))
+            else:
+                scorer = pns.default_scorer
+        prepare = pns.edit_prepare_fn(eng, pipe.scheduler, vae.config.scaling_factor, moments, h, w, strength, mask=lmask,
+                                      masked_moments=masked_moments, concat=concat)
+        stage_pre, stage_fin = pns.edit_two_stage_fns(eng, pipe.scheduler, prepare, strength, preview_steps, num_inference_steps,
+                                                      step_noise=step_noise, inpaint=inpaint, **schedule_kw)
+        state = {"n": None}
+
+        def cond(n):
+            if state["n"] != n:
+                eng.set_conditioning(rep(pe, n), rep(ne, n), rep(ppe.to(ipe.device), n), rep(npe.to(ipe.device), n), height, width,
+                                     guidance_scale=guidance_scale)
+                state["n"] = n
+
+        def preview(noise, seeds=None):
+            cond(noise.shape[0])
+            return stage_pre(seeds=seeds)
+
+        def final(noise, seeds=None):
+            cond(noise.shape[0])
+            return stage_fin(seeds=seeds)
+
+        r = pns.run_pns(preview, seeds, (1, 4, h, w), scorer=scorer, device=self.device, final_fn=final, batch=S, pass_seeds=True)
+        out = r["latents"]
+        if output_type != "latent":
             if pipe.vae is not None:
                 from .vae import decode_latents, postprocess
                 out = postprocess(decode_latents(pipe.vae, out), output_type)

@@ -18,6 +18,8 @@ IMH_DT_BF16, IMH_DT_F16 = 0, 1
 GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL, GF_ACT_QGELU = 1, 2, 4, 8, 16, 32, 64, 128
 OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN, OP_ATTN_ENC, OP_ATTN_ENC_CAUSAL = range(10)
 OP_STEP_SEEDED, OP_RANDN_SEEDED = 10, 11      # the seeded step noise (imh.h): additive plan kinds
+OP_CLIP_PREPROCESS = 13                       # imh_clip_preprocess (imh.h: kind 12 stays refused)
+CLIP_DT_F32 = 2                               # imh_clip_preprocess's fp32 rows (no other entry takes it)
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
  EW_ROW_STATS, EW_STEP_ROW, EW_GATHER_ROWS, EW_CFG_MSTEP) = range(14)
@@ -111,6 +113,12 @@ class RandnArgs(C.Structure):
     _fields_ = [("y", _vp), ("seeds", _vp), ("step", _vp), ("S", _i32), ("HW", _i32), ("row", C.c_uint32), ("stream", C.c_uint32), ("raw", _i32), ("quad0", C.c_uint32)]
 
 
+class ClipPreprocessArgs(C.Structure):
+    _fields_ = [("x", _vp), ("y", _vp), ("S", _i32), ("H", _i32), ("W", _i32), ("nh", _i32), ("nw", _i32), ("top", _i32), ("left", _i32),
+                ("size", _i32), ("patch", _i32), ("ldp", _i32), ("mean0", _f32), ("mean1", _f32), ("mean2", _f32),
+                ("std0", _f32), ("std1", _f32), ("std2", _f32), ("dtype", _i32)]
+
+
 class F32Args(C.Structure):
     _fields_ = [("X", _vp), ("W", _vp), ("Y", _vp), ("bias", _vp), ("residual", _vp), ("gamma", _vp), ("beta", _vp), ("ws", _vp),
                 ("M", _i32), ("N", _i32), ("K", _i32), ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32),
@@ -149,6 +157,7 @@ SYMBOLS = [
     ("imh_step_seeded", C.c_int, [C.POINTER(SeededArgs), _vp]),
     ("imh_randn_seeded", C.c_int, [C.POINTER(RandnArgs), _vp]),
     ("imh_randn_seeded_host", C.c_int, [C.POINTER(RandnArgs)]),
+    ("imh_clip_preprocess", C.c_int, [C.POINTER(ClipPreprocessArgs), _vp]),
     ("imh_f32", C.c_int, [C.c_int, C.POINTER(F32Args), _vp]),
     ("imh_plan_create", _vp, []),
     ("imh_plan_destroy", None, [_vp]),

@@ -98,10 +98,18 @@ class ClipPreferenceJudge:
     scored by cosine similarity with ``target_embeds`` -- the harmony-fused image embedding
     ``clip + HarmonyAttention(text, clip)`` (ip_adapter.py:170-173) the denoise was conditioned on."""
 
-    MEAN = (0.48145466, 0.4578275, 0.40821073)
-    STD = (0.26862954, 0.26130258, 0.27577711)
+    from .imageops import CLIP_MEAN as MEAN, CLIP_STD as STD      # one set of constants for both preprocess backends
 
-    def __init__(self, decode_fn, image_encoder, target_embeds, image_size=None):
+    def __init__(self, decode_fn, image_encoder, target_embeds, image_size=None, preprocess_backend="torch"):
+        """preprocess_backend: "torch" (default) -- ``preprocess`` below, a chain of torch ops over the full-resolution images, then the
+        encoder's ``forward``; "hip" -- ``CLIPVisionEncoder.embed_decoded``: one imh_clip_preprocess launch writes the encoder's patch rows
+        from the decoded images (the same steps, specified in imagharmony_amd/imageops.py); needs a CLIPVisionEncoder (ValueError)."""
+        if preprocess_backend not in ("torch", "hip"):
+            raise ValueError(f"preprocess_backend={preprocess_backend!r}: 'torch' or 'hip'")
+        if preprocess_backend == "hip" and not hasattr(image_encoder, "embed_decoded"):
+            raise ValueError('preprocess_backend="hip" needs imagharmony_amd.clip_vision.CLIPVisionEncoder as the image encoder '
+                             f"(got {type(image_encoder).__name__})")
+        self.preprocess_backend = preprocess_backend
         self.decode_fn = decode_fn
         self.image_encoder = image_encoder
         cfg = getattr(image_encoder, "config", None)
@@ -126,6 +134,10 @@ class ClipPreferenceJudge:
     @torch.no_grad()
     def __call__(self, latents):
         images = self.decode_fn(latents)
+        if self.preprocess_backend == "hip":
+            emb = self.image_encoder.embed_decoded(images.float().to(self.image_encoder.device)).image_embeds.float()
+            emb = torch.nn.functional.normalize(emb, dim=-1)
+            return (emb * self.target.to(emb.device)).sum(-1)
         p = next(self.image_encoder.parameters())
         px = self.preprocess(images).to(device=p.device, dtype=p.dtype)
         emb = self.image_encoder(px).image_embeds.float()
@@ -166,6 +178,69 @@ def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, step_nois
 
     def final(noise, seeds=None):
         return run(final_steps, noise, seeds)
+
+    return preview, final
+
+
+def edit_draws(seeds, h, w, third=False):
+    """what a candidate seed means in an edit: per seed the draws of the image-to-image / inpainting pipelines, in their order, from
+    ``torch.Generator("cpu").manual_seed(seed)`` -- the posterior noise of the image, the add-noise noise and, ``third`` (9-channel
+    inpainting UNet), the posterior noise of the masked image.  -> (n1, n2, n3 or None), each fp32 [len(seeds), 4, h, w] on the CPU: the
+    tensors ``pipe(..., generator=[that generator])`` draws for a batch of one, stacked."""
+    gens = [torch.Generator("cpu").manual_seed(int(s)) for s in seeds]
+    draw = lambda: torch.cat([torch.randn((1, 4, int(h), int(w)), generator=g, dtype=torch.float32) for g in gens], 0)      # noqa: E731
+    n1, n2 = draw(), draw()
+    return n1, n2, (draw() if third else None)
+
+
+def edit_prepare_fn(engine, scheduler, scaling, moments, h, w, strength, mask=None, masked_moments=None, concat=False):
+    """``prepare(seeds, t_start)`` for ``edit_two_stage_fns``: draws every candidate's noise (edit_draws) and writes the stacked initial
+    latents -- and, inpainting, the blend / conv_in state -- into the engine under its current schedule.  moments: the image's encoder
+    moments (one image, every candidate reads it; None where nothing reads them: a 9-channel UNet at strength 1.0); mask: the latent mask
+    [1, 1, h, w] (inpainting, else None); concat: a 9-channel UNet, with masked_moments the masked image's encoder moments."""
+    strength_max = float(strength) == 1.0
+
+    def prepare(seeds, t_start):
+        n1, n2, n3 = edit_draws(seeds, h, w, third=concat)
+        a, b = scheduler.add_noise_coefficients(t_start)
+        if mask is None:
+            return engine.prepare_img2img(moments, n1, n2, scaling, a, b)
+        return engine.prepare_inpaint(moments, n1, n2, scaling, a, b, mask, strength_max=strength_max, masked_moments=masked_moments, n3=n3)
+
+    return prepare
+
+
+def edit_two_stage_fns(engine, scheduler, prepare, strength, preview_steps=10, final_steps=30, step_noise="global", inpaint=False, **schedule_kw):
+    """two_stage_fns for an edit (image-to-image, inpainting): every candidate seed gets a ``preview_steps`` schedule truncated by
+    ``strength`` as the pipelines truncate theirs, the judged-best seed the ``final_steps`` one.  Returns (preview_fn, final_fn) for
+    ``run_pns(..., pass_seeds=True)``: the functions ignore the noise run_pns hands them (an edit's initial latents are not plain noise)
+    and take the candidates' ``seeds=``.  Per stage: scheduler.set_timesteps(steps); t_start from schedulers.get_timesteps (a schedule that
+    truncates to no step raises its ValueError); engine.set_schedule(..., t_start=t_start, inpaint=inpaint[, seeded_noise=True]);
+    ``prepare(seeds, t_start)`` puts the stacked initial latents in place (edit_prepare_fn); engine.denoise(None, ...).
+    step_noise as in two_stage_fns; with "seed" the step noise rows read are the schedule's rows t_start .. (the device step counter), as
+    in the pipelines' ``step_noise="seeded"`` call with one generator per sample."""
+    from .schedulers import get_timesteps
+    if step_noise not in ("global", "seed"):
+        raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
+    seeded = step_noise == "seed"
+
+    def run(steps, seeds):
+        if seeds is None:
+            raise ValueError("an edit candidate is defined by its seed: run_pns(..., pass_seeds=True)")
+        seeds = [int(s) for s in seeds]
+        scheduler.set_timesteps(steps)
+        _, t_start = get_timesteps(scheduler, steps, strength)
+        engine.set_schedule(scheduler, steps, t_start=t_start, inpaint=inpaint, **({"seeded_noise": True} if seeded else {}), **schedule_kw)
+        prepare(seeds, t_start)
+        if seeded and engine.seeded:                     # (a deterministic sampler ignores the flag: it draws no noise)
+            return engine.denoise(None, step_seeds=seeds).clone()
+        return engine.denoise(None).clone()
+
+    def preview(noise=None, seeds=None):
+        return run(preview_steps, seeds)
+
+    def final(noise=None, seeds=None):
+        return run(final_steps, seeds)
 
     return preview, final
 

@@ -44,7 +44,8 @@ extern "C" {
  * CFG + scheduler step of the multistep and ancestral samplers, IMH_EW_CFG_MSTEP (13): one more elementwise op on imh_ew_args as it is,
  * and for the two query entries of the dispatch contract, imh_conv_halo_lds_bytes and imh_gemm_check, and for the seeded step noise:
  * three entries (imh_step_seeded, imh_randn_seeded, imh_randn_seeded_host) with argument structs of their own and two plan kinds
- * (IMH_OP_STEP_SEEDED = 10, IMH_OP_RANDN_SEEDED = 11); enum imh_ew_op and imh_ew_args are as they were. */
+ * (IMH_OP_STEP_SEEDED = 10, IMH_OP_RANDN_SEEDED = 11); enum imh_ew_op and imh_ew_args are as they were.  And for the image op of the PNS
+ * judge: one entry (imh_clip_preprocess) with an argument struct of its own and one plan kind (IMH_OP_CLIP_PREPROCESS = 13). */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
@@ -528,6 +529,44 @@ typedef struct imh_randn_args {
 } imh_randn_args;
 int imh_randn_seeded(const imh_randn_args* a, void* stream);
 int imh_randn_seeded_host(const imh_randn_args* a);
+
+/* ---- image ops: decoded image -> the patch rows of the CLIP vision tower ------------------------------------------------------------
+ * The preprocessing of the PNS judge (imagharmony_amd.pns.ClipPreferenceJudge.preprocess, i.e. CLIPImageProcessor's resize / centre crop
+ * / normalise on tensors) and the im2col of the tower's patch embedding in one launch.  x: fp32 NCHW [S, 3, H, W], nominally in [-1, 1],
+ * dense.  y: [S g g, ldp] of T, g = size / patch; row s g g + gy g + gx holds the 3 patch patch values of patch (gy, gx) of image s in
+ * Conv2d's weight order (c, py, px).  Per value:
+ *   1. u = clamp(x / 2 + 0.5, 0, 1)
+ *   2. antialiased bicubic (A = -0.5) resize of u to (nh, nw), separable, horizontal pass first; per axis, with scale = in / out:
+ *        support = 2 scale if scale >= 1 else 2;   centre = scale (i + 0.5);
+ *        taps j in [max(0, int(centre - support + 0.5)), min(in, int(centre + support + 0.5)));
+ *        weight cubic((j - centre + 0.5) (1 / scale if scale >= 1 else 1)), the weights of one output normalised to sum 1;
+ *        cubic(t) = (1.5 |t| - 2.5) t t + 1 below 1, -0.5 (((|t| - 5) |t| + 8) |t| - 4) below 2, else 0
+ *      -- the filter of torch's upsample_bicubic2d_aa; this statement was run against torch's CPU result (tests/test_clip_preprocess_host.py,
+ *      profiles/clip_judge_parity.json) and needed no correction.  The caller derives nh, nw (shortest edge -> size, Python's round, at
+ *      least size) and the crop origin top = (nh - size) / 2, left = (nw - size) / 2 and passes them; only the cropped pixels are computed
+ *   3. clamp to [0, 1]    4. (v - mean[c]) / std[c]    5. one rounding to T.
+ * imagharmony_amd/imageops.py restates this in numpy float64.  fp32 accumulation in tap order; no atomics: the rows are a pure function
+ * of x and the arguments, the same bits eagerly, from a plan and from a replayed graph.
+ * dtype: IMH_DT_BF16, IMH_DT_F16 or IMH_CLIP_DT_F32 (fp32 rows; this entry only).
+ * Refused without a launch: null x / y or misaligned pointers, a dtype that is none of the three, std <= 0 (IMH_ERR_ARG); S, H, W < 1,
+ * size % patch != 0, patch outside [1, 32], nh < size or nw < size, a crop outside (nh, nw), ldp < 3 patch patch, S g g ldp or S 3 H W
+ * >= 2^31 (IMH_ERR_SHAPE); and a downscale whose tap tables and source window exceed 64 KB of LDS (IMH_ERR_SHAPE; 1024 -> 224 needs 21 KB).
+ * In a plan: kind IMH_OP_CLIP_PREPROCESS = 13.  enum imh_op_kind is as it was and kind 12 stays refused.
+ * Memory: reads, of every image and channel, the source pixels under the taps of the cropped outputs only (inside [0, H) x [0, W));
+ * writes columns [0, 3 patch patch) of rows [0, S g g) of y and leaves the columns [3 patch patch, ldp) of every row alone. */
+#define IMH_CLIP_DT_F32 2
+#define IMH_OP_CLIP_PREPROCESS 13
+typedef struct imh_clip_preprocess_args {
+    const float* x;
+    void* y;
+    int32_t S, H, W;
+    int32_t nh, nw, top, left;
+    int32_t size, patch, ldp;
+    float mean0, mean1, mean2;
+    float std0, std1, std2;
+    int32_t dtype;
+} imh_clip_preprocess_args;
+int imh_clip_preprocess(const imh_clip_preprocess_args* a, void* stream);
 
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
  * ip_adapter/custom_pipelines.py:365-377 upcasts the SDXL VAE to fp32 before `vae.decode` (it overflows in fp16): this entry keeps
