@@ -15,7 +15,10 @@ _CLIP_TEXT = ("CLIPTextEncoder", "CLIPTextEncoderConfig")
 
 
 # the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
-_PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline")
+_PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline",
+              "StableDiffusionXLControlNetCustomPipeline")
+# the SDXL ControlNet (controlnet.py): the model whose residuals the UNet forward adds to its skips
+_CONTROLNET = ("ControlNetModel",)
 # the schedulers of the device-resident loop (schedulers.py): the two linear ones and the multistep / ancestral ones
 _SCHEDULERS = ("DDIMScheduler", "EulerDiscreteScheduler", "DPMSolverMultistepScheduler", "EulerAncestralDiscreteScheduler")
 # the seeded step noise restated in numpy (noise.py): seeded_randn / seed_rows, the yardstick of the device generator
@@ -37,6 +40,9 @@ def __getattr__(name):
     if name in _PIPELINES:
         from . import pipeline
         return getattr(pipeline, name)
+    if name in _CONTROLNET:
+        from . import controlnet
+        return getattr(controlnet, name)
     if name in _SCHEDULERS:
         from . import schedulers
         return getattr(schedulers, name)

@@ -278,6 +278,23 @@ static int do_clip_preprocess(const imh_clip_preprocess_args* a, hipStream_t s) 
     return clip_preprocess_launch(p, a->dtype, s);
 }
 
+static int do_control_add(const imh_control_add_args* a, hipStream_t s) {
+    const char* who = "imh_control_add";
+    if (!a || !a->x || !a->r || !a->y) { set_error("%s: null pointer argument", who); return IMH_ERR_ARG; }
+    if (((uintptr_t)a->x | (uintptr_t)a->r | (uintptr_t)a->y) & 15) { set_error("%s: x, r and y must be 16-byte aligned", who); return IMH_ERR_ARG; }
+    if (((uintptr_t)a->partial | (uintptr_t)a->tab | (uintptr_t)a->step) & 3) { set_error("%s: partial, tab and step must be 4-byte aligned", who); return IMH_ERR_ARG; }
+    if ((a->tab == nullptr) != (a->step == nullptr)) { set_error("%s: tab and step come together", who); return IMH_ERR_ARG; }
+    if (a->B <= 0 || a->HW <= 0 || a->C <= 0 || a->Br <= 0) { set_error("%s: B=%d Br=%d HW=%d C=%d must be positive", who, a->B, a->Br, a->HW, a->C); return IMH_ERR_SHAPE; }
+    // y overlapping x or r (the in-place form included) is refused: the superseded tensor stays what its other readers saw
+    const size_t yb = (size_t)a->B * a->HW * a->C * 2, rb = (size_t)a->Br * a->HW * a->C * 2;
+    const uintptr_t y0 = (uintptr_t)a->y, x0 = (uintptr_t)a->x, r0 = (uintptr_t)a->r;
+    if ((y0 < x0 + yb && x0 < y0 + yb) || (y0 < r0 + rb && r0 < y0 + yb)) { set_error("%s: y must not overlap x or r (no in-place form)", who); return IMH_ERR_ARG; }
+    ControlAddParams p;
+    p.x = a->x; p.r = a->r; p.y = a->y; p.partial = a->partial; p.tab = a->tab; p.step = a->step; p.scale = a->scale;
+    p.B = a->B; p.Br = a->Br; p.HW = a->HW; p.C = a->C; p.sub = a->sub;
+    return control_add_launch(p, a->dtype, s);
+}
+
 }  // namespace imh
 
 using namespace imh;
@@ -298,6 +315,7 @@ struct imh_op {
         imh_seeded_args seeded;
         imh_randn_args randn;
         imh_clip_preprocess_args clip;
+        imh_control_add_args cadd;
     } u;
 };
 
@@ -325,6 +343,7 @@ static int run_op(const imh_op& o, hipStream_t s) {
         case IMH_OP_STEP_SEEDED: return do_step_seeded(&o.u.seeded, s);
         case IMH_OP_RANDN_SEEDED: return do_randn_seeded(&o.u.randn, s);
         case IMH_OP_CLIP_PREPROCESS: return do_clip_preprocess(&o.u.clip, s);
+        case IMH_OP_CONTROL_ADD: return do_control_add(&o.u.cadd, s);
     }
     set_error("plan: unknown op kind %d", o.kind);
     return IMH_ERR_ARG;
@@ -350,6 +369,7 @@ static size_t args_size(int kind) {
         case IMH_OP_STEP_SEEDED: return sizeof(imh_seeded_args);
         case IMH_OP_RANDN_SEEDED: return sizeof(imh_randn_args);
         case IMH_OP_CLIP_PREPROCESS: return sizeof(imh_clip_preprocess_args);
+        case IMH_OP_CONTROL_ADD: return sizeof(imh_control_add_args);
     }
     return 0;
 }
@@ -443,6 +463,7 @@ int imh_elementwise(int op, const imh_ew_args* a, void* stream) { return do_ew(o
 int imh_step_seeded(const imh_seeded_args* a, void* stream) { return do_step_seeded(a, (hipStream_t)stream); }
 int imh_randn_seeded(const imh_randn_args* a, void* stream) { return do_randn_seeded(a, (hipStream_t)stream); }
 int imh_clip_preprocess(const imh_clip_preprocess_args* a, void* stream) { return do_clip_preprocess(a, (hipStream_t)stream); }
+int imh_control_add(const imh_control_add_args* a, void* stream) { return do_control_add(a, (hipStream_t)stream); }
 int imh_randn_seeded_host(const imh_randn_args* a) {
     RandnParams p;
     const int rc = to_randn(a, "imh_randn_seeded_host", &p);

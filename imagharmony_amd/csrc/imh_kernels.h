@@ -164,6 +164,17 @@ int groupnorm_stats_blocks(int HW, int C);
 int groupnorm_stats_sub(int C, int groups);
 int layernorm_launch(const NormParams& p, int dtype, hipStream_t stream);
 
+// imh_control_add (norm.hip, beside gn_stats_kernel whose statistics routine it shares): y = x + g * r[b % Br] over dense NHWC [B, HW, C],
+// g = scale * (tab ? tab[*step] : 1); partial != null: the IMH_GN_STATS partials of y (sub-runs of `sub` channels) from the same launch
+struct ControlAddParams {
+    const void* x; const void* r; void* y;
+    float* partial;
+    const float* tab; const int* step;
+    float scale;
+    int B, Br, HW, C, sub;
+};
+int control_add_launch(const ControlAddParams& p, int dtype, hipStream_t stream);
+
 // fp32 (reference-precision) kernels of the VAE decode tail (f32.hip).  op 0: GEMM / conv3x3 (X, W, Y, bias, residual; conv fields);
 // 1: GroupNorm statistics (X [B, HW, C] -> ws [B, nblk, groups, 2]); 2: table (ws, gamma, beta -> Y [B, C, 2]); 3: apply (X, ws = table -> Y);
 // 4: row softmax (X [M, ldx] -> Y [M, ldy], N columns, scale); 5: img2img initial latents (imh.h IMH_F32_IMG2IMG_INIT)

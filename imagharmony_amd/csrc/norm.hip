@@ -58,28 +58,28 @@ __device__ __forceinline__ void chan_merge(float& n, float& s, float& m2, const 
 // step 1, stand-alone: thread t < CL*P: channel chunk cl = t % CL (8 channels), pixel lane pl = t / CL; per channel a pivot-shifted
 // (sum, sum of squares) over the lane's pixels -> (n, sum, M2); thread j < C / sub then merges its sub-run's sub x P triples in a
 // FIXED order (deterministic).  partial[((b * nblk + blk) * nsub + j) * 2 + {0, 1}]; n = (pixels of the block) * sub.
-template <typename T>
-__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const NormParams p, int nblk, int sub) {
+// The routine is shared: `load(b, pix, cl)` hands over the eight values of channels [8 cl, 8 cl + 8) of pixel pix of sample b AS STORED --
+// gn_stats_kernel reads them from x, control_add_kernel computes, stores and returns them -- so the partials of the two are the same bits.
+template <typename T, typename Load>
+__device__ __forceinline__ void gn_stats_block(const int C, const int HW, const int nblk, const int sub, float* partial, float* lds, Load load) {
     typedef typename Vec<T>::v8 v8;
-    extern __shared__ float lds[];   // [P*C] sums, [P*C] M2, [P] counts
-    const int C = p.C, CL = C >> 3;
+    const int CL = C >> 3;          // lds: [P*C] sums, [P*C] M2, [P] counts
     const int P = max(1, GN_THREADS / CL);
     float* ls = lds;
     float* lm = lds + P * C;
     float* ln = lds + 2 * P * C;
     const int b = blockIdx.y, blk = blockIdx.x;
-    const int ppb = (p.HW + nblk - 1) / nblk;
-    const int start = blk * ppb, end = min(p.HW, start + ppb);
+    const int ppb = (HW + nblk - 1) / nblk;
+    const int start = blk * ppb, end = min(HW, start + ppb);
     const int t = threadIdx.x;
     if (t < CL * P) {
         const int cl = t % CL, pl = t / CL;
         float s[8], q[8], pv[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; pv[e] = 0.f; }
-        const T* x = (const T*)p.x + ((size_t)b * p.HW) * C + cl * 8;
         int cnt = 0;
         for (int pix = start + pl; pix < end; pix += P) {
-            const v8 v = *(const v8*)(x + (size_t)pix * C);
+            const v8 v = load(b, pix, cl);
             if (cnt == 0) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) pv[e] = to_f32(v[e]);
@@ -104,9 +104,78 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const NormParams p
             const float np = ln[pl];
             for (int c = j * sub; c < (j + 1) * sub; ++c) chan_merge(n, s, m2, np, ls[pl * C + c], lm[pl * C + c]);
         }
-        float* o = p.partial + (((size_t)b * nblk + blk) * nsub + j) * 2;
+        float* o = partial + (((size_t)b * nblk + blk) * nsub + j) * 2;
         o[0] = s; o[1] = m2;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const NormParams p, int nblk, int sub) {
+    typedef typename Vec<T>::v8 v8;
+    extern __shared__ float lds[];
+    const T* x = (const T*)p.x;
+    const int C = p.C, HW = p.HW;
+    gn_stats_block<T>(C, HW, nblk, sub, p.partial, lds, [&](int b, int pix, int cl) -> v8 {
+        return *(const v8*)(x + ((size_t)b * HW + pix) * C + cl * 8);
+    });
+}
+
+// imh_control_add (include/imh.h): y = round_T(x + g * r[b % Br]) over dense NHWC [B, HW, C], g = scale * (tab ? tab[*step] : 1) -- the
+// ControlNet's residual injection (diffusers UNet2DConditionModel.forward: down_block_res_sample + down_block_additional_residual, mid
+// likewise; ControlNetModel.forward: sample + controlnet_cond) with the conditioning scale and the guidance window folded into one
+// per-step table.  Product and sum are two fp32 roundings (no contraction): what torch computes.  STATS: the launch has gn_stats_kernel's
+// grid and thread layout and hands every stored v8 to gn_stats_block, so the GroupNorm partials of y cost no pass of their own.
+template <typename T, bool STATS>
+__global__ __launch_bounds__(GN_THREADS) void control_add_kernel(const ControlAddParams p, int nblk) {
+    typedef typename Vec<T>::v8 v8;
+    extern __shared__ float lds[];
+    const T* x = (const T*)p.x;
+    const T* r = (const T*)p.r;
+    T* y = (T*)p.y;
+    const int C = p.C, HW = p.HW, Br = p.Br;
+    const float g = p.tab ? __fmul_rn(p.scale, p.tab[*p.step]) : p.scale;
+    auto one = [&](int b, int pix, int cl) -> v8 {
+        const size_t off = ((size_t)b * HW + pix) * C + cl * 8;
+        const v8 xv = *(const v8*)(x + off);
+        const v8 rv = *(const v8*)(r + ((size_t)(b % Br) * HW + pix) * C + cl * 8);
+        v8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = from_f32<T>(__fadd_rn(to_f32(xv[e]), __fmul_rn(g, to_f32(rv[e]))));
+        *(v8*)(y + off) = o;
+        return o;
+    };
+    if constexpr (STATS) {
+        gn_stats_block<T>(C, HW, nblk, p.sub, p.partial, lds, one);
+    } else {
+        const int CL = C >> 3;
+        const int P = max(1, GN_THREADS / CL);
+        const int ppb = (HW + nblk - 1) / nblk;
+        const int start = blockIdx.x * ppb, end = min(HW, start + ppb);
+        const int t = threadIdx.x;
+        if (t < CL * P)
+            for (int pix = start + t / CL; pix < end; pix += P) one(blockIdx.y, pix, t % CL);
+    }
+}
+
+int control_add_launch(const ControlAddParams& p, int dtype, hipStream_t stream) {
+    if (p.C <= 0 || p.C % 8 || (p.C >> 3) > GN_THREADS || p.B <= 0 || p.B > 65535 || p.HW <= 0 || p.Br <= 0 || p.B % p.Br) {
+        set_error("control_add: unsupported B=%d Br=%d HW=%d C=%d (C a multiple of 8 up to %d, Br a divisor of B)", p.B, p.Br, p.HW, p.C, GN_THREADS * 8);
+        return IMH_ERR_SHAPE;
+    }
+    if (dtype != IMH_DT_BF16 && dtype != IMH_DT_F16) { set_error("control_add: unknown dtype %d", dtype); return IMH_ERR_DTYPE; }
+    if (p.partial && (p.sub <= 0 || p.C % p.sub)) { set_error("control_add: sub-run width %d does not divide C=%d", p.sub, p.C); return IMH_ERR_ARG; }
+    const int nblk = gn_nblk(p.HW, p.C);
+    dim3 grid(nblk, p.B);
+    if (p.partial) {
+        const int P = std::max(1, GN_THREADS / (p.C >> 3));
+        const size_t lds = (2 * (size_t)p.C * P + P) * sizeof(float);
+        if (dtype == IMH_DT_BF16) hipLaunchKernelGGL((control_add_kernel<bf16_t, true>), grid, dim3(GN_THREADS), lds, stream, p, nblk);
+        else hipLaunchKernelGGL((control_add_kernel<f16_t, true>), grid, dim3(GN_THREADS), lds, stream, p, nblk);
+    } else {
+        if (dtype == IMH_DT_BF16) hipLaunchKernelGGL((control_add_kernel<bf16_t, false>), grid, dim3(GN_THREADS), 0, stream, p, nblk);
+        else hipLaunchKernelGGL((control_add_kernel<f16_t, false>), grid, dim3(GN_THREADS), 0, stream, p, nblk);
+    }
+    return check_launch("control_add_kernel");
 }
 
 // step 2 (imh_gntable.h): one QUARTER wave per (sample, group) -- its 16 lanes stride over the group's partials of one or two sources in

@@ -225,6 +225,8 @@ class Ctx:
             rc = self.lib.imh_randn_seeded(C.byref(args), s)
         elif kind == L.OP_CLIP_PREPROCESS:
             rc = self.lib.imh_clip_preprocess(C.byref(args), s)
+        elif kind == L.OP_CONTROL_ADD:
+            rc = self.lib.imh_control_add(C.byref(args), s)
         else:
             rc = self.lib.imh_elementwise(ew_op, C.byref(args), s)
         L.check(rc, descr or f"op kind {kind}")
@@ -1042,6 +1044,44 @@ class Ctx:
         a.dtype = _DT.get(out.dtype, L.CLIP_DT_F32)
         self._emit(L.OP_CLIP_PREPROCESS, a, descr=descr, nbytes=4.0 * images.numel() + float(out.element_size()) * S * g * g * k, keep=(images, out))
         return out
+
+    def control_add(self, x, r, scale=1.0, tab=None, step=None, gn_sub=None, descr="control_add"):
+        """y = x + g * r[b % Br] (imh_control_add), g = scale * (tab[*step] if tab is given else 1): the ControlNet's gated residual
+        injection.  x [B, ..., C] and r [Br, ..., C] dense NHWC in the compute dtype over the same pixels, B % Br == 0; tab fp32 (device),
+        step the device step counter (together or not at all).  The product and the sum are separate fp32 roundings: torch's
+        (x.float() + g * r.float()).to(dtype) bit for bit.  Returns a new tensor y shaped like x (there is no in-place form); with
+        gn_sub -> (y, GnStats): the GroupNorm partials of y in sub-runs of gn_sub channels from the same launch, bit-equal to
+        gn_stats(y, gn_sub).  What the library refuses is refused here, where the launch is recorded."""
+        self._chk(x, descr + ".x"); self._chk(r, descr + ".r")
+        self._chk(tab, descr + ".tab", torch.float32); self._chk(step, descr + ".step", torch.int32)
+        if x.dim() < 2 or r.dim() != x.dim() or not x.is_contiguous() or not r.is_contiguous():
+            raise L.ImhError(f"{descr}: x {tuple(x.shape)} / r {tuple(r.shape)} must be dense NHWC tensors of one rank")
+        B, Br, Cc = int(x.shape[0]), int(r.shape[0]), int(x.shape[-1])
+        if B < 1 or Br < 1 or B % Br or tuple(r.shape[1:]) != tuple(x.shape[1:]) or x.numel() == 0:
+            raise L.ImhError(f"{descr}: r {tuple(r.shape)} does not serve x {tuple(x.shape)} (same pixels and channels, a batch that divides B)")
+        HW = x.numel() // (B * Cc)
+        if Cc % 8 or Cc > 4096 or B > 65535:
+            raise L.ImhError(f"{descr}: C={Cc} must be a multiple of 8 up to 4096 (B={B} up to 65535)")
+        if (tab is None) != (step is None):
+            raise L.ImhError(f"{descr}: tab and step come together")
+        if gn_sub is not None and (int(gn_sub) < 1 or Cc % int(gn_sub)):
+            raise L.ImhError(f"{descr}: sub-run width {gn_sub} does not divide C={Cc}")
+        if not self.dry and (x.data_ptr() | r.data_ptr()) & 15:
+            raise L.ImhError(f"{descr}: x and r must be 16-byte aligned")
+        y = self.new(*x.shape)
+        gs = None
+        a = L.ControlAddArgs()
+        a.x, a.r, a.y, a.tab, a.step = x.data_ptr(), r.data_ptr(), y.data_ptr(), self._p(tab), self._p(step)
+        a.scale, a.B, a.Br, a.HW, a.C, a.dtype = float(scale), B, Br, HW, Cc, self.dt
+        if gn_sub is not None:
+            nblk = self.lib.imh_groupnorm_stats_blocks(HW, Cc)
+            t = self.new(B, nblk, Cc // int(gn_sub), 2, dtype=torch.float32)
+            a.partial, a.sub = t.data_ptr(), int(gn_sub)
+            gs = GnStats(t, nblk, int(gn_sub), 0, Cc)
+        es = x.element_size()
+        self._emit(L.OP_CONTROL_ADD, a, descr=descr, flops=2.0 * x.numel(), nbytes=float(es) * (2 * x.numel() + r.numel()),
+                   keep=(x, r, y, tab, step) + ((gs.t,) if gs else ()), shape=(B, HW, Cc, Br), epi=dict(tab=tab is not None, gn_sub=gn_sub))
+        return (y, gs) if gn_sub is not None else y
 
     def gather_rows(self, table, idx, add=None, out=None, descr="gather_rows"):
         """out[r] = table[idx[r]] (+ add[r % P]) (IMH_EW_GATHER_ROWS): table [rows, C] and add [P, C] row-major in the compute dtype, idx

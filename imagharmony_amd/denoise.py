@@ -48,6 +48,64 @@ class DenoiseEngine:
         self.stochastic = False  # ... and reads a noise row per step
         self.seeded = False      # ... which the step generates from st.seed_rows instead of reading a bank (set_schedule(seeded_noise=True))
 
+    # the ControlNet state (class-level defaults: an engine without one carries nothing)
+    controlnet = None        # a controlnet.ControlNetModel whose branch is recorded in front of the UNet (set_controlnet)
+    cn = None                # its state: dict(image, scale, hint, cond = StepState with its aug_emb / K,V caches) (set_control_image)
+    cn_scale_tab = None      # fp32 [steps] conditioning_scale * keep(i) of the current schedule (set_schedule)
+
+    # -- ControlNet (opt-in; an engine without one records, launches and returns what it always did) --
+    def set_controlnet(self, controlnet):
+        """controlnet: an imagharmony_amd.controlnet.ControlNetModel on the engine's device, or None to switch the branch off.  The next
+        set_schedule picks (or records) the plan of that mode: the plans with and without the branch of one schedule coexist."""
+        if controlnet is not None:
+            if isinstance(controlnet, (list, tuple)) or hasattr(controlnet, "nets"):
+                raise NotImplementedError("several ControlNets (MultiControlNetModel) are not supported: one ControlNetModel")
+            if not hasattr(controlnet, "controlnet_down_blocks") or not hasattr(controlnet, "prepare_hint"):
+                raise TypeError(f"set_controlnet takes an imagharmony_amd.controlnet.ControlNetModel, not {type(controlnet).__name__}")
+            if getattr(self, "cfg_role", None) is not None:
+                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+        if controlnet is not self.controlnet:
+            if self.controlnet is not None and controlnet is not None:
+                self.cn, self._plans = None, {}          # another model: its caches and every plan recorded with the old one go
+            self.plan, self._sched_key = None, None
+        self.controlnet = controlnet
+
+    @torch.no_grad()
+    def set_control_image(self, image, conditioning_scale=1.0):
+        """The per-image state of the ControlNet branch, computed once, outside the step: the hint controlnet_cond_embedding(image)
+        (NHWC [Sh, H/8, W/8, C0], Sh = 1 or S: one control image may serve every stacked sample) and -- here or at the next
+        set_conditioning, whichever comes later -- the ControlNet's aug_emb and the text-only K / V^T caches of its cross-attention
+        layers.  image: float [1 | S, 3, height, width] in [0, 1].  conditioning_scale enters the per-schedule gate table, so
+        set_schedule follows this call."""
+        if self.controlnet is None:
+            raise L.ImhError("set_control_image needs a ControlNet: set_controlnet first")
+        self.cn = dict(image=image, scale=float(conditioning_scale), hint=None, cond=None)
+        self._plans = {k: v for k, v in self._plans.items() if k[9] is None}      # a plan recorded with the branch points at the previous hint
+        self.plan, self._sched_key = None, None
+        if self.st is not None and getattr(self, "_cond_in", None) is not None:
+            self._prepare_control()
+
+    def _prepare_control(self):
+        cn, net = self.cn, self.controlnet
+        if getattr(self, "cfg_role", None) is not None:
+            raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+        img = cn["image"]
+        if img.dim() != 4 or img.shape[0] not in (1, self.S):
+            raise L.ImhError(f"control image {tuple(img.shape)}: one image or one per sample ({self.S}) as [n, 3, H, W]")
+        ctx = Ctx(self.device, self.dtype)       # fresh context: the hint and the caches must outlive pooled buffers
+        cn["hint"] = net.prepare_hint(ctx, img, self.H, self.W)
+        ehs, text, ids = self._cond_in
+        cn["cond"] = net.prepare_conditioning(ctx, ehs, text, ids)
+        cn["ctx"] = ctx
+
+    @staticmethod
+    def gate_table(n, t_start, start, end, value):
+        """[n] floats: `value` where the window keeps step i of the m = n - t_start steps that run (custom_pipelines.py:319-329;
+        diffusers controlnet_keep: 1 - (i / m < start or (i + 1) / m > end)), 0 where it does not, at rows t_start + i; rows before
+        t_start (never read) hold `value`"""
+        m = n - t_start
+        return [float(value)] * t_start + [0.0 if (i / m < start) or ((i + 1) / m > end) else float(value) for i in range(m)]
+
     # -- conditioning (once per image / per PNS run; shared by every candidate seed) --
     @torch.no_grad()
     def set_conditioning(self, prompt_embeds, negative_prompt_embeds, pooled, negative_pooled, height, width,
@@ -61,6 +119,8 @@ class DenoiseEngine:
         the serial tail of the two-stage PNS schedule)."""
         if cfg_role not in (None, 0, 1):
             raise ValueError("cfg_role must be None, 0 (unconditional half) or 1 (conditional half)")
+        if cfg_role is not None and self.controlnet is not None:
+            raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
         if cfg_role != getattr(self, "cfg_role", None):
             self.plan = None
         self._plans = {}                          # every recorded plan points into the previous conditioning's caches
@@ -92,6 +152,11 @@ class DenoiseEngine:
             for k in ("latents", "t_table", "step", "in_scale_tab", "ip_scale_tab", "coef_tab", "blend_tab") + self._GENERAL_STEP + self._INPAINT_BUFFERS:
                 setattr(st, k, getattr(old, k, None))
         self.plan = None                         # conditioning buffers changed -> re-record
+        self._cond_in = (ehs, text, ids)
+        if self.cn is not None:
+            self.cn["hint"] = self.cn["cond"] = None      # the ControlNet's caches belong to the previous conditioning (and size)
+            if self.controlnet is not None:
+                self._prepare_control()
         return st
 
     # inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
@@ -102,7 +167,8 @@ class DenoiseEngine:
 
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
-                     denoising_end=None, t_start=0, inpaint=False, seeded_noise=False):
+                     denoising_end=None, t_start=0, inpaint=False, seeded_noise=False, controlnet_guidance_start=0.0,
+                     controlnet_guidance_end=1.0):
         """inpaint: the schedule of an inpainting call (prepare_inpaint).  On a 4-channel UNet every step then ends with upstream's masked
         blend, latents = (1 - m) * add_noise(z, n, timesteps[i + 1]) + m * latents, whose add_noise pair comes from blend_tab: row r holds
         scheduler.add_noise_coefficients(r + 1), the last row that runs (1, 0) -- the image latents themselves.  On a 9-channel UNet there is
@@ -148,8 +214,7 @@ class DenoiseEngine:
         m = n - t_start                                                      # steps that run: table rows t_start .. n - 1
         # custom_pipelines.py:319-329 over the m steps that run, at rows t_start + i; the rows before t_start are never read (base
         # there, so that a text-to-image and an image-to-image call with the same window share one gating table and plan)
-        gate = [float(base)] * t_start + [0.0 if (i / m < control_guidance_start) or ((i + 1) / m > control_guidance_end) else float(base)
-                                          for i in range(m)]
+        gate = self.gate_table(n, t_start, control_guidance_start, control_guidance_end, base)
         # the gating table is part of what the recorded plan reads: its fingerprint is part of the key
         fp.update(torch.tensor(gate, dtype=torch.float32).numpy().tobytes())
         mode = None
@@ -157,7 +222,13 @@ class DenoiseEngine:
             mode = "concat" if self.unet.config.in_channels == 9 else "blend"
         stochastic = general and bool(getattr(scheduler, "stochastic", False))
         seeded = bool(seeded_noise) and stochastic
-        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), mode, seeded)
+        cn_gate = cn_key = None
+        if self.controlnet is not None:
+            if self.cn is None:
+                raise L.ImhError("a ControlNet is set but no control image: set_control_image before set_schedule")
+            cn_gate = self.gate_table(n, t_start, controlnet_guidance_start, controlnet_guidance_end, self.cn["scale"])
+            cn_key = hashlib.sha1(torch.tensor(cn_gate, dtype=torch.float32).numpy().tobytes()).hexdigest()
+        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), cn_key, mode, seeded)
         self.t_start = t_start
         self.inpaint = mode
         self.general = general
@@ -172,6 +243,7 @@ class DenoiseEngine:
             self.steps, self.init_noise_sigma = hit["steps"], hit["init_noise_sigma"]
             self.plan, self.noise_pred, self._temb_ctx = hit["plan"], hit["noise_pred"], hit["temb_ctx"]
             self.plan_tail, self.np_full = hit.get("plan_tail"), hit.get("np_full")
+            self.cn_scale_tab, self._cn_temb = hit.get("cn_scale_tab"), hit.get("cn_temb")
             self._sched_key = key
             return
         st.t_table = tab["timesteps"].to(dev)
@@ -190,6 +262,7 @@ class DenoiseEngine:
         st.in_scale_tab = tab["in_scale"].to(dev) if tab["in_scale"] is not None else None
         st.ip_scale_tab = torch.tensor(gate, dtype=torch.float32, device=dev)
         st.blend_tab = self.blend_table(scheduler, num_inference_steps, n).to(dev) if mode == "blend" else None
+        self.cn_scale_tab = torch.tensor(cn_gate, dtype=torch.float32, device=dev) if cn_gate is not None else None
         if st.step is None:
             st.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.steps = n
@@ -216,6 +289,7 @@ class DenoiseEngine:
                   "xcd_candidates", "xcd_cells", "t_start", "inpaint"):
             setattr(e, k, getattr(self, k))
         e.general, e.stochastic, e.seeded = self.general, self.stochastic, self.seeded
+        e.controlnet, e.cn, e.cn_scale_tab = self.controlnet, self.cn, self.cn_scale_tab      # shared, read-only during denoising: hint, caches, table
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
@@ -245,6 +319,18 @@ class DenoiseEngine:
         # the time-embedding rows of every step of this schedule under this conditioning: once here, not five launches per step
         self._temb_ctx = Ctx(self.device, self.dtype)          # (its pool owns the table for the life of the plan)
         self.unet.precompute_temb(self._temb_ctx, st, st.t_table)
+        cst = None
+        if self.controlnet is not None:
+            if split:
+                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+            if self.inpaint or self.unet.config.in_channels != 4:
+                raise NotImplementedError("the ControlNet branch runs text-to-image schedules (no inpainting mode)")
+            if self.cn is None or self.cn.get("hint") is None or self.cn.get("cond") is None or self.cn_scale_tab is None:
+                raise L.ImhError("the ControlNet branch needs set_conditioning, set_control_image and then set_schedule")
+            from .controlnet import control_state
+            cst = control_state(st, self.cn["cond"])       # the UNet's latents / counter / tables, the ControlNet's conditioning
+            self.controlnet.precompute_temb(self._temb_ctx, cst, st.t_table)
+            self._cn_temb = cst.temb_table
         if not split and self.use_graph and len(self.xcd_candidates) > 1 and self.xcd_cells is None:
             pk = (self.device.index or 0, self.S, self.H, self.W, str(self.dtype), bool(self.do_cfg))
             if pk not in _XCD_PICK and not self._is_fork:
@@ -254,7 +340,12 @@ class DenoiseEngine:
                 self.xcd_times_ms = _XCD_PICK[pk][1]
         rec = Ctx(self.device, self.dtype, record=True)
         rec.xcd_cells = self.xcd_cells or 0
-        out = self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg and not split)
+        control = None
+        if cst is not None:
+            # the ControlNet branch, then the UNet that consumes its residuals, in ONE plan on one stream: a linear capture
+            control = self.controlnet.emit_forward(rec, cst, self.S, self.H, self.W, cfg_dup=self.do_cfg, hint=self.cn["hint"],
+                                                   tab=self.cn_scale_tab)
+        out = self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg and not split, **({"control": control} if control is not None else {}))
         if split:
             # this rank's half of the noise prediction ends the forward plan; the CFG combine + scheduler step + step counter are a
             # second tiny plan over BOTH halves ([uncond | cond] = the layout the fused step reads), run after the per-step exchange
@@ -318,7 +409,8 @@ class DenoiseEngine:
         self._plans[self._sched_key] = dict(
             st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + self._GENERAL_STEP},
             steps=self.steps, init_noise_sigma=self.init_noise_sigma, plan=self.plan, noise_pred=self.noise_pred,
-            temb_ctx=self._temb_ctx, plan_tail=getattr(self, "plan_tail", None), np_full=getattr(self, "np_full", None))
+            temb_ctx=self._temb_ctx, plan_tail=getattr(self, "plan_tail", None), np_full=getattr(self, "np_full", None),
+            cn_scale_tab=self.cn_scale_tab, cn_temb=getattr(self, "_cn_temb", None))
         while len(self._plans) > self.max_cached_plans:              # (each plan keeps ~2 GB of activation buffers alive at 1024^2)
             self._plans.pop(next(iter(self._plans)))
 

@@ -19,6 +19,7 @@ GF_GEGLU, GF_ACT_GELU, GF_ACT_SILU, GF_VT_PERM, GF_OUT_F32, GF_LN_ROW, GF_LN_COL
 OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL, OP_XATTN, OP_ATTN_ENC, OP_ATTN_ENC_CAUSAL = range(10)
 OP_STEP_SEEDED, OP_RANDN_SEEDED = 10, 11      # the seeded step noise (imh.h): additive plan kinds
 OP_CLIP_PREPROCESS = 13                       # imh_clip_preprocess (imh.h: kind 12 stays refused)
+OP_CONTROL_ADD = 15                           # imh_control_add: the ControlNet's gated residual add (+ GroupNorm partials of the sum); 12 and 14 stay refused
 CLIP_DT_F32 = 2                               # imh_clip_preprocess's fp32 rows (no other entry takes it)
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
@@ -119,6 +120,11 @@ class ClipPreprocessArgs(C.Structure):
                 ("std0", _f32), ("std1", _f32), ("std2", _f32), ("dtype", _i32)]
 
 
+class ControlAddArgs(C.Structure):
+    _fields_ = [("x", _vp), ("r", _vp), ("y", _vp), ("partial", _vp), ("tab", _vp), ("step", _vp), ("scale", _f32),
+                ("B", _i32), ("Br", _i32), ("HW", _i32), ("C", _i32), ("sub", _i32), ("dtype", _i32)]
+
+
 class F32Args(C.Structure):
     _fields_ = [("X", _vp), ("W", _vp), ("Y", _vp), ("bias", _vp), ("residual", _vp), ("gamma", _vp), ("beta", _vp), ("ws", _vp),
                 ("M", _i32), ("N", _i32), ("K", _i32), ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32),
@@ -158,6 +164,7 @@ SYMBOLS = [
     ("imh_randn_seeded", C.c_int, [C.POINTER(RandnArgs), _vp]),
     ("imh_randn_seeded_host", C.c_int, [C.POINTER(RandnArgs)]),
     ("imh_clip_preprocess", C.c_int, [C.POINTER(ClipPreprocessArgs), _vp]),
+    ("imh_control_add", C.c_int, [C.POINTER(ControlAddArgs), _vp]),
     ("imh_f32", C.c_int, [C.c_int, C.POINTER(F32Args), _vp]),
     ("imh_plan_create", _vp, []),
     ("imh_plan_destroy", None, [_vp]),

@@ -365,3 +365,109 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
         out = eng.denoise(None, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
         out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+
+
+def prepare_control_image(image, height, width):
+    """diffusers StableDiffusionXLControlNetPipeline.prepare_image with VaeImageProcessor(do_normalize=False): a PIL image (or a list of
+    them) or a float tensor [n, 3, H, W] / [3, H, W] in [0, 1] -> float32 [n, 3, height, width] in [0, 1], resized when the size
+    differs (PIL: Lanczos, upstream's default resample; tensors: bilinear), NOT normalised to [-1, 1]"""
+    if torch.is_tensor(image):
+        img = image.detach().to("cpu", torch.float32)
+        if img.dim() == 3:
+            img = img[None]
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"control image tensor {tuple(image.shape)}: expected [n, 3, H, W] in [0, 1]")
+        if tuple(img.shape[2:]) != (height, width):
+            img = torch.nn.functional.interpolate(img, size=(height, width), mode="bilinear", align_corners=False)
+        return img.contiguous()
+    import numpy as np
+    from PIL import Image
+    imgs = list(image) if isinstance(image, (list, tuple)) else [image]
+    out = []
+    for im in imgs:
+        if not isinstance(im, Image.Image):
+            raise ValueError(f"control image of type {type(im).__name__}: a PIL image, a list of PIL images or a float tensor")
+        im = im.convert("RGB")
+        if im.size != (width, height):
+            im = im.resize((width, height), resample=Image.LANCZOS)
+        out.append(torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0).permute(2, 0, 1))
+    return torch.stack(out, 0).contiguous()
+
+
+class StableDiffusionXLControlNetCustomPipeline(StableDiffusionXLCustomPipeline):
+    """Text-to-image under a ControlNet, with diffusers' ``StableDiffusionXLControlNetPipeline`` call surface (0.30) for what this path
+    builds: one ``controlnet.ControlNetModel``, one control image (or one per sample), ``controlnet_conditioning_scale`` and a guidance
+    window.  The pipe exposes ``.controlnet``, so ``IPAdapterXL(pipe, ...)`` installs ``CNAttnProcessor2_0`` on it (ip_adapter/ip_adapter.py:
+    126-133) and ``IPAdapterXL.generate(..., image=, controlnet_conditioning_scale=)`` reaches ``__call__`` through its **kwargs.
+
+    Naming: upstream's ControlNet pipelines call their window ``control_guidance_start / _end``; the reference's custom pipeline uses those
+    names for the IP-scale window (custom_pipelines.py:326-329) and they keep that meaning here.  The ControlNet's window is
+    ``controlnet_guidance_start / controlnet_guidance_end``.
+
+    Not built: ``guess_mode``, several ControlNets (``MultiControlNetModel`` / a list), ControlNet variants of the image-to-image and
+    inpainting pipelines (NotImplementedError)."""
+
+    def __init__(self, unet, controlnet, scheduler=None, device="cuda:0", dtype=torch.bfloat16, **kw):
+        if isinstance(controlnet, (list, tuple)) or hasattr(controlnet, "nets"):
+            raise NotImplementedError("several ControlNets (MultiControlNetModel) are not supported: pass one ControlNetModel")
+        super().__init__(unet, scheduler=scheduler, device=device, dtype=dtype, **kw)
+        self.controlnet = controlnet
+        self.engine.set_controlnet(controlnet)
+
+    def to(self, device):
+        super().to(device)
+        self.controlnet.to(self.device)
+        self.engine.set_controlnet(self.controlnet)
+        return self
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, height=None, width=None, num_inference_steps: int = 50, guidance_scale: float = 5.0,
+                 negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents=None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
+                 controlnet_guidance_start: float = 0.0, controlnet_guidance_end: float = 1.0,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+                 callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
+                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator", **kwargs):
+        """image: the control image -- PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1] -- resized to (height, width),
+        not normalised; one image serves every sample.  Everything else as StableDiffusionXLCustomPipeline.__call__.
+        Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no image, a window outside 0 <= start <= end <= 1
+        (ValueError)."""
+        if guess_mode:
+            raise NotImplementedError("guess_mode is not supported on this path")
+        if isinstance(controlnet_conditioning_scale, (list, tuple)):
+            raise NotImplementedError("a list of conditioning scales belongs to MultiControlNetModel, which is not supported")
+        if image is None:
+            raise ValueError("the ControlNet pipeline needs `image`: the control image (PIL or a float tensor [n, 3, H, W] in [0, 1])")
+        if not 0.0 <= float(controlnet_guidance_start) <= float(controlnet_guidance_end) <= 1.0:
+            raise ValueError(f"controlnet guidance window [{controlnet_guidance_start}, {controlnet_guidance_end}] must satisfy 0 <= start <= end <= 1")
+        self._refuse(output_type, eta, kwargs)
+        seed_tab = self.step_seed_table(step_noise, generator, None)
+        height = height or self.default_sample_size * self.vae_scale_factor
+        width = width or self.default_sample_size * self.vae_scale_factor
+        cond = prepare_control_image(image, height, width)
+        if prompt_embeds is None:
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
+                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
+        if pooled_prompt_embeds is None:
+            raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
+        S = prompt_embeds.shape[0]
+        if cond.shape[0] not in (1, S):
+            raise ValueError(f"{cond.shape[0]} control images for {S} samples: one image, or one per sample")
+        eng = self.engine
+        eng.set_controlnet(self.controlnet)
+        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
+                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
+                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
+        eng.set_control_image(cond, conditioning_scale=float(controlnet_conditioning_scale))
+        seed_tab = self.step_seed_table(step_noise, generator, S)
+        eng.set_schedule(self.scheduler, num_inference_steps, control_guidance_start, control_guidance_end,
+                         denoising_end=denoising_end, controlnet_guidance_start=float(controlnet_guidance_start),
+                         controlnet_guidance_end=float(controlnet_guidance_end), **({"seeded_noise": True} if seed_tab else {}))
+        if latents is None:
+            latents = randn_latents((S, 4, height // 8, width // 8), generator)
+        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
+        out = self._output(out, output_type)
+        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import AttnProcessor2_0, IPAttnProcessor2_0, _b, _vkey, _w
+from .attention_processor import AttnProcessor2_0, CNAttnProcessor2_0, IPAttnProcessor2_0, _b, _vkey, _w
 from .ctx import Ctx, GnSpec
 
 
@@ -60,6 +60,11 @@ GN_FUSE = os.environ.get("IMH_GN_FUSE", "1") != "0"
 # IMH_GN_TABLE_APPLY; csrc/imh_gntable.h: the same routine as the table launch, bit-identical).  False = one table launch per
 # GroupNorm (A/B; IMH_GN_TABLE_FOLD=0).
 GN_TABLE_FOLD = os.environ.get("IMH_GN_TABLE_FOLD", "1") != "0"
+
+
+# a ControlNet carries ONE CNAttnProcessor2_0 object on all its layers (ip_adapter/ip_adapter.py:126-133): on attn1 it is plain
+# self-attention, which this processor records (no parameters, no state); on attn2 it is IPAttnProcessor2_0(skip=True) by its own emit
+_SELF_ATTN = AttnProcessor2_0()
 
 
 class Feat:
@@ -271,14 +276,17 @@ class BasicTransformerBlock(nn.Module):
         self.ff = FeedForward(dim)
 
     def fused(self, L_):
-        """the folded-LayerNorm form applies (both processors are the HIP ones, 64-aligned token count)"""
-        return FOLD_LAYERNORM and isinstance(self.attn1.processor, AttnProcessor2_0) \
-            and isinstance(self.attn2.processor, IPAttnProcessor2_0) and L_ % 64 == 0
+        """the folded-LayerNorm form applies (both processors are the HIP ones -- a ControlNet's CNAttnProcessor2_0 on both layers
+        included --, 64-aligned token count)"""
+        return FOLD_LAYERNORM and isinstance(self.attn1.processor, (AttnProcessor2_0, CNAttnProcessor2_0)) \
+            and isinstance(self.attn2.processor, (IPAttnProcessor2_0, CNAttnProcessor2_0)) and L_ % 64 == 0
 
     def emit(self, ctx, h, B, L_, kv, st, stats=None, want_stats=False):
         """h: the residual stream [B*L, C] (consumed).  stats = row statistics of h from the GEMM that wrote it (or None);
         want_stats: return (h3, statistics of h3) for the next block's norm1."""
         p1, p2 = self.attn1.processor, self.attn2.processor
+        if isinstance(p1, CNAttnProcessor2_0):
+            p1 = _SELF_ATTN
         if not hasattr(p1, "emit") or not hasattr(p2, "emit"):
             raise L.ImhError("a non-HIP attention processor is installed; the fused forward needs "
                              "imagharmony_amd.attention_processor processors")
@@ -717,21 +725,9 @@ class UNet2DConditionModel(nn.Module):
             ctx.keep.extend([ids, add_in, ehs])
         return st
 
-    # ---- the forward, as emitted ops ----
-    def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True):
-        """Records one UNet forward.  Reads st.latents (fp32 NCHW [S,4,Hl,Wl]); batch B = 2S when
-        cfg_dup (CFG halves share the latent, custom_pipelines.py:332).  Returns the noise prediction
-        as NHWC [B, Hl*Wl, 4] in the compute dtype."""
-        cfg = self.config
-        B = 2 * S if cfg_dup else S
-        boc = cfg.block_out_channels
-        div = 1 << (len(boc) - 1)
-        if Hl % div or Wl % div:
-            # diffusers interpolates the up path to the skip's size in that case (forward_upsample_size); the
-            # fused nearest-x2 upsampling here does not, so refuse instead of producing misaligned skips
-            raise L.ImhError(f"latent {Hl}x{Wl}: sides must be multiples of {div} (image sides multiples of {8 * div})")
-        # -- time embedding (SURVEY.md Appendix A.1) --
-        ctx.tag = 1
+    def _emit_time_embedding(self, ctx, st, B):
+        """st.temb_all = the stacked time_emb_proj rows of this step (shared with ControlNetModel, whose encoder has the same chain)"""
+        boc = self.config.block_out_channels
         if st.temb_table is not None and st.t_table is not None and st.temb_table.shape[1] == B * self.temb_total:
             # the chain below depends on the step and the conditioning only, not on the latent: all steps' rows were computed once
             # per schedule (precompute_temb); the step's row is copied in (one launch instead of five)
@@ -746,6 +742,27 @@ class UNet2DConditionModel(nn.Module):
                 ctx.ew(L.EW_TIMESTEP, tsin, a=st.t_value, n=B, i=(boc[0], 0, 0, 0, 0, 0), descr="time_proj")
             st.temb_all = self._temb_chain(ctx, tsin, st.aug_emb)
             ctx.free(tsin)
+
+    # ---- the forward, as emitted ops ----
+    def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None):
+        """Records one UNet forward.  Reads st.latents (fp32 NCHW [S,4,Hl,Wl]); batch B = 2S when
+        cfg_dup (CFG halves share the latent, custom_pipelines.py:332).  Returns the noise prediction
+        as NHWC [B, Hl*Wl, 4] in the compute dtype.
+        control: a controlnet.ControlResiduals (diffusers down_block_additional_residuals / mid_block_additional_residual): after the
+        mid block and before the up path every skip and the mid output are replaced by x + g * r (Ctx.control_add, whose partials
+        take the place of the superseded tensor's); the down path and the mid block have read the unmodified tensors, as upstream.
+        The residuals are consumed.  None: the launch list is what it is without the argument."""
+        cfg = self.config
+        B = 2 * S if cfg_dup else S
+        boc = cfg.block_out_channels
+        div = 1 << (len(boc) - 1)
+        if Hl % div or Wl % div:
+            # diffusers interpolates the up path to the skip's size in that case (forward_upsample_size); the
+            # fused nearest-x2 upsampling here does not, so refuse instead of producing misaligned skips
+            raise L.ImhError(f"latent {Hl}x{Wl}: sides must be multiples of {div} (image sides multiples of {8 * div})")
+        # -- time embedding (SURVEY.md Appendix A.1) --
+        ctx.tag = 1
+        self._emit_time_embedding(ctx, st, B)
         # -- conv_in (+ CFG duplication + scale_model_input) --
         ctx.tag = 2
         x = ctx.new(B, Hl, Wl, boc[0])
@@ -789,6 +806,19 @@ class UNet2DConditionModel(nn.Module):
         h = mb.attentions[0].emit(ctx, h, kv_of(mb.attentions[0]), st)
         ctx.tag = 30
         h = mb.resnets[1].emit(ctx, h, st)
+        if control is not None:
+            ctx.tag = 32
+            if len(control.down) != len(skips):
+                raise L.ImhError(f"{len(control.down)} ControlNet residuals for {len(skips)} skip connections")
+            inject = lambda f, r, descr: Feat(*ctx.control_add(f.t, r.view(r.shape[0], *f.t.shape[1:]), scale=control.scale, tab=control.tab, step=control.step,
+                                                               gn_sub=math.gcd(f.t.shape[-1] // cfg.norm_num_groups, 10), descr=descr))
+            for i, r in enumerate(control.down):
+                f = skips[i]
+                skips[i] = inject(f, r, "control.skip")
+                f.free(ctx); ctx.free(r)
+            f = h
+            h = inject(f, control.mid, "control.mid")
+            f.free(ctx); ctx.free(control.mid)
         # -- up --
         for bi, blk in enumerate(self.up_blocks):
             for i, r in enumerate(blk.resnets):
@@ -852,6 +882,14 @@ class UNet2DConditionModel(nn.Module):
         st.latents = sample[:, :4].to(torch.float32).contiguous()
         if sample.shape[1] == 9:                 # the inpainting UNet's [latents | mask | masked-image latents]
             st.conv_in_extra = sample[:, 4:].to(torch.float32).contiguous()
-        out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False)
+        control = None
+        down_res, mid_res = kw.pop("down_block_additional_residuals", None), kw.pop("mid_block_additional_residual", None)
+        if (down_res is None) != (mid_res is None):
+            raise NotImplementedError("ControlNet residuals come as the pair down_block_additional_residuals + mid_block_additional_residual")
+        if down_res is not None:                 # NCHW, already scaled (diffusers ControlNetModel.forward's outputs)
+            from .controlnet import ControlResiduals
+            nhwc = lambda t: t.to(device=dev, dtype=dtype).permute(0, 2, 3, 1).contiguous()
+            control = ControlResiduals([nhwc(t) for t in down_res], nhwc(mid_res))
+        out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, control=control)
         y = out.view(B, Hl, Wl, -1).permute(0, 3, 1, 2).to(sample.dtype)
         return (y,)

@@ -45,7 +45,8 @@ extern "C" {
  * and for the two query entries of the dispatch contract, imh_conv_halo_lds_bytes and imh_gemm_check, and for the seeded step noise:
  * three entries (imh_step_seeded, imh_randn_seeded, imh_randn_seeded_host) with argument structs of their own and two plan kinds
  * (IMH_OP_STEP_SEEDED = 10, IMH_OP_RANDN_SEEDED = 11); enum imh_ew_op and imh_ew_args are as they were.  And for the image op of the PNS
- * judge: one entry (imh_clip_preprocess) with an argument struct of its own and one plan kind (IMH_OP_CLIP_PREPROCESS = 13). */
+ * judge: one entry (imh_clip_preprocess) with an argument struct of its own and one plan kind (IMH_OP_CLIP_PREPROCESS = 13).  And for the
+ * ControlNet's gated residual add: one entry (imh_control_add), an argument struct of its own, one plan kind (IMH_OP_CONTROL_ADD = 15; 12 and 14 stay refused). */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
@@ -567,6 +568,39 @@ typedef struct imh_clip_preprocess_args {
     int32_t dtype;
 } imh_clip_preprocess_args;
 int imh_clip_preprocess(const imh_clip_preprocess_args* a, void* stream);
+
+/* ---- gated residual add with GroupNorm partials: the ControlNet's injections ------------------------------------------------------------
+ * y[b, p, c] = round_T( x[b, p, c] + g * r[b % Br, p, c] ),   g = scale * (tab ? tab[*step] : 1)
+ * over dense NHWC [B, HW, C] in bf16 / fp16: diffusers UNet2DConditionModel.forward's `down_block_res_sample + down_block_additional_residual`
+ * (nine skips) and `sample + mid_block_additional_residual`, with ControlNetModel.forward's `sample * conditioning_scale` and the pipeline's
+ * controlnet_keep window folded into the per-schedule table `tab` (fp32, indexed by the device step counter); and ControlNetModel.forward's
+ * `sample + controlnet_cond` behind conv_in (Br = 1: one hint for every sample; g = 1).  B % Br == 0; C % 8 == 0, C <= 4096 (16-byte accesses;
+ * x, r, y 16-byte aligned).  g * r and the sum are two separate fp32 operations, never contracted, so torch's
+ * (x.float() + g * r.float()).to(T) gives the same bits; with g == 0 and finite r, y == x (a -0 in x becomes +0, as IEEE addition has it).
+ * partial != NULL: the same launch writes the GroupNorm partials of y AS STORED in the IMH_GN_STATS format,
+ * partial[B][imh_groupnorm_stats_blocks(HW, C)][C / sub][2] (ragged blocks: npart = 0), by the statistics routine of IMH_GN_STATS itself
+ * (csrc/norm.hip gn_stats_block: same accumulation, same merge order) -- bit-equal to imh_groupnorm(IMH_GN_STATS) run over y, without
+ * the pass.  sub must divide C.  No atomics: the same bits eagerly, from a plan and from a replayed graph.
+ * Refused without a launch: null x / r / y, misaligned pointers, tab without step or step without tab, y overlapping x or r -- there is no
+ * in-place form: the down path and the mid block of the UNet have read x -- (IMH_ERR_ARG); a non-positive extent, C % 8, C > 4096,
+ * B % Br, B > 65535 (IMH_ERR_SHAPE); another dtype (IMH_ERR_DTYPE).
+ * In a plan: kind IMH_OP_CONTROL_ADD = 15, a #define like kind 13: enum imh_op_kind is as it was, and kinds 12 and 14 stay refused (callers and
+ * tests written against the first version 13 hold imh_plan_add to refusing both, so 15 is the next number that is free).
+ * Memory: reads the B * HW * C elements of x, the Br * HW * C elements of r, *step and tab[*step]; writes the B * HW * C elements of y and,
+ * when asked, the B * blocks * (C / sub) * 2 floats of partial.  Nothing else. */
+#define IMH_OP_CONTROL_ADD 15
+typedef struct imh_control_add_args {
+    const void* x;
+    const void* r;
+    void* y;
+    float* partial;          /* optional: the IMH_GN_STATS partials of y */
+    const float* tab;        /* optional per-step gate table, indexed by *step (with step) */
+    const int32_t* step;
+    float scale;
+    int32_t B, Br, HW, C, sub;
+    int32_t dtype;
+} imh_control_add_args;
+int imh_control_add(const imh_control_add_args* a, void* stream);
 
 /* ---- fp32 (reference-precision) kernels for the VAE decode tail -------------------------------
  * ip_adapter/custom_pipelines.py:365-377 upcasts the SDXL VAE to fp32 before `vae.decode` (it overflows in fp16): this entry keeps
