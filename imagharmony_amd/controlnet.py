@@ -19,15 +19,10 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import _b, _vkey, _w
-from .unet import (Conv2d, DownBlock, Feat, MidBlock, StepState, TimestepEmbedding, UNet2DConditionModel, UNetConfig,
-                   GN_STATS_HANDOVER)
+from .attention_processor import _b, _w
+from .unet import Conv2d, DownBlock, Feat, MidBlock, StepState, TimestepEmbedding, UNet2DConditionModel, UNetConfig
 
 COND_CHANNELS = (16, 32, 96, 256)       # diffusers conditioning_embedding_out_channels (every published SDXL ControlNet)
-
-
-def _pad64(n):
-    return (n + 63) // 64 * 64
 
 
 class ControlResiduals:
@@ -49,26 +44,6 @@ class ControlNetConditioningEmbedding(nn.Module):
             blocks.append(Conv2d(channels[i], channels[i + 1], 3))           # stride 2
         self.blocks = nn.ModuleList(blocks)
         self.conv_out = Conv2d(channels[-1], c0, 3)
-
-
-def _padded(conv, ctx, pad_out=True):
-    """[Cout, Cin, 3, 3] -> packed [Cout', 9 * Cin'] with Cin' (and Cout' unless pad_out is False) zero-padded to a multiple of 64, and
-    the bias padded alike: the padded output channels are exact zeros, silu(0) = 0, so the chain stays what the unpadded convs give
-    (vae._pad_conv_in is the precedent)"""
-    key = (_vkey(conv.weight, conv.bias), ctx.dtype, str(ctx.device), pad_out)
-    c = getattr(conv, "_imh_padded", None)
-    if c is None or c[0] != key:
-        w = conv.weight.detach()
-        co, ci = w.shape[:2]
-        cop, cip = (_pad64(co) if pad_out else co), _pad64(ci)
-        wp = torch.zeros(cop, cip, 3, 3, dtype=w.dtype, device=w.device)
-        wp[:co, :ci] = w
-        bp = torch.zeros(cop, dtype=w.dtype, device=w.device)
-        bp[:co] = conv.bias.detach()
-        c = (key, wp.permute(0, 2, 3, 1).reshape(cop, -1).to(device=ctx.device, dtype=ctx.dtype).contiguous(),
-             bp.to(device=ctx.device, dtype=ctx.dtype))
-        conv._imh_padded = c
-    return c[1], c[2]
 
 
 class ControlNetModel(nn.Module):
@@ -124,6 +99,7 @@ class ControlNetModel(nn.Module):
     _temb_stack = UNet2DConditionModel._temb_stack
     _temb_chain = UNet2DConditionModel._temb_chain
     _emit_time_embedding = UNet2DConditionModel._emit_time_embedding
+    _emit_encoder = UNet2DConditionModel._emit_encoder
     precompute_temb = UNet2DConditionModel.precompute_temb
     prepare_conditioning = UNet2DConditionModel.prepare_conditioning
     _pname = UNet2DConditionModel._pname
@@ -166,17 +142,17 @@ class ControlNetModel(nn.Module):
         Sh = image.shape[0]
         x = torch.zeros(Sh, 8 * Hl, 8 * Wl, 64, dtype=ctx.dtype, device=ctx.device)                 # plumbing: NHWC, channels padded to 64
         x[..., :3] = image.to(device=ctx.device, dtype=ctx.dtype).permute(0, 2, 3, 1)
-        w, b = _padded(emb.conv_in, ctx)
+        w, b = emb.conv_in.packed_padded(ctx)
         h = ctx.conv3x3(x, w, bias=b, descr="cn.hint.conv_in")
         for i, blk in enumerate(emb.blocks):
             s = ctx.silu(h, descr="cn.hint.silu")
             ctx.free(h)
-            w, b = _padded(blk, ctx)
+            w, b = blk.packed_padded(ctx)
             h = ctx.conv3x3(s, w, bias=b, stride=2 if i % 2 else 1, descr=f"cn.hint.blocks.{i}")
             ctx.free(s)
         s = ctx.silu(h, descr="cn.hint.silu")
         ctx.free(h)
-        w, b = _padded(emb.conv_out, ctx, pad_out=False)
+        w, b = emb.conv_out.packed_padded(ctx, pad_out=False)
         hint = ctx.conv3x3(s, w, bias=b, descr="cn.hint.conv_out")
         ctx.free(s)
         if tuple(hint.shape) != (Sh, Hl, Wl, self.config.block_out_channels[0]):
@@ -210,31 +186,7 @@ class ControlNetModel(nn.Module):
         # sample = conv_in(sample) + controlnet_cond_embedding(cond): the hint add leaves the GroupNorm partials a conv_in output needs
         y, gs = ctx.control_add(x, hint, gn_sub=math.gcd(boc[0] // groups, 10), descr="cn.hint_add")
         ctx.free(x)
-        h = Feat(y, gs)
-        feats = [h]
-        ho = GN_STATS_HANDOVER
-        kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
-        for bi, blk in enumerate(self.down_blocks):
-            for i, r in enumerate(blk.resnets):
-                ctx.tag = 83
-                h = r.emit(ctx, h, st, keep_input=True)
-                if blk.has_attn:
-                    ctx.tag = 84
-                    h = blk.attentions[i].emit(ctx, h, kv_of(blk.attentions[i]), st)
-                feats.append(h)
-            if blk.downsamplers is not None:
-                ctx.tag = 83
-                d = blk.downsamplers[0].conv
-                r_ = ctx.conv3x3(h.t, d.packed(ctx), bias=_b(d, ctx), stride=2, descr="cn.downsample", gn_groups=1 if ho else 0)
-                h = Feat(*r_) if ho else Feat(r_)
-                feats.append(h)
-        ctx.tag = 85
-        mb = self.mid_block
-        h = mb.resnets[0].emit(ctx, h, st, keep_input=True)
-        ctx.tag = 86
-        h = mb.attentions[0].emit(ctx, h, kv_of(mb.attentions[0]), st)
-        ctx.tag = 85
-        h = mb.resnets[1].emit(ctx, h, st)
+        h, feats = self._emit_encoder(ctx, st, Feat(y, gs), (83, 84, 85, 86), prefix="cn.")
         # the zero convs: 1 x 1 convs are Linears over the pixels
         ctx.tag = 87
         down = []

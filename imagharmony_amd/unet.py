@@ -141,6 +141,25 @@ class Conv2d(nn.Module):
             self._imh_packed = c
         return c[1]
 
+    def packed_padded(self, ctx, pad_out=True):
+        """-> (packed [Cout', k*k * Cin'], bias [Cout']) with Cin' (and Cout' unless pad_out is False) zero-padded to a multiple of 64, so
+        a conv over a few channels runs on the implicit-GEMM kernel: the padded output channels are exact zeros, silu(0) = 0, so a chain
+        of such convs stays what the unpadded convs give.  Cached."""
+        key = (_vkey(self.weight, self.bias), ctx.dtype, str(ctx.device), pad_out)
+        c = getattr(self, "_imh_padded", None)
+        if c is None or c[0] != key:
+            w = self.weight.detach()
+            co, ci = w.shape[:2]
+            cop, cip = ((co + 63) // 64 * 64 if pad_out else co), (ci + 63) // 64 * 64
+            wp = torch.zeros(cop, cip, *w.shape[2:], dtype=w.dtype, device=w.device)
+            wp[:co, :ci] = w
+            bp = torch.zeros(cop, dtype=w.dtype, device=w.device)
+            bp[:co] = self.bias.detach()
+            c = (key, wp.permute(0, 2, 3, 1).reshape(cop, -1).to(device=ctx.device, dtype=ctx.dtype).contiguous(),
+                 bp.to(device=ctx.device, dtype=ctx.dtype))
+            self._imh_padded = c
+        return c[1], c[2]
+
     def packed_phase(self, ctx):
         """the 3 x 3 weight of an upsampler conv in the phase form of Ctx.conv3x3(up=2): [4 * Cout, 4 * Cin], pre-summed in fp32 from
         the stored weight and rounded once to the model dtype (ctx.phase_pack), cached."""
@@ -743,6 +762,38 @@ class UNet2DConditionModel(nn.Module):
             st.temb_all = self._temb_chain(ctx, tsin, st.aug_emb)
             ctx.free(tsin)
 
+    # ---- the encoder (down path + mid block), shared with controlnet.ControlNetModel ----
+    def _emit_encoder(self, ctx, st, h, tags, tag_step=0, prefix=""):
+        """h: the Feat after conv_in -> (the mid block's output, [h and every down-path output in skip order]).
+        tags = (down ResNets / downsamplers, down transformers, mid ResNets, mid transformer); the first two advance by tag_step per
+        down block; prefix goes in front of the downsamplers' descr."""
+        t_res, t_attn, t_mid_res, t_mid_attn = tags
+        feats = [h]
+        ho = GN_STATS_HANDOVER
+        kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
+        for bi, blk in enumerate(self.down_blocks):
+            for i, r in enumerate(blk.resnets):
+                ctx.tag = t_res + bi * tag_step
+                h = r.emit(ctx, h, st, keep_input=True)       # inputs are skip tensors: keep
+                if blk.has_attn:
+                    ctx.tag = t_attn + bi * tag_step
+                    h = blk.attentions[i].emit(ctx, h, kv_of(blk.attentions[i]), st)
+                feats.append(h)
+            if blk.downsamplers is not None:
+                ctx.tag = t_res + bi * tag_step
+                d = blk.downsamplers[0].conv
+                r_ = ctx.conv3x3(h.t, d.packed(ctx), bias=_b(d, ctx), stride=2, descr=prefix + "downsample", gn_groups=1 if ho else 0)
+                h = Feat(*r_) if ho else Feat(r_)
+                feats.append(h)
+        ctx.tag = t_mid_res
+        mb = self.mid_block
+        h = mb.resnets[0].emit(ctx, h, st, keep_input=True)
+        ctx.tag = t_mid_attn
+        h = mb.attentions[0].emit(ctx, h, kv_of(mb.attentions[0]), st)
+        ctx.tag = t_mid_res
+        h = mb.resnets[1].emit(ctx, h, st)
+        return h, feats
+
     # ---- the forward, as emitted ops ----
     def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None):
         """Records one UNet forward.  Reads st.latents (fp32 NCHW [S,4,Hl,Wl]); batch B = 2S when
@@ -780,32 +831,9 @@ class UNet2DConditionModel(nn.Module):
                i=(S, Hl, Wl, boc[0], B, 9 if cin == 9 else 0), f=(1.0, 0, 0, 0), descr="conv_in", x2=extra,
                nbytes=2.0 * B * Hl * Wl * boc[0])
         h = Feat(x)                      # (conv_in has no statistics epilogue: Feat.stats() takes one pass, shared by both readers)
-        skips = [h]
+        h, skips = self._emit_encoder(ctx, st, h, (10, 20, 30, 31), 1)
         ho = GN_STATS_HANDOVER
         kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
-        # -- down --
-        for bi, blk in enumerate(self.down_blocks):
-            for i, r in enumerate(blk.resnets):
-                ctx.tag = 10 + bi
-                h = r.emit(ctx, h, st, keep_input=True)       # inputs are skip tensors: keep
-                if blk.has_attn:
-                    ctx.tag = 20 + bi
-                    h = blk.attentions[i].emit(ctx, h, kv_of(blk.attentions[i]), st)
-                skips.append(h)
-            if blk.downsamplers is not None:
-                ctx.tag = 10 + bi
-                d = blk.downsamplers[0].conv
-                r_ = ctx.conv3x3(h.t, d.packed(ctx), bias=_b(d, ctx), stride=2, descr="downsample", gn_groups=1 if ho else 0)
-                h = Feat(*r_) if ho else Feat(r_)
-                skips.append(h)
-        # -- mid --
-        ctx.tag = 30
-        mb = self.mid_block
-        h = mb.resnets[0].emit(ctx, h, st, keep_input=True)
-        ctx.tag = 31
-        h = mb.attentions[0].emit(ctx, h, kv_of(mb.attentions[0]), st)
-        ctx.tag = 30
-        h = mb.resnets[1].emit(ctx, h, st)
         if control is not None:
             ctx.tag = 32
             if len(control.down) != len(skips):

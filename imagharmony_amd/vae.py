@@ -20,6 +20,9 @@ Both run a materialised single-head attention for the mid block (scores GEMM -> 
 width 512 does not fit the head_dim-64 flash kernel, and it runs once per image).  Tiled decoding follows diffusers'
 ``tiled_decode`` (overlapping 64x64-latent tiles, linear blends).  Host-side torch is plumbing only: channel padding
 of the 4-channel latent, the tile blends / concatenation, and the final NHWC->image conversion.
+
+The graph is written once: ``_decode_walk`` / ``_encode_walk`` (and the ResNet block, attention and mid block under them) run against a
+back-end object, ``_Native`` or ``_F32``, that owns what differs between the modes; the modules below only hold parameters.
 """
 from dataclasses import dataclass
 from typing import Tuple
@@ -47,12 +50,6 @@ class VAEConfig:
     tile_overlap_factor: float = 0.25
 
 
-def _gn(ctx, norm, x, groups, silu, descr):
-    B, H, W, C_ = x.shape
-    return ctx.groupnorm(x.view(B, H * W, C_), _w(norm, ctx), _b(norm, ctx), groups, norm.eps, silu=silu,
-                         descr=descr).view(B, H, W, C_)
-
-
 class ResnetBlock2D(nn.Module):
     def __init__(self, cin, cout, groups):
         super().__init__()
@@ -62,26 +59,6 @@ class ResnetBlock2D(nn.Module):
         self.norm2 = Norm(cout, 1e-6)
         self.conv2 = Conv2d(cout, cout, 3)
         self.conv_shortcut = Conv2d(cin, cout, 1) if cin != cout else None
-
-    def emit(self, ctx, x):
-        """x NHWC [B, H, W, Cin] (consumed) -> [B, H, W, Cout]"""
-        B, H, W, Cin = x.shape
-        n = _gn(ctx, self.norm1, x, self.groups, True, "vae.res.norm1")
-        h = ctx.conv3x3(n, self.conv1.packed(ctx), bias=_b(self.conv1, ctx), descr="vae.res.conv1")
-        ctx.free(n)
-        n = _gn(ctx, self.norm2, h, self.groups, True, "vae.res.norm2")
-        ctx.free(h)
-        if self.conv_shortcut is not None:
-            sc = ctx.gemm(x.view(B * H * W, Cin), self.conv_shortcut.packed(ctx), bias=_b(self.conv_shortcut, ctx),
-                          descr="vae.res.shortcut")
-        else:
-            sc = x.view(B * H * W, Cin)
-        out = ctx.conv3x3(n, self.conv2.packed(ctx), bias=_b(self.conv2, ctx), residual=sc, descr="vae.res.conv2")
-        ctx.free(n)
-        if self.conv_shortcut is not None:
-            ctx.free(sc)
-        ctx.free(x)
-        return out
 
 
 class VAEAttention(nn.Module):
@@ -96,55 +73,11 @@ class VAEAttention(nn.Module):
         self.to_v = Linear(channels, channels)
         self.to_out = nn.ModuleList([Linear(channels, channels), nn.Identity()])
 
-    def emit(self, ctx, x):
-        B, H, W, C_ = x.shape
-        Lq = H * W
-        # a token count that is not a multiple of 64 (a 100 x 100 latent): the PV GEMM runs over Lp keys (its K step is 64) from a
-        # probability matrix and a V^T whose padded keys are zero-filled and never written, so they contribute exact zeros; the scores
-        # GEMM runs over the Lq real keys, the softmax over Ls >= Lq columns (a multiple of 4) whose tail holds -inf scores (weight 0)
-        Lp, Ls = (Lq + 63) // 64 * 64, (Lq + 3) // 4 * 4
-        n = _gn(ctx, self.group_norm, x, self.groups, False, "vae.attn.norm").view(B * Lq, C_)
-        q = ctx.gemm(n, _w(self.to_q, ctx), bias=_b(self.to_q, ctx), descr="vae.attn.to_q")
-        k = ctx.gemm(n, _w(self.to_k, ctx), bias=_b(self.to_k, ctx), descr="vae.attn.to_k")
-        # V^T = Wv n^T (swapped operands) feeds the PV GEMM as its [N, K] operand; softmax rows sum to 1, so the
-        # to_v bias is added once after PV instead of to every value row
-        if Lp == Lq:
-            vt = ctx.gemm(_w(self.to_v, ctx), n, descr="vae.attn.to_v^T")                   # [C, B*L]
-        else:
-            vt = ctx.zeros(C_, B * Lp)                                                      # [C, B*Lp], batch b's keys at b*Lp
-            for b in range(B):
-                ctx.gemm(_w(self.to_v, ctx), n[b * Lq:(b + 1) * Lq], out=vt[:, b * Lp:b * Lp + Lq], descr="vae.attn.to_v^T")
-        ctx.free(n)
-        o = ctx.new(B * Lq, C_)
-        if Ls == Lq:
-            sc = ctx.new(Lq, Lp, dtype=torch.float32)
-        else:
-            sc = ctx.zeros(Lq, Lp, dtype=torch.float32)
-            sc[:, Lq:Ls] = float("-inf")                                                    # plumbing: the softmax's padded columns
-        pr = ctx.new(Lq, Lp) if Lp == Lq else ctx.zeros(Lq, Lp)
-        for b in range(B):
-            qb, kb = q[b * Lq:(b + 1) * Lq], k[b * Lq:(b + 1) * Lq]
-            ctx.gemm(qb, kb, out=sc[:, :Lq], flags=L.GF_OUT_F32, descr="vae.attn.scores")   # [L, L] fp32
-            ctx.ew(L.EW_SOFTMAX, pr, a=sc, i=(Lq, Ls, Lp, Lp, 0, 0), f=(C_ ** -0.5, 0.0, 0.0, 0.0),
-                   descr="vae.attn.softmax", nbytes=6.0 * Lq * Ls)
-            ctx.gemm(pr, vt[:, b * Lp:(b + 1) * Lp], out=o[b * Lq:(b + 1) * Lq], bias=_b(self.to_v, ctx), N=C_, K=Lp,
-                     ldw=B * Lp, descr="vae.attn.pv")
-        ctx.free(sc); ctx.free(pr); ctx.free(q); ctx.free(k); ctx.free(vt)
-        out = ctx.gemm(o, _w(self.to_out[0], ctx), bias=_b(self.to_out[0], ctx), residual=x.view(B * Lq, C_),
-                       descr="vae.attn.to_out")
-        ctx.free(o); ctx.free(x)
-        return out.view(B, H, W, C_)
-
 
 class Upsample2D(nn.Module):
     def __init__(self, ch):
         super().__init__()
         self.conv = Conv2d(ch, ch, 3)
-
-    def emit(self, ctx, x):
-        out = ctx.conv3x3(x, self.conv.packed(ctx), bias=_b(self.conv, ctx), up=1, descr="vae.upsample")   # nearest x2 fused
-        ctx.free(x)
-        return out
 
 
 class UpDecoderBlock2D(nn.Module):
@@ -154,13 +87,6 @@ class UpDecoderBlock2D(nn.Module):
         if up:
             self.upsamplers = nn.ModuleList([Upsample2D(cout)])
 
-    def emit(self, ctx, x):
-        for r in self.resnets:
-            x = r.emit(ctx, x)
-        for u in getattr(self, "upsamplers", []):
-            x = u.emit(ctx, x)
-        return x
-
 
 class Downsample2D(nn.Module):
     """diffusers Downsample2D(padding=0): conv3x3(F.pad(x, (0, 1, 0, 1)), stride 2) -- the pad is the conv's padding mode 1"""
@@ -168,11 +94,6 @@ class Downsample2D(nn.Module):
     def __init__(self, ch):
         super().__init__()
         self.conv = Conv2d(ch, ch, 3)
-
-    def emit(self, ctx, x):
-        out = ctx.conv3x3(x, self.conv.packed(ctx), bias=_b(self.conv, ctx), stride=2, pad=1, descr="vae.downsample")
-        ctx.free(x)
-        return out
 
 
 class DownEncoderBlock2D(nn.Module):
@@ -182,22 +103,12 @@ class DownEncoderBlock2D(nn.Module):
         if down:
             self.downsamplers = nn.ModuleList([Downsample2D(cout)])
 
-    def emit(self, ctx, x):
-        for r in self.resnets:
-            x = r.emit(ctx, x)
-        for d in getattr(self, "downsamplers", []):
-            x = d.emit(ctx, x)
-        return x
-
 
 class MidBlock(nn.Module):
     def __init__(self, ch, groups):
         super().__init__()
         self.attentions = nn.ModuleList([VAEAttention(ch, groups)])
         self.resnets = nn.ModuleList([ResnetBlock2D(ch, ch, groups), ResnetBlock2D(ch, ch, groups)])
-
-    def emit(self, ctx, x):
-        return self.resnets[1].emit(ctx, self.attentions[0].emit(ctx, self.resnets[0].emit(ctx, x)))
 
 
 class Decoder(nn.Module):
@@ -260,34 +171,21 @@ class AutoencoderKLOutput:
     latent_dist: DiagonalGaussianDistribution
 
 
-def _pad_conv_in(conv, ctx, cpad=64):
-    """conv_in reads a 4-channel latent: zero-pad Cin to 64 so it runs on the implicit-GEMM kernel (K = 9*64)"""
-    key = (_vkey(conv.weight), ctx.dtype, str(ctx.device))
-    c = getattr(conv, "_imh_padded", None)
-    if c is None or c[0] != key:
-        w = conv.weight.detach()
-        wp = torch.zeros(w.shape[0], cpad, 3, 3, dtype=w.dtype, device=w.device)
-        wp[:, :w.shape[1]] = w
-        c = (key, wp.permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(device=ctx.device, dtype=ctx.dtype).contiguous())
-        conv._imh_padded = c
-    return c[1]
-
-
-def _pad_1x1(conv, ctx, cpad=64):
-    key = (_vkey(conv.weight, conv.bias), ctx.dtype, str(ctx.device))
-    c = getattr(conv, "_imh_padded", None)
+def _pad_1x1(conv, cpad, dtype, device):
+    """a 1 x 1 conv as a [cpad, cpad] matrix and a [cpad] bias, zero-padded, cached per cpad"""
+    key = (_vkey(conv.weight, conv.bias), dtype, str(device))
+    c = getattr(conv, f"_imh_padded{cpad}", None)
     if c is None or c[0] != key:
         w = conv.weight.detach().view(conv.weight.shape[0], -1)
         wp = torch.zeros(cpad, cpad, dtype=w.dtype, device=w.device)
         wp[:w.shape[0], :w.shape[1]] = w
         bp = torch.zeros(cpad, dtype=w.dtype, device=w.device)
         bp[:w.shape[0]] = conv.bias.detach()
-        c = (key, wp.to(device=ctx.device, dtype=ctx.dtype).contiguous(), bp.to(device=ctx.device, dtype=ctx.dtype))
-        conv._imh_padded = c
+        c = (key, wp.to(device=device, dtype=dtype).contiguous(), bp.to(device=device, dtype=dtype))
+        setattr(conv, f"_imh_padded{cpad}", c)
     return c[1], c[2]
 
 
-# ---- fp32 (reference-precision) decode: the same graph on csrc/f32.hip --------------------------------------------------
 def _f32_cached(mod, name, build, *src):
     """fp32 copy of a module's (packed / padded) parameter on the device, rebuilt when the source changes (in place or re-assigned)"""
     key = (_vkey(*src), str(src[0].device))
@@ -298,20 +196,19 @@ def _f32_cached(mod, name, build, *src):
     return c[1]
 
 
-def _f32_conv_w(conv, cin_pad=0):
-    """[Cout, Cin, 3, 3] -> packed fp32 [Cout, 9 * Cin'] (K index = (ky*3+kx)*Cin' + c), Cin zero-padded to cin_pad"""
+def _f32_w(mod, cin_pad=0):
+    """a Linear's [N, K], or a conv's [Cout, Cin, k, k] -> packed [Cout, k*k * Cin'] (K index = (ky*k+kx)*Cin' + c) with Cin zero-padded
+    to cin_pad, in fp32"""
     def build():
-        w = conv.weight.detach().float()
-        if cin_pad and cin_pad > w.shape[1]:
-            wp = torch.zeros(w.shape[0], cin_pad, 3, 3, dtype=torch.float32, device=w.device)
-            wp[:, :w.shape[1]] = w
-            w = wp
-        return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
-    return _f32_cached(conv, "_imh_f32_w", build, conv.weight)
-
-
-def _f32_lin_w(lin):
-    return _f32_cached(lin, "_imh_f32_w", lambda: lin.weight.detach().float().reshape(lin.weight.shape[0], -1).contiguous(), lin.weight)
+        w = mod.weight.detach().float()
+        if w.dim() == 4:
+            if cin_pad > w.shape[1]:
+                wp = torch.zeros(w.shape[0], cin_pad, *w.shape[2:], dtype=torch.float32, device=w.device)
+                wp[:, :w.shape[1]] = w
+                w = wp
+            w = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+        return w.contiguous()
+    return _f32_cached(mod, "_imh_f32_w", build, mod.weight)
 
 
 def _f32_vec(mod, attr="bias"):
@@ -319,60 +216,215 @@ def _f32_vec(mod, attr="bias"):
     return _f32_cached(mod, "_imh_f32_" + attr, lambda: t.detach().float().contiguous(), t)
 
 
-def _gn32(ctx, norm, x, groups, silu, descr):
+# ---- the two back ends: everything that differs between the compute modes; the walks below are written once against them ----
+class _Native:
+    """16-bit: NHWC activations in the module's dtype on the UNet's own kernels"""
+    pre = "vae."        # descr prefix
+    kstep = 64          # the K step of the GEMM / implicit-GEMM kernels: the few-channel inputs and the attention's keys are padded to it
+
+    def __init__(self, device, dtype):
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise L.ImhError("the native HIP VAE path computes in bf16 or fp16 (precision='fp32' runs any module in fp32)")
+        self.ctx = ctx = Ctx(device, dtype)
+        self.dtype = dtype
+        self.conv3x3, self.gemm = ctx.conv3x3, ctx.gemm
+
+    def w(self, mod, cin_pad=False):
+        if cin_pad:     # conv_in reads a 3- / 4-channel input: Cin zero-padded to 64 so it runs on the implicit-GEMM kernel (K = 9*64)
+            return mod.packed_padded(self.ctx, pad_out=False)[0]
+        return mod.packed(self.ctx) if mod.weight.dim() == 4 else _w(mod, self.ctx)
+
+    def b(self, mod):
+        return _b(mod, self.ctx)
+
+    def groupnorm(self, norm, x, groups, silu, descr):
+        return self.ctx.groupnorm(x, _w(norm, self.ctx), _b(norm, self.ctx), groups, norm.eps, silu=silu, descr=descr)
+
+    def probs_scratch(self, Lq, Lp):
+        """fp32 scores and the probabilities in the compute dtype.  The softmax runs over Ls >= Lq columns (a multiple of 4) whose tail
+        holds -inf scores (weight 0); the scores GEMM writes the Lq real ones"""
+        ctx, Ls = self.ctx, (Lq + 3) // 4 * 4
+        if Ls == Lq:
+            sc = ctx.new(Lq, Lp, dtype=torch.float32)
+        else:
+            sc = ctx.zeros(Lq, Lp, dtype=torch.float32)
+            sc[:, Lq:Ls] = float("-inf")                                                    # plumbing: the softmax's padded columns
+        return sc, (ctx.new(Lq, Lp) if Lp == Lq else ctx.zeros(Lq, Lp))
+
+    def probs(self, q, k, scratch, scale):
+        sc, pr = scratch
+        (Lq, Lp), Ls = pr.shape, (pr.shape[0] + 3) // 4 * 4
+        self.ctx.gemm(q, k, out=sc[:, :Lq], flags=L.GF_OUT_F32, descr="vae.attn.scores")   # [L, L] fp32
+        self.ctx.ew(L.EW_SOFTMAX, pr, a=sc, i=(Lq, Ls, Lp, Lp, 0, 0), f=(scale, 0.0, 0.0, 0.0), descr="vae.attn.softmax", nbytes=6.0 * Lq * Ls)
+        return pr
+
+    def post_quant(self, conv, zp):
+        wq, bq = _pad_1x1(conv, self.kstep, self.dtype, self.ctx.device)
+        return self.ctx.gemm(zp, wq, bias=bq, descr="vae.post_quant")
+
+    def quant(self, conv, yp, c2):
+        wq, bq = _pad_1x1(conv, self.kstep, self.dtype, self.ctx.device)
+        m = torch.empty(yp.shape[0], self.kstep, dtype=torch.float32, device=yp.device)
+        self.ctx.gemm(yp, wq, bias=bq, out=m, flags=L.GF_OUT_F32, descr="vae.enc.quant_conv")                 # fp32 moments
+        return m[:, :c2]
+
+    def image(self, y):
+        return y.permute(0, 3, 1, 2).float()
+
+
+class _F32:
+    """fp32 (reference precision): fp32 activations, the stored weights upcast exactly, every product in fp32 on csrc/f32.hip"""
+    pre = "vae32."
+    kstep = 16
+    dtype = torch.float32
+
+    def __init__(self, device):
+        self.ctx = ctx = Ctx(device, torch.bfloat16)                            # (pool / stream only: every tensor is fp32)
+        self.conv3x3, self.gemm = ctx.f32_conv3x3, ctx.f32_gemm
+
+    def w(self, mod, cin_pad=False):
+        return _f32_w(mod, self.kstep if cin_pad else 0)
+
+    def b(self, mod):
+        return _f32_vec(mod)
+
+    def groupnorm(self, norm, x, groups, silu, descr):
+        return self.ctx.f32_groupnorm(x, _f32_vec(norm, "weight"), _f32_vec(norm, "bias"), groups, norm.eps, silu=silu, descr=descr)
+
+    def probs_scratch(self, Lq, Lp):
+        ctx = self.ctx
+        return (ctx.new(Lq, Lq, dtype=torch.float32) if Lp == Lq else ctx.zeros(Lq, Lp, dtype=torch.float32),)
+
+    def probs(self, q, k, scratch, scale):
+        sc, Lq = scratch[0], q.shape[0]
+        self.ctx.f32_gemm(q, k, out=sc[:, :Lq], descr="vae32.attn.scores")
+        self.ctx.f32_softmax(sc[:, :Lq], sc[:, :Lq], scale, descr="vae32.attn.softmax")     # in place (a row is read before it is written)
+        return sc
+
+    def post_quant(self, conv, zp):
+        wq, bq = _pad_1x1(conv, self.kstep, torch.float32, self.ctx.device)
+        return self.ctx.f32_gemm(zp, wq, bias=bq, descr="vae32.post_quant")
+
+    def quant(self, conv, yp, c2):
+        return self.ctx.f32_gemm(yp, _f32_w(conv, self.kstep), bias=_f32_vec(conv), descr="vae32.enc.quant_conv").clone()
+
+    def image(self, y):
+        return y.permute(0, 3, 1, 2).contiguous()
+
+
+def _gn(be, norm, x, groups, silu, descr):
     B, H, W, C_ = x.shape
-    return ctx.f32_groupnorm(x.view(B, H * W, C_), _f32_vec(norm, "weight"), _f32_vec(norm, "bias"), groups, norm.eps, silu=silu,
-                             descr=descr).view(B, H, W, C_)
+    return be.groupnorm(norm, x.view(B, H * W, C_), groups, silu, be.pre + descr).view(B, H, W, C_)
 
 
-def _res32(ctx, r, x):
+def _conv(be, conv, x, descr, **kw):
+    """x NHWC (consumed) -> conv3x3(x)"""
+    out = be.conv3x3(x, be.w(conv), bias=be.b(conv), descr=be.pre + descr, **kw)
+    be.ctx.free(x)
+    return out
+
+
+def _resnet(be, r, x):
+    """x NHWC [B, H, W, Cin] (consumed) -> [B, H, W, Cout]"""
+    ctx = be.ctx
     B, H, W, Cin = x.shape
-    n = _gn32(ctx, r.norm1, x, r.groups, True, "vae32.res.norm1")
-    h = ctx.f32_conv3x3(n, _f32_conv_w(r.conv1), bias=_f32_vec(r.conv1), descr="vae32.res.conv1")
-    ctx.free(n)
-    n = _gn32(ctx, r.norm2, h, r.groups, True, "vae32.res.norm2")
+    h = _conv(be, r.conv1, _gn(be, r.norm1, x, r.groups, True, "res.norm1"), "res.conv1")
+    n = _gn(be, r.norm2, h, r.groups, True, "res.norm2")
     ctx.free(h)
+    sc = x.view(B * H * W, Cin)
     if r.conv_shortcut is not None:
-        sc = ctx.f32_gemm(x.view(B * H * W, Cin), _f32_lin_w(r.conv_shortcut), bias=_f32_vec(r.conv_shortcut), descr="vae32.res.shortcut")
-    else:
-        sc = x.view(B * H * W, Cin)
-    out = ctx.f32_conv3x3(n, _f32_conv_w(r.conv2), bias=_f32_vec(r.conv2), residual=sc, descr="vae32.res.conv2")
-    ctx.free(n)
+        sc = be.gemm(sc, be.w(r.conv_shortcut), bias=be.b(r.conv_shortcut), descr=be.pre + "res.shortcut")
+    out = _conv(be, r.conv2, n, "res.conv2", residual=sc)
     if r.conv_shortcut is not None:
         ctx.free(sc)
     ctx.free(x)
     return out
 
 
-def _attn32(ctx, at, x):
+def _attention(be, at, x):
+    ctx = be.ctx
     B, H, W, C_ = x.shape
     Lq = H * W
-    # a token count that is not a multiple of 16 (the PV GEMM's K step): the probabilities and V^T of the Lq real keys sit in zero-filled
-    # buffers of Lp keys whose padded columns are never written, so they contribute exact zeros
-    Lp = (Lq + 15) // 16 * 16
-    n = _gn32(ctx, at.group_norm, x, at.groups, False, "vae32.attn.norm").view(B * Lq, C_)
-    q = ctx.f32_gemm(n, _f32_lin_w(at.to_q), bias=_f32_vec(at.to_q), descr="vae32.attn.to_q")
-    k = ctx.f32_gemm(n, _f32_lin_w(at.to_k), bias=_f32_vec(at.to_k), descr="vae32.attn.to_k")
-    # V^T = Wv n^T (swapped operands) feeds the PV GEMM as its [N, K] operand; softmax rows sum to 1, so the to_v bias is added once after PV
+    # a token count that is not a multiple of the PV GEMM's K step (a 100 x 100 latent): that GEMM runs over Lp keys from a probability
+    # matrix and a V^T whose padded keys are zero-filled and never written, so they contribute exact zeros; the scores GEMM runs over
+    # the Lq real keys
+    Lp = (Lq + be.kstep - 1) // be.kstep * be.kstep
+    n = _gn(be, at.group_norm, x, at.groups, False, "attn.norm").view(B * Lq, C_)
+    q = be.gemm(n, be.w(at.to_q), bias=be.b(at.to_q), descr=be.pre + "attn.to_q")
+    k = be.gemm(n, be.w(at.to_k), bias=be.b(at.to_k), descr=be.pre + "attn.to_k")
+    # V^T = Wv n^T (swapped operands) feeds the PV GEMM as its [N, K] operand; softmax rows sum to 1, so the
+    # to_v bias is added once after PV instead of to every value row
     if Lp == Lq:
-        vt = ctx.f32_gemm(_f32_lin_w(at.to_v), n, descr="vae32.attn.to_v^T")                  # [C, B*L]
+        vt = be.gemm(be.w(at.to_v), n, descr=be.pre + "attn.to_v^T")                        # [C, B*L]
     else:
-        vt = ctx.zeros(C_, B * Lp, dtype=torch.float32)                                         # [C, B*Lp], batch b's keys at b*Lp
+        vt = ctx.zeros(C_, B * Lp, dtype=be.dtype)                                          # [C, B*Lp], batch b's keys at b*Lp
         for b in range(B):
-            ctx.f32_gemm(_f32_lin_w(at.to_v), n[b * Lq:(b + 1) * Lq], out=vt[:, b * Lp:b * Lp + Lq], descr="vae32.attn.to_v^T")
+            be.gemm(be.w(at.to_v), n[b * Lq:(b + 1) * Lq], out=vt[:, b * Lp:b * Lp + Lq], descr=be.pre + "attn.to_v^T")
     ctx.free(n)
-    o = ctx.new(B * Lq, C_, dtype=torch.float32)
-    sc = ctx.new(Lq, Lq, dtype=torch.float32) if Lp == Lq else ctx.zeros(Lq, Lp, dtype=torch.float32)
+    o = ctx.new(B * Lq, C_, dtype=be.dtype)
+    scratch = be.probs_scratch(Lq, Lp)
     for b in range(B):
-        qb, kb = q[b * Lq:(b + 1) * Lq], k[b * Lq:(b + 1) * Lq]
-        ctx.f32_gemm(qb, kb, out=sc[:, :Lq], descr="vae32.attn.scores")
-        ctx.f32_softmax(sc[:, :Lq], sc[:, :Lq], C_ ** -0.5, descr="vae32.attn.softmax")          # in place (a row is read before it is written)
-        ctx.f32_gemm(sc, vt[:, b * Lp:(b + 1) * Lp], out=o[b * Lq:(b + 1) * Lq], bias=_f32_vec(at.to_v), N=C_, K=Lp, ldw=B * Lp,
-                     descr="vae32.attn.pv")
-    ctx.free(sc); ctx.free(q); ctx.free(k); ctx.free(vt)
-    out = ctx.f32_gemm(o, _f32_lin_w(at.to_out[0]), bias=_f32_vec(at.to_out[0]), residual=x.view(B * Lq, C_), descr="vae32.attn.to_out")
+        pr = be.probs(q[b * Lq:(b + 1) * Lq], k[b * Lq:(b + 1) * Lq], scratch, C_ ** -0.5)  # [Lq, Lp]
+        be.gemm(pr, vt[:, b * Lp:(b + 1) * Lp], out=o[b * Lq:(b + 1) * Lq], bias=be.b(at.to_v), N=C_, K=Lp, ldw=B * Lp,
+                descr=be.pre + "attn.pv")
+    for t in (*scratch, q, k, vt):
+        ctx.free(t)
+    out = be.gemm(o, be.w(at.to_out[0]), bias=be.b(at.to_out[0]), residual=x.view(B * Lq, C_), descr=be.pre + "attn.to_out")
     ctx.free(o); ctx.free(x)
     return out.view(B, H, W, C_)
+
+
+def _mid(be, mb, x):
+    return _resnet(be, mb.resnets[1], _attention(be, mb.attentions[0], _resnet(be, mb.resnets[0], x)))
+
+
+def _padded_input(be, x):
+    """NCHW fp32 -> NHWC in the back end's dtype, the channels zero-padded to its K step (plumbing)"""
+    B, c, H, W = x.shape
+    xp = torch.zeros(B, H, W, be.kstep, dtype=be.dtype, device=x.device)
+    xp[..., :c] = x.permute(0, 2, 3, 1).to(be.dtype)
+    return xp
+
+
+def _head(be, net, x, pre):
+    """conv_out(silu(conv_norm_out(x))), x consumed"""
+    n = _gn(be, net.conv_norm_out, x, net.groups, True, pre + "conv_norm_out")
+    be.ctx.free(x)
+    return _conv(be, net.conv_out, n, pre + "conv_out")
+
+
+def _decode_walk(be, vae, z):
+    """z: [B, 4, h, w] fp32 on the device -> [B, 3, 8h, 8w] fp32"""
+    d = vae.decoder
+    zp = _padded_input(be, z)
+    B, h, w, kp = zp.shape
+    t = be.post_quant(vae.post_quant_conv, zp.view(B * h * w, kp)).view(B, h, w, kp)
+    x = be.conv3x3(t, be.w(d.conv_in, cin_pad=True), bias=be.b(d.conv_in), descr=be.pre + "conv_in")
+    be.ctx.free(t)
+    x = _mid(be, d.mid_block, x)
+    for blk in d.up_blocks:
+        for r in blk.resnets:
+            x = _resnet(be, r, x)
+        for u in getattr(blk, "upsamplers", []):
+            x = _conv(be, u.conv, x, "upsample", up=1)                                      # nearest x2 fused
+    return be.image(_head(be, d, x, ""))                                                    # [B, 8h, 8w, 3] -> NCHW
+
+
+def _encode_walk(be, vae, x):
+    """x: [B, 3, H, W] fp32 on the device -> the moments quant_conv(encoder(x)) as NHWC [B, h, w, 2 C] fp32"""
+    e = vae._encoder()
+    h = be.conv3x3(_padded_input(be, x), be.w(e.conv_in, cin_pad=True), bias=be.b(e.conv_in), descr=be.pre + "enc.conv_in")
+    for blk in e.down_blocks:
+        for r in blk.resnets:
+            h = _resnet(be, r, h)
+        for d in getattr(blk, "downsamplers", []):
+            h = _conv(be, d.conv, h, "enc.downsample", stride=2, pad=1)
+    y = _head(be, e, _mid(be, e.mid_block, h), "enc.")                                      # [B, h, w, 2C]
+    B, hh, ww, c2 = y.shape
+    yp = torch.zeros(B * hh * ww, be.kstep, dtype=be.dtype, device=x.device)                # plumbing: K padded to the K step
+    yp[:, :c2] = y.view(-1, c2)
+    be.ctx.free(y)
+    return be.quant(vae.quant_conv, yp, c2).reshape(B, hh, ww, c2)
 
 
 class AutoencoderKL(nn.Module):
@@ -436,66 +488,12 @@ class AutoencoderKL(nn.Module):
             raise ValueError(f"precision {precision!r} (expected 'auto', 'fp32' or 'native')")
         return precision
 
-    def _decode_tile_f32(self, z):
-        """z: [B, 4, h, w] fp32 on the device -> [B, 3, 8h, 8w] fp32, every activation and every product in fp32"""
-        dev = z.device
-        ctx = Ctx(dev, torch.bfloat16)                                           # (pool / stream only: every tensor below is fp32)
-        B, _, h, w = z.shape
-        d = self.decoder
-        zp = torch.zeros(B, h, w, 16, dtype=torch.float32, device=dev)           # plumbing: NHWC, channels padded to the K step of 16
-        zp[..., :z.shape[1]] = z.permute(0, 2, 3, 1)
-        pq = self.post_quant_conv
-
-        def build_pq():
-            wq = torch.zeros(16, 16, dtype=torch.float32, device=dev)
-            wq[:pq.weight.shape[0], :pq.weight.shape[1]] = pq.weight.detach().float().view(pq.weight.shape[0], -1)
-            bq = torch.zeros(16, dtype=torch.float32, device=dev)
-            bq[:pq.bias.shape[0]] = pq.bias.detach().float()
-            return wq, bq
-        wq, bq = _f32_cached(pq, "_imh_f32_w", build_pq, pq.weight, pq.bias)
-        t = ctx.f32_gemm(zp.view(B * h * w, 16), wq, bias=bq, descr="vae32.post_quant").view(B, h, w, 16)
-        x = ctx.f32_conv3x3(t, _f32_conv_w(d.conv_in, cin_pad=16), bias=_f32_vec(d.conv_in), descr="vae32.conv_in")
-        ctx.free(t)
-        x = _res32(ctx, d.mid_block.resnets[0], x)
-        x = _attn32(ctx, d.mid_block.attentions[0], x)
-        x = _res32(ctx, d.mid_block.resnets[1], x)
-        for blk in d.up_blocks:
-            for r in blk.resnets:
-                x = _res32(ctx, r, x)
-            for u in getattr(blk, "upsamplers", []):
-                y = ctx.f32_conv3x3(x, _f32_conv_w(u.conv), bias=_f32_vec(u.conv), up=1, descr="vae32.upsample")    # nearest x2 fused
-                ctx.free(x)
-                x = y
-        n = _gn32(ctx, d.conv_norm_out, x, d.groups, True, "vae32.conv_norm_out")
-        ctx.free(x)
-        y = ctx.f32_conv3x3(n, _f32_conv_w(d.conv_out), bias=_f32_vec(d.conv_out), descr="vae32.conv_out")          # [B, 8h, 8w, 3]
-        ctx.free(n)
-        return y.permute(0, 3, 1, 2).contiguous()
+    def _backend(self, device, precision):
+        return _F32(device) if precision == "fp32" else _Native(device, self.dtype)
 
     def _decode_tile(self, z, precision="native"):
         """z: [B, 4, h, w] fp32 on the device -> [B, 3, 8h, 8w] fp32"""
-        if precision == "fp32":
-            return self._decode_tile_f32(z)
-        dev, dt = z.device, self.dtype
-        if dt not in (torch.bfloat16, torch.float16):
-            raise L.ImhError("the native HIP VAE path computes in bf16 or fp16 (precision='fp32' runs any module in fp32)")
-        ctx = Ctx(dev, dt)
-        B, _, h, w = z.shape
-        zp = torch.zeros(B, h, w, 64, dtype=dt, device=dev)                     # plumbing: NHWC, channels padded to 64
-        zp[..., :z.shape[1]] = z.permute(0, 2, 3, 1).to(dt)
-        wq, bq = _pad_1x1(self.post_quant_conv, ctx)
-        t = ctx.gemm(zp.view(B * h * w, 64), wq, bias=bq, descr="vae.post_quant").view(B, h, w, 64)
-        d = self.decoder
-        x = ctx.conv3x3(t, _pad_conv_in(d.conv_in, ctx), bias=_b(d.conv_in, ctx), descr="vae.conv_in")
-        ctx.free(t)
-        x = d.mid_block.emit(ctx, x)
-        for blk in d.up_blocks:
-            x = blk.emit(ctx, x)
-        n = _gn(ctx, d.conv_norm_out, x, d.groups, True, "vae.conv_norm_out")
-        ctx.free(x)
-        y = ctx.conv3x3(n, d.conv_out.packed(ctx), bias=_b(d.conv_out, ctx), descr="vae.conv_out")    # [B, 8h, 8w, 3]
-        ctx.free(n)
-        return y.permute(0, 3, 1, 2).float()
+        return _decode_walk(self._backend(z.device, precision), self, z)
 
     @staticmethod
     def _blend(a, b, extent, dim):
@@ -505,24 +503,23 @@ class AutoencoderKL(nn.Module):
         head = a.narrow(dim, a.shape[dim] - extent, extent) * (1 - wgt) + b.narrow(dim, 0, extent) * wgt
         return torch.cat([head, b.narrow(dim, extent, b.shape[dim] - extent)], dim)
 
-    def tiled_decode(self, z, precision="native"):
-        overlap = int(self.tile_latent_min_size * (1 - self.tile_overlap_factor))
-        extent = int(self.tile_sample_min_size * self.tile_overlap_factor)
-        limit = self.tile_sample_min_size - extent
-        # every operation of the decoder is per sample, so the tiles of one shape are decoded as ONE batch (round 6: 3 x 3 tiles of a 128 x 128
+    def _stitch(self, x, tile, stride, extent, limit, fn):
+        """diffusers tiled_decode / tiled_encode: overlapping tiles of `tile` at `stride`, fn per tile (NCHW -> NCHW), in-place blend_v /
+        blend_h over `extent` rows / columns, crop to `limit`, concatenate"""
+        # every operation of the decoder / encoder is per sample, so the tiles of one shape run as ONE batch (round 6: 3 x 3 tiles of a 128 x 128
         # latent = 4 launches' worth of work instead of 9 under-filled ones; in the fp32 path the same bits per tile as one tile at a time, in the
         # 16-bit path the same to rounding -- there the GEMM variant depends on M)
-        ii, jj = list(range(0, z.shape[2], overlap)), list(range(0, z.shape[3], overlap))
-        tiles = {(i, j): z[:, :, i:i + self.tile_latent_min_size, j:j + self.tile_latent_min_size] for i in ii for j in jj}
+        ii, jj = list(range(0, x.shape[2], stride)), list(range(0, x.shape[3], stride))
+        tiles = {(i, j): x[:, :, i:i + tile, j:j + tile] for i in ii for j in jj}
         groups = {}
         for key, t in tiles.items():
             groups.setdefault(tuple(t.shape[2:]), []).append(key)
-        dec = {}
+        done = {}
         for keys in groups.values():
-            out = self._decode_tile(torch.cat([tiles[k] for k in keys], 0).contiguous(), precision)
-            for k, o in zip(keys, out.split(z.shape[0], 0)):
-                dec[k] = o
-        rows = [[dec[(i, j)] for j in jj] for i in ii]
+            out = fn(torch.cat([tiles[k] for k in keys], 0).contiguous())
+            for k, o in zip(keys, out.split(x.shape[0], 0)):
+                done[k] = o
+        rows = [[done[(i, j)] for j in jj] for i in ii]
         out_rows = []
         for i, row in enumerate(rows):
             out = []
@@ -535,6 +532,10 @@ class AutoencoderKL(nn.Module):
                 out.append(t[:, :, :limit, :limit])
             out_rows.append(torch.cat(out, dim=3))
         return torch.cat(out_rows, dim=2)
+
+    def tiled_decode(self, z, precision="native"):
+        lat, px, f = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
+        return self._stitch(z, lat, int(lat * (1 - f)), int(px * f), px - int(px * f), lambda t: self._decode_tile(t, precision))
 
     @torch.no_grad()
     def decode(self, z, precision=None):
@@ -546,109 +547,23 @@ class AutoencoderKL(nn.Module):
             return self.tiled_decode(z, precision)
         return self._decode_tile(z, precision)
 
-
     # -- encode (image-to-image) --
     def _encoder(self):
         if not self.with_encoder:
             raise NotImplementedError("this AutoencoderKL holds no encoder: construct it with with_encoder=True (image-to-image)")
         return self.encoder
 
-    def _encode_tile_f32(self, x):
-        """x: [B, 3, H, W] fp32 on the device -> moments NHWC [B, H/8', W/8', 2 C] fp32 (quant_conv(encoder(x))), every product in fp32"""
-        dev = x.device
-        ctx = Ctx(dev, torch.bfloat16)                                           # (pool / stream only: every tensor below is fp32)
-        e = self._encoder()
-        B, cin, H, W = x.shape
-        xp = torch.zeros(B, H, W, 16, dtype=torch.float32, device=dev)          # plumbing: NHWC, channels padded to the K step of 16
-        xp[..., :cin] = x.permute(0, 2, 3, 1)
-        h = ctx.f32_conv3x3(xp, _f32_conv_w(e.conv_in, cin_pad=16), bias=_f32_vec(e.conv_in), descr="vae32.enc.conv_in")
-        for blk in e.down_blocks:
-            for r in blk.resnets:
-                h = _res32(ctx, r, h)
-            for d in getattr(blk, "downsamplers", []):
-                y = ctx.f32_conv3x3(h, _f32_conv_w(d.conv), bias=_f32_vec(d.conv), stride=2, pad=1, descr="vae32.enc.downsample")
-                ctx.free(h)
-                h = y
-        h = _res32(ctx, e.mid_block.resnets[0], h)
-        h = _attn32(ctx, e.mid_block.attentions[0], h)
-        h = _res32(ctx, e.mid_block.resnets[1], h)
-        n = _gn32(ctx, e.conv_norm_out, h, e.groups, True, "vae32.enc.conv_norm_out")
-        ctx.free(h)
-        y = ctx.f32_conv3x3(n, _f32_conv_w(e.conv_out), bias=_f32_vec(e.conv_out), descr="vae32.enc.conv_out")      # [B, h, w, 2C]
-        ctx.free(n)
-        B, hh, ww, c2 = y.shape
-        yp = torch.zeros(B * hh * ww, 16, dtype=torch.float32, device=dev)      # plumbing: K padded to 16
-        yp[:, :c2] = y.view(-1, c2)
-        ctx.free(y)
-        qc = self.quant_conv
-
-        def build_q():
-            wq = torch.zeros(c2, 16, dtype=torch.float32, device=dev)
-            wq[:, :c2] = qc.weight.detach().float().view(c2, c2)
-            return wq
-        wq = _f32_cached(qc, "_imh_f32_w", build_q, qc.weight)
-        m = ctx.f32_gemm(yp, wq, bias=_f32_vec(qc), descr="vae32.enc.quant_conv")
-        return m.view(B, hh, ww, c2).clone()
-
     def _encode_tile(self, x, precision="native"):
         """x: [B, 3, H, W] fp32 on the device -> moments NHWC [B, h, w, 2 C] fp32"""
-        if precision == "fp32":
-            return self._encode_tile_f32(x)
-        dev, dt = x.device, self.dtype
-        if dt not in (torch.bfloat16, torch.float16):
-            raise L.ImhError("the native HIP VAE path computes in bf16 or fp16 (precision='fp32' runs any module in fp32)")
-        ctx = Ctx(dev, dt)
-        e = self._encoder()
-        B, cin, H, W = x.shape
-        xp = torch.zeros(B, H, W, 64, dtype=dt, device=dev)                     # plumbing: NHWC, channels padded to 64
-        xp[..., :cin] = x.permute(0, 2, 3, 1).to(dt)
-        h = ctx.conv3x3(xp, _pad_conv_in(e.conv_in, ctx), bias=_b(e.conv_in, ctx), descr="vae.enc.conv_in")
-        for blk in e.down_blocks:
-            h = blk.emit(ctx, h)
-        h = e.mid_block.emit(ctx, h)
-        n = _gn(ctx, e.conv_norm_out, h, e.groups, True, "vae.enc.conv_norm_out")
-        ctx.free(h)
-        y = ctx.conv3x3(n, e.conv_out.packed(ctx), bias=_b(e.conv_out, ctx), descr="vae.enc.conv_out")        # [B, h, w, 2C]
-        ctx.free(n)
-        B, hh, ww, c2 = y.shape
-        yp = torch.zeros(B * hh * ww, 64, dtype=dt, device=dev)                 # plumbing: K padded to 64
-        yp[:, :c2] = y.view(-1, c2)
-        ctx.free(y)
-        wq, bq = _pad_1x1(self.quant_conv, ctx)
-        m = torch.empty(B * hh * ww, 64, dtype=torch.float32, device=dev)
-        ctx.gemm(yp, wq, bias=bq, out=m, flags=L.GF_OUT_F32, descr="vae.enc.quant_conv")                        # fp32 moments
-        return m[:, :c2].reshape(B, hh, ww, c2)
+        return _encode_walk(self._backend(x.device, precision), self, x)
 
     def tiled_encode(self, x, precision="native"):
         """diffusers 0.30 tiled_encode: tiles of tile_sample_min_size px at stride (1 - overlap) of that, encoder + quant_conv per tile,
-        in-place blend_v / blend_h over int(tile_latent_min_size * overlap) latent rows, crop to tile_latent_min_size - blend_extent.
-        Returns NCHW moments [B, 2 C, h, w].  The tiles of one shape are encoded as one batch, as tiled_decode does."""
-        overlap = int(self.tile_sample_min_size * (1 - self.tile_overlap_factor))
-        extent = int(self.tile_latent_min_size * self.tile_overlap_factor)
-        limit = self.tile_latent_min_size - extent
-        ii, jj = list(range(0, x.shape[2], overlap)), list(range(0, x.shape[3], overlap))
-        tiles = {(i, j): x[:, :, i:i + self.tile_sample_min_size, j:j + self.tile_sample_min_size] for i in ii for j in jj}
-        groups = {}
-        for key, t in tiles.items():
-            groups.setdefault(tuple(t.shape[2:]), []).append(key)
-        enc = {}
-        for keys in groups.values():
-            out = self._encode_tile(torch.cat([tiles[k] for k in keys], 0).contiguous(), precision).permute(0, 3, 1, 2)
-            for k, o in zip(keys, out.split(x.shape[0], 0)):
-                enc[k] = o
-        rows = [[enc[(i, j)] for j in jj] for i in ii]
-        out_rows = []
-        for i, row in enumerate(rows):
-            out = []
-            for j, t in enumerate(row):
-                if i > 0:
-                    t = self._blend(rows[i - 1][j], t, extent, 2)
-                if j > 0:
-                    t = self._blend(row[j - 1], t, extent, 3)
-                row[j] = t               # diffusers blends in place: later tiles see the blended neighbour
-                out.append(t[:, :, :limit, :limit])
-            out_rows.append(torch.cat(out, dim=3))
-        return torch.cat(out_rows, dim=2)
+        blends over int(tile_latent_min_size * overlap) latent rows, crop to tile_latent_min_size - blend_extent.
+        Returns NCHW moments [B, 2 C, h, w]."""
+        lat, px, f = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
+        return self._stitch(x, px, int(px * (1 - f)), int(lat * f), lat - int(lat * f),
+                            lambda t: self._encode_tile(t, precision).permute(0, 3, 1, 2))
 
     @torch.no_grad()
     def encode_moments(self, x, precision=None):
