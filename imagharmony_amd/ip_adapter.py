@@ -56,6 +56,25 @@ from .utils import get_generator  # noqa: E402
 IPAttnProcessor = IPAttnProcessor2_0
 
 
+def _prompts(prompt, negative_prompt, n=None):
+    """the reference's prompt defaults (ip_adapter.py:200-212); n given: a single prompt is broadcast to a list of n"""
+    prompt = prompt if prompt is not None else "best quality, high quality"
+    negative_prompt = negative_prompt if negative_prompt is not None else \
+        "monochrome, lowres, bad anatomy, worst quality, low quality"
+    if n is not None and not isinstance(prompt, List):
+        prompt = [prompt] * n
+    if n is not None and not isinstance(negative_prompt, List):
+        negative_prompt = [negative_prompt] * n
+    return prompt, negative_prompt
+
+
+def _default_batch(n_seeds):
+    """PNS candidates stacked per UNet forward: as many as a rank holds, up to 4"""
+    import torch.distributed as dist
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    return min(4, (n_seeds + world - 1) // world)
+
+
 class IPAdapter:
     """``IPAdapter.__init__`` / ``set_ip_adapter`` / ``load_ip_adapter`` / ``get_image_embeds`` / ``set_scale``
     (ip_adapter.py:70-182).  Differences, all behaviour-compatible: the compute dtype is a parameter (the
@@ -160,6 +179,15 @@ class IPAdapter:
         uncond_image_prompt_embeds = self._g(self.image_proj_model)(torch.zeros_like(clip_image_embeds))
         return image_prompt_embeds, uncond_image_prompt_embeds
 
+    def _hidden_states(self, pil_image, instead):
+        """the Plus variants' input: the penultimate CLIP hidden states [B, 257, hidden] of the images and of an all-zero image"""
+        if self.image_encoder is None or self.clip_image_processor is None:
+            raise NotImplementedError(f"CLIP image encoder not attached: pass {instead}")
+        imgs = pil_image if isinstance(pil_image, (list, tuple)) else [pil_image]
+        px = self.clip_image_processor(images=imgs, return_tensors="pt").pixel_values.to(self.device, dtype=self.dtype)
+        return (self.image_encoder(px, output_hidden_states=True).hidden_states[-2],
+                self.image_encoder(torch.zeros_like(px), output_hidden_states=True).hidden_states[-2])
+
     def set_scale(self, scale):                                           # ip_adapter.py:179-182
         set_scale(self.pipe.unet, scale)
 
@@ -172,13 +200,7 @@ class IPAdapter:
             n = len(pil_image) if isinstance(pil_image, (list, tuple)) else 1
         else:
             n = clip_image_embeds.size(0)
-        prompt = prompt if prompt is not None else "best quality, high quality"
-        negative_prompt = negative_prompt if negative_prompt is not None else \
-            "monochrome, lowres, bad anatomy, worst quality, low quality"
-        if not isinstance(prompt, List):
-            prompt = [prompt] * n
-        if not isinstance(negative_prompt, List):
-            negative_prompt = [negative_prompt] * n
+        prompt, negative_prompt = _prompts(prompt, negative_prompt, n)
         extra = {k: kwargs.pop(k) for k in ("uncond_clip_image_embeds",) if k in kwargs}   # IPAdapterPlus / Full, no CLIP attached
         ipe, uipe = self.get_image_embeds(pil_image=pil_image, clip_image_embeds=clip_image_embeds, **extra)
         bs, seq_len, _ = ipe.shape
@@ -234,13 +256,7 @@ class IPAdapterXL(IPAdapter):
             n = clip_image_embeds.size(0)
         else:
             n = 1 if not isinstance(pil_image, (list, tuple)) else len(pil_image)
-        prompt = prompt if prompt is not None else "best quality, high quality"
-        negative_prompt = negative_prompt if negative_prompt is not None else \
-            "monochrome, lowres, bad anatomy, worst quality, low quality"
-        if not isinstance(prompt, List):
-            prompt = [prompt] * n
-        if not isinstance(negative_prompt, List):
-            negative_prompt = [negative_prompt] * n
+        prompt, negative_prompt = _prompts(prompt, negative_prompt, n)
         if extra_prompt_embeds is None and extra_text is not None:      # ip_adapter.py:285-297 (NameError upstream if None)
             extra_prompt_embeds = self.pipe.encode_prompt(extra_text, num_images_per_prompt=num_samples,
                                                           do_classifier_free_guidance=True,
@@ -280,24 +296,68 @@ class IPAdapterXL(IPAdapter):
         height / width follow the image there.
         Returns dict(images, best_seed, scores, latents)."""
         from . import pns
-        from .pipeline import StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline
+        from .pipeline import (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline, decode_output,
+                               edit_moments)
         seeds = list(seeds)                       # consumed more than once below: a generator passed as `seeds` must survive that
         if judge_preprocess not in ("torch", "hip"):
             raise ValueError(f"judge_preprocess={judge_preprocess!r}: 'torch' or 'hip'")
         if judge_preprocess == "hip" and not hasattr(self.image_encoder, "embed_decoded"):
             raise ValueError('judge_preprocess="hip" needs the HIP CLIP vision tower as the image encoder '
                              '(image_encoder_backend="hip" / image_encoder=CLIPVisionEncoder)')
-        if isinstance(self.pipe, (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline)):
-            return self._generate_pns_edit(seeds, pil_image, prompt, negative_prompt, extra_text, scale, preview_steps, num_inference_steps,
-                                           guidance_scale, scorer, batch, clip_image_embeds, prompt_embeds, extra_prompt_embeds, output_type,
-                                           step_noise, image, mask_image, strength, judge_preprocess, schedule_kw)
-        if image is not None or mask_image is not None or strength is not None:
-            raise ValueError("image= / mask_image= / strength= belong to an image-to-image or inpainting pipeline")
+        pipe = self.pipe
+        inpaint = isinstance(pipe, StableDiffusionXLInpaintCustomPipeline)
+        edit = inpaint or isinstance(pipe, StableDiffusionXLImg2ImgCustomPipeline)
+        if edit:
+            img, mask, strength = self._pns_edit_inputs(image, mask_image, strength, preview_steps, num_inference_steps, output_type, step_noise)
+            height, width = int(img.shape[2]), int(img.shape[3])
+        else:
+            if image is not None or mask_image is not None or strength is not None:
+                raise ValueError("image= / mask_image= / strength= belong to an image-to-image or inpainting pipeline")
+            if output_type != "latent" and pipe.vae is None and pipe.vae_decode is None:
+                raise NotImplementedError("output_type=%r needs a VAE on the pipeline; pass output_type='latent'" % (output_type,))
+            height = height or pipe.default_sample_size * pipe.vae_scale_factor
+            width = width or pipe.default_sample_size * pipe.vae_scale_factor
+        h, w = height // 8, width // 8
+        fused, cond = self._pns_setup(scale, pil_image, clip_image_embeds, prompt, negative_prompt, extra_text, prompt_embeds, extra_prompt_embeds)
+        S = max(1, int(_default_batch(len(seeds)) if batch is None else batch))
+        eng = pipe.engine
+        if edit:
+            # everything a candidate shares is computed once, the moments at batch 1 as the pipelines encode a per-sample-generator call;
+            # a candidate costs its draws, one fused initial-latents launch (stacked ``batch`` per call) and the truncated denoise
+            from .vae import latent_mask
+            concat = inpaint and pipe.unet.config.in_channels == 9
+            moments, masked_moments = edit_moments(pipe.vae, img, True, 9 if concat else 4, float(strength) == 1.0, mask)
+            prepare = pns.edit_prepare_fn(eng, pipe.scheduler, pipe.vae.config.scaling_factor, moments, h, w, strength,
+                                          mask=latent_mask(mask, h, w) if inpaint else None, masked_moments=masked_moments, concat=concat)
+            stages = pns.edit_two_stage_fns(eng, pipe.scheduler, prepare, strength, preview_steps, num_inference_steps,
+                                            step_noise=step_noise, inpaint=inpaint, **schedule_kw)
+        else:
+            stages = pns.two_stage_fns(eng, pipe.scheduler, preview_steps, num_inference_steps, step_noise=step_noise, **schedule_kw)
+        if scorer is None:
+            scorer = self._default_scorer(pipe.vae, fused, judge_preprocess)
+        state = {"n": None}
+
+        def stacked(stage):
+            """the stage function behind a re-conditioning whenever the stack size changes"""
+            def fn(noise, **kw):
+                n = noise.shape[0]
+                if state["n"] != n:
+                    eng.set_conditioning(*(t.repeat(*([n] + [1] * (t.ndim - 1))) for t in cond), height, width, guidance_scale=guidance_scale)
+                    state["n"] = n
+                return stage(noise, **kw)
+            return fn
+
+        r = pns.run_pns(stacked(stages[0]), seeds, (1, 4, h, w), scorer=scorer, device=self.device, final_fn=stacked(stages[1]), batch=S,
+                        pass_seeds=edit or step_noise == "seed")
+        out = decode_output(pipe.vae, pipe.vae_decode, r["latents"], output_type)
+        return dict(images=out, best_seed=r["best_seed"], scores=r["scores"], latents=r["latents"])
+
+    def _pns_setup(self, scale, pil_image, clip_image_embeds, prompt, negative_prompt, extra_text, prompt_embeds, extra_prompt_embeds):
+        """what the candidates of a generate_pns call share -> (the fused CLIP embedding the default judge scores against, the conditioning
+        of one sample (pe, ne, ppe, npe) with the image tokens appended)"""
         self.set_scale(scale)
         pipe = self.pipe
-        prompt = prompt if prompt is not None else "best quality, high quality"
-        negative_prompt = negative_prompt if negative_prompt is not None else \
-            "monochrome, lowres, bad anatomy, worst quality, low quality"
+        prompt, negative_prompt = _prompts(prompt, negative_prompt)
         if extra_prompt_embeds is None and extra_text is not None:
             extra_prompt_embeds = pipe.encode_prompt(extra_text, num_images_per_prompt=1, do_classifier_free_guidance=True,
                                                      negative_prompt=negative_prompt)[0]
@@ -310,69 +370,25 @@ class IPAdapterXL(IPAdapter):
         pe, ne, ppe, npe = prompt_embeds
         pe = torch.cat([pe.to(ipe.device, self.dtype), ipe], dim=1)
         ne = torch.cat([ne.to(ipe.device, self.dtype), uipe], dim=1)
-        height = height or pipe.default_sample_size * pipe.vae_scale_factor
-        width = width or pipe.default_sample_size * pipe.vae_scale_factor
-        if batch is None:
-            import torch.distributed as dist
-            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-            batch = min(4, (len(seeds) + world - 1) // world)
-        S = max(1, int(batch))
-        eng = pipe.engine
-        rep = lambda t, n: t.repeat(*([n] + [1] * (t.ndim - 1)))
-        if scorer is None:
-            if pipe.vae is not None and self.image_encoder is not None:
-                from .vae import decode_latents
-                scorer = pns.ClipPreferenceJudge(lambda z: decode_latents(pipe.vae, z), self.image_encoder, fused,
-                                                 **({"preprocess_backend": "hip"} if judge_preprocess == "hip" else {}))
-            else:
-                scorer = pns.default_scorer
-        shape = (1, 4, height // 8, width // 8)
+        return fused, (pe, ne, ppe.to(ipe.device), npe.to(ipe.device))
 
-        def cond(n):
-            eng.set_conditioning(rep(pe, n), rep(ne, n), rep(ppe.to(ipe.device), n), rep(npe.to(ipe.device), n), height, width,
-                                 guidance_scale=guidance_scale)
-
-        state = {"n": None}
-        if step_noise not in ("global", "seed"):
-            raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
-        by_seed = step_noise == "seed"
-        stage_pre, stage_fin = pns.two_stage_fns(eng, pipe.scheduler, preview_steps, num_inference_steps, step_noise=step_noise, **schedule_kw)
-
-        def preview(noise, **kw):
-            if state["n"] != noise.shape[0]:
-                cond(noise.shape[0]); state["n"] = noise.shape[0]
-            return stage_pre(noise, **kw)
-
-        def final(noise, **kw):
-            if state["n"] != noise.shape[0]:
-                cond(noise.shape[0]); state["n"] = noise.shape[0]
-            return stage_fin(noise, **kw)
-
-        r = pns.run_pns(preview, seeds, shape, scorer=scorer, device=self.device, final_fn=final, batch=S, **({"pass_seeds": True} if by_seed else {}))
-        out = r["latents"]
-        if output_type != "latent":
-            if pipe.vae is None and pipe.vae_decode is None:
-                raise NotImplementedError("output_type=%r needs a VAE on the pipeline; pass output_type='latent'" % (output_type,))
-            if pipe.vae is not None:
-                from .vae import decode_latents, postprocess
-                out = postprocess(decode_latents(pipe.vae, out), output_type)
-            else:
-                out = pipe.vae_decode(out)
-        return dict(images=out, best_seed=r["best_seed"], scores=r["scores"], latents=r["latents"])
-
-    def _generate_pns_edit(self, seeds, pil_image, prompt, negative_prompt, extra_text, scale, preview_steps, num_inference_steps,
-                           guidance_scale, scorer, batch, clip_image_embeds, prompt_embeds, extra_prompt_embeds, output_type, step_noise,
-                           image, mask_image, strength, judge_preprocess, schedule_kw):
-        """generate_pns on an image-to-image / inpainting pipe (its docstring states the contract): everything a candidate shares -- the
-        conditioning, the encoder moments of the image (and masked image), the latent mask -- is computed once; a candidate costs its
-        draws, one fused initial-latents launch (stacked ``batch`` per call) and the truncated denoise."""
+    def _default_scorer(self, vae, fused, judge_preprocess):
+        """the CLIP-space judge when a VAE and a CLIP vision model are attached, else the latent statistic"""
         from . import pns
+        if vae is None or self.image_encoder is None:
+            return pns.default_scorer
+        from .vae import decode_latents
+        return pns.ClipPreferenceJudge(lambda z: decode_latents(vae, z), self.image_encoder, fused,
+                                       **({"preprocess_backend": "hip"} if judge_preprocess == "hip" else {}))
+
+    def _pns_edit_inputs(self, image, mask_image, strength, preview_steps, num_inference_steps, output_type, step_noise):
+        """generate_pns on an image-to-image / inpainting pipe (its docstring states the contract): the refusals, all before any GPU work
+        -> (the preprocessed image [1, 3, H, W], the mask [1, 1, H, W] or None, the strength)"""
         from .pipeline import StableDiffusionXLInpaintCustomPipeline
         from .schedulers import get_timesteps
-        from .vae import latent_mask, preprocess, preprocess_mask
+        from .vae import preprocess, preprocess_mask
         pipe = self.pipe
         inpaint = isinstance(pipe, StableDiffusionXLInpaintCustomPipeline)
-        # refusals first, before any GPU work
         if step_noise not in ("global", "seed"):
             raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
         if image is None:
@@ -396,78 +412,12 @@ class IPAdapterXL(IPAdapter):
         img = preprocess(image)
         if img.shape[0] != 1:
             raise ValueError(f"PNS edits one image (the candidates are its seeds), got a batch of {img.shape[0]}")
-        height, width = int(img.shape[2]), int(img.shape[3])
-        h, w = height // 8, width // 8
         mask = None
         if inpaint:
-            mask = preprocess_mask(mask_image, height, width)
+            mask = preprocess_mask(mask_image, int(img.shape[2]), int(img.shape[3]))
             if mask.shape[0] != 1:
                 raise ValueError(f"PNS edits one image under one mask, got a mask batch of {mask.shape[0]}")
-        self.set_scale(scale)
-        prompt = prompt if prompt is not None else "best quality, high quality"
-        negative_prompt = negative_prompt if negative_prompt is not None else \
-            "monochrome, lowres, bad anatomy, worst quality, low quality"
-        if extra_prompt_embeds is None and extra_text is not None:
-            extra_prompt_embeds = pipe.encode_prompt(extra_text, num_images_per_prompt=1, do_classifier_free_guidance=True,
-                                                     negative_prompt=negative_prompt)[0]
-        fused = self.fused_clip_embeds(pil_image, clip_image_embeds, extra_prompt_embeds)
-        ipe = self._g(self.image_proj_model)(fused)
-        uipe = self._g(self.image_proj_model)(torch.zeros_like(fused))
-        if prompt_embeds is None:
-            prompt_embeds = pipe.encode_prompt(prompt, num_images_per_prompt=1, do_classifier_free_guidance=True,
-                                               negative_prompt=negative_prompt)
-        pe, ne, ppe, npe = prompt_embeds
-        pe = torch.cat([pe.to(ipe.device, self.dtype), ipe], dim=1)
-        ne = torch.cat([ne.to(ipe.device, self.dtype), uipe], dim=1)
-        if batch is None:
-            import torch.distributed as dist
-            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-            batch = min(4, (len(seeds) + world - 1) // world)
-        S = max(1, int(batch))
-        eng, vae = pipe.engine, pipe.vae
-        rep = lambda t, n: t.repeat(*([n] + [1] * (t.ndim - 1)))      # noqa: E731
-        # encoded once, at batch 1 as the pipelines encode a per-sample-generator call
-        concat = inpaint and pipe.unet.config.in_channels == 9
-        need_z = not concat or float(strength) != 1.0                # (9 channels at strength 1.0: nothing reads the image latents)
-        moments = vae.encode_moments(img).clone() if need_z else None
-        masked_moments = vae.encode_moments(img * (mask < 0.5)).clone() if concat else None
-        lmask = latent_mask(mask, h, w) if inpaint else None
-        if scorer is None:
-            if self.image_encoder is not None:
-                from .vae import decode_latents
-                scorer = pns.ClipPreferenceJudge(lambda z: decode_latents(vae, z), self.image_encoder, fused,
-                                                 **({"preprocess_backend": "hip"} if judge_preprocess == "hip" else {}))
-            else:
-                scorer = pns.default_scorer
-        prepare = pns.edit_prepare_fn(eng, pipe.scheduler, vae.config.scaling_factor, moments, h, w, strength, mask=lmask,
-                                      masked_moments=masked_moments, concat=concat)
-        stage_pre, stage_fin = pns.edit_two_stage_fns(eng, pipe.scheduler, prepare, strength, preview_steps, num_inference_steps,
-                                                      step_noise=step_noise, inpaint=inpaint, **schedule_kw)
-        state = {"n": None}
-
-        def cond(n):
-            if state["n"] != n:
-                eng.set_conditioning(rep(pe, n), rep(ne, n), rep(ppe.to(ipe.device), n), rep(npe.to(ipe.device), n), height, width,
-                                     guidance_scale=guidance_scale)
-                state["n"] = n
-
-        def preview(noise, seeds=None):
-            cond(noise.shape[0])
-            return stage_pre(seeds=seeds)
-
-        def final(noise, seeds=None):
-            cond(noise.shape[0])
-            return stage_fin(seeds=seeds)
-
-        r = pns.run_pns(preview, seeds, (1, 4, h, w), scorer=scorer, device=self.device, final_fn=final, batch=S, pass_seeds=True)
-        out = r["latents"]
-        if output_type != "latent":
-            if pipe.vae is not None:
-                from .vae import decode_latents, postprocess
-                out = postprocess(decode_latents(pipe.vae, out), output_type)
-            else:
-                out = pipe.vae_decode(out)
-        return dict(images=out, best_seed=r["best_seed"], scores=r["scores"], latents=r["latents"])
+        return img, mask, strength
 
 
 class IPAdapterPlus(IPAdapter):
@@ -484,12 +434,7 @@ class IPAdapterPlus(IPAdapter):
         """clip_image_embeds here = penultimate hidden states [B, 257, hidden] (as upstream names them); without an
         attached CLIP model pass them together with ``uncond_clip_image_embeds`` (hidden states of a zero image)."""
         if pil_image is not None:
-            if self.image_encoder is None or self.clip_image_processor is None:
-                raise NotImplementedError("CLIP image encoder not attached: pass clip_image_embeds (hidden states)")
-            imgs = pil_image if isinstance(pil_image, (list, tuple)) else [pil_image]
-            px = self.clip_image_processor(images=imgs, return_tensors="pt").pixel_values.to(self.device, dtype=self.dtype)
-            clip_image_embeds = self.image_encoder(px, output_hidden_states=True).hidden_states[-2]
-            uncond_clip_image_embeds = self.image_encoder(torch.zeros_like(px), output_hidden_states=True).hidden_states[-2]
+            clip_image_embeds, uncond_clip_image_embeds = self._hidden_states(pil_image, "clip_image_embeds (hidden states)")
         if uncond_clip_image_embeds is None:
             raise NotImplementedError("pass uncond_clip_image_embeds (CLIP hidden states of an all-zero image)")
         c = clip_image_embeds.to(self.device, self.dtype)
@@ -516,12 +461,7 @@ class IPAdapterPlusXL(IPAdapter):
     @torch.inference_mode()
     def get_image_embeds(self, pil_image=None, clip_hidden_states=None, uncond_clip_hidden_states=None):   # :405-417
         if pil_image is not None:
-            if self.image_encoder is None or self.clip_image_processor is None:
-                raise NotImplementedError("CLIP image encoder not attached: pass clip_hidden_states")
-            imgs = pil_image if isinstance(pil_image, (list, tuple)) else [pil_image]
-            px = self.clip_image_processor(images=imgs, return_tensors="pt").pixel_values.to(self.device, dtype=self.dtype)
-            clip_hidden_states = self.image_encoder(px, output_hidden_states=True).hidden_states[-2]
-            uncond_clip_hidden_states = self.image_encoder(torch.zeros_like(px), output_hidden_states=True).hidden_states[-2]
+            clip_hidden_states, uncond_clip_hidden_states = self._hidden_states(pil_image, "clip_hidden_states")
         c = clip_hidden_states.to(self.device, self.dtype)
         u = uncond_clip_hidden_states.to(self.device, self.dtype)
         return self._g(self.image_proj_model)(c), self._g(self.image_proj_model)(u)
@@ -534,12 +474,6 @@ class IPAdapterPlusXL(IPAdapter):
             n = clip_hidden_states.size(0)
         else:
             n = 1 if not isinstance(pil_image, (list, tuple)) else len(pil_image)
-        prompt = prompt if prompt is not None else "best quality, high quality"
-        negative_prompt = negative_prompt if negative_prompt is not None else \
-            "monochrome, lowres, bad anatomy, worst quality, low quality"
-        if not isinstance(prompt, List):
-            prompt = [prompt] * n
-        if not isinstance(negative_prompt, List):
-            negative_prompt = [negative_prompt] * n
+        prompt, negative_prompt = _prompts(prompt, negative_prompt, n)
         ipe, uipe = self.get_image_embeds(pil_image, clip_hidden_states, uncond_clip_hidden_states)
         return self._run(ipe, uipe, prompt, negative_prompt, num_samples, seed, num_inference_steps, prompt_embeds, kwargs)

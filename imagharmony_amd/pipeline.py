@@ -4,6 +4,7 @@ embeddings in, latents out.  Text encoders, the VAE decode and PIL post-processi
 SURVEY.md 8(f) marks "next"; they can be plugged in (``vae_decode`` / ``text_encoder`` callables) but are
 not part of this library.
 """
+import types
 from dataclasses import dataclass
 from typing import Any, Callable, List, Optional, Union
 
@@ -29,6 +30,140 @@ def randn_latents(shape, generator=None, dtype=torch.float32):
                           for g in generator], 0)
     dev = generator.device if generator is not None else "cpu"
     return torch.randn(tuple(shape), generator=generator, device=dev, dtype=dtype).cpu()
+
+
+def decode_output(vae, vae_decode, latents, output_type, watermark=None):
+    """custom_pipelines.py:365-386, the tail of every pipeline call and of generate_pns: 'latent' returns the latents; with ``vae`` (an
+    ``imagharmony_amd.vae.AutoencoderKL``) the HIP decode, the watermark if any and the post-processing; else ``vae_decode(latents)``"""
+    if output_type == "latent":
+        return latents
+    if vae is None:
+        return vae_decode(latents)
+    from .vae import decode_latents, postprocess
+    image = decode_latents(vae, latents)
+    if watermark is not None:
+        image = watermark.apply_watermark(image)
+    return postprocess(image, output_type)
+
+
+# An edit's preparation (image-to-image, inpainting), stated once: the pipelines' __call__ and PNS over edits (pns.edit_prepare_fn,
+# IPAdapterXL.generate_pns) both go through these three functions, so a PNS winner is the pipe's own call with that seed's generator.
+
+def edit_moments(vae, img, per_sample, cin=4, strength_max=False, mask=None):
+    """What an edit encodes, and at which batch -> (moments, masked_moments); either may be None.  The image's moments are read by a
+    4-channel UNet and below strength 1.0 (is_strength_max); a 9-channel UNet also reads those of the masked image
+    ``img * (mask < 0.5)`` (prepare_mask_latents), image and mask batch repeated to the larger of the two.  per_sample (the generator is
+    a list): every image is encoded on its own, at batch 1 as diffusers encodes them, and read by index."""
+    masked = None
+    if cin == 9:
+        B, Mb = img.shape[0], mask.shape[0]
+        Bm = max(B, Mb)
+        if Bm % B or Bm % Mb:
+            raise ValueError(f"cannot pair an image batch of {B} with a mask batch of {Mb}")
+        masked = img.repeat(Bm // B, 1, 1, 1) * (mask.repeat(Bm // Mb, 1, 1, 1) < 0.5)
+    need_z = cin == 4 or not strength_max
+    encode = (lambda x: torch.cat([vae.encode_moments(x[j:j + 1]) for j in range(x.shape[0])], 0)) if per_sample else vae.encode_moments
+    return encode(img) if need_z else None, encode(masked) if masked is not None else None
+
+
+def edit_draws(generator, S, B, h, w, Bm=None):
+    """An edit's draws from ``generator`` (one, or a list with one per sample), in upstream's order -> (n1, n2, n3 or None), fp32 on the
+    CPU: the posterior noise of the image (prepare_latents; one generator: one draw per image, B rows, repeated S // B times; a list: S
+    rows), the add-noise noise (S rows) and -- Bm given: a 9-channel UNet with Bm masked images -- the posterior noise of the masked
+    image (prepare_mask_latents).  The first draw is made even where nothing reads it, so that the order holds in every mode."""
+    per_sample = isinstance(generator, (list, tuple))
+    n1 = randn_latents((S if per_sample else B, 4, h, w), generator)
+    n2 = randn_latents((S, 4, h, w), generator)
+    return n1, n2, (randn_latents((S if per_sample else Bm, 4, h, w), generator) if Bm else None)
+
+
+def edit_prepare(engine, scheduler, t_start, scaling, moments, draws, lmask=None, strength_max=False, masked_moments=None):
+    """The hand-over: the initial latents of a schedule that starts at its row t_start -- and, inpainting (lmask: the latent mask), the
+    blend / conv_in state -- written into the engine by one fused launch, under the schedule set_schedule has just set"""
+    n1, n2, n3 = draws
+    a, b = scheduler.add_noise_coefficients(t_start)
+    if lmask is None:
+        return engine.prepare_img2img(moments, n1, n2, scaling, a, b)
+    return engine.prepare_inpaint(moments, n1, n2, scaling, a, b, lmask, strength_max=strength_max, masked_moments=masked_moments, n3=n3)
+
+
+class _Call(types.SimpleNamespace):
+    """One __call__ of a pipeline: its arguments by name (its locals() on entry) and, in four hooks, what that __call__ adds to the
+    sequence of StableDiffusionXLCustomPipeline._run -- begin (its refusals; height / width), schedule_kw (the refusals that need the
+    batch; set_schedule's extra keywords), condition (the engine calls around set_conditioning) and start (how the initial latents
+    reach the engine: returned for denoise, or written into it and None).  The hooks go with the __call__, not with the pipe's class:
+    the base class's __call__ on an image-to-image or inpainting pipe is a text-to-image call.  This class: text-to-image."""
+
+    def __init__(self, ns):
+        super().__init__(**{k: v for k, v in ns.items() if k != "self"})
+
+    def begin(self, pipe):
+        self.height = self.height or pipe.default_sample_size * pipe.vae_scale_factor      # :189-190
+        self.width = self.width or pipe.default_sample_size * pipe.vae_scale_factor
+
+    def schedule_kw(self, pipe, S):
+        return {}
+
+    def condition(self, pipe, eng):
+        eng.set_conditioning(self.prompt_embeds, self.negative_prompt_embeds, self.pooled_prompt_embeds, self.negative_pooled_prompt_embeds,
+                             self.height, self.width, self.guidance_scale, guidance_rescale=self.guidance_rescale,
+                             original_size=self.original_size, crops_coords_top_left=self.crops_coords_top_left, target_size=self.target_size)
+
+    def start(self, pipe, eng, S):
+        if self.latents is not None:
+            return self.latents
+        return randn_latents((S, 4, self.height // 8, self.width // 8), self.generator)       # prepare_latents :255-265
+
+
+class _EditCall(_Call):
+    """What the image-to-image and the inpainting __call__ share: the refusals around ``image``, the batch checks, the schedule truncated
+    by ``strength`` and, in place of initial noise, the edit preparation above."""
+
+    def __init__(self, ns, edit="image-to-image"):
+        super().__init__(ns)
+        self.edit, self.inpaint = edit, edit == "inpainting"
+
+    def begin(self, pipe):
+        if self.latents is not None:
+            raise NotImplementedError(f"latents= is not supported by the {self.edit} path: the initial latents come from `image`")
+        if self.image is None:
+            raise ValueError(f"{self.edit} needs `image` (PIL, a list of PIL images or a tensor [B, 3, H, W])")
+        if self.inpaint and self.mask_image is None:
+            raise ValueError("inpainting needs `mask_image` (PIL, a list of PIL images or a tensor; white = repaint)")
+        if torch.is_tensor(self.image) and self.image.dim() >= 3 and self.image.shape[-3] == 4:
+            raise NotImplementedError("a 4-channel latent `image` is not supported: pass the image itself")
+        if not 0.0 <= float(self.strength) <= 1.0:
+            raise ValueError(f"strength must be in [0.0, 1.0], got {self.strength}")
+        from .vae import preprocess, preprocess_mask
+        self.img, self.mask = preprocess(self.image), None                   # image_processor.preprocess
+        H, W = self.img.shape[2], self.img.shape[3]
+        if self.inpaint:
+            if (self.height or H, self.width or W) != (H, W):
+                raise NotImplementedError(f"height / width {self.height} x {self.width} differ from the image's {H} x {W}: resize the image first")
+            self.mask = preprocess_mask(self.mask_image, H, W)               # mask_processor.preprocess
+        if pipe.vae is None or not getattr(pipe.vae, "with_encoder", False):
+            raise NotImplementedError(f"{self.edit} needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
+        self.height, self.width = H, W
+
+    def schedule_kw(self, pipe, S):
+        if isinstance(self.generator, (list, tuple)) and len(self.generator) != S:
+            raise ValueError(f"got {len(self.generator)} generators for a batch of {S}")
+        for what, t in (("an image", self.img), ("a mask", self.mask)):      # prepare_latents, prepare_mask_latents
+            if t is not None and (S < t.shape[0] or S % t.shape[0]):
+                raise ValueError(f"cannot duplicate {what} batch of {t.shape[0]} to {S} samples")
+        pipe.scheduler.set_timesteps(self.num_inference_steps)
+        _, self.t_start = get_timesteps(pipe.scheduler, self.num_inference_steps, self.strength)
+        return dict(t_start=self.t_start, **({"inpaint": True} if self.inpaint else {}))
+
+    def start(self, pipe, eng, S):
+        from .vae import latent_mask
+        h, w = self.height // 8, self.width // 8
+        cin = pipe.unet.config.in_channels if self.inpaint else 4           # num_channels_unet
+        strength_max = self.inpaint and float(self.strength) == 1.0         # is_strength_max
+        moments, masked_moments = edit_moments(pipe.vae, self.img, isinstance(self.generator, (list, tuple)), cin, strength_max, self.mask)
+        draws = edit_draws(self.generator, S, self.img.shape[0], h, w, Bm=max(self.img.shape[0], self.mask.shape[0]) if cin == 9 else None)
+        edit_prepare(eng, pipe.scheduler, self.t_start, pipe.vae.config.scaling_factor, moments, draws,
+                     latent_mask(self.mask, h, w) if self.inpaint else None, strength_max, masked_moments)
 
 
 class StableDiffusionXLCustomPipeline:
@@ -95,28 +230,30 @@ class StableDiffusionXLCustomPipeline:
         ``generator`` on the host, in diffusers' order; "seeded" generates it on the device from the generators' seeds (step_seed_table:
         one generator -> its initial_seed() with lane = sample index, a list -> each generator's own seed with lane 0), so that a seed
         reproduces its image whatever the batch -- it needs a generator (ValueError without one)."""
-        self._refuse(output_type, eta, kwargs)
-        seed_tab = self.step_seed_table(step_noise, generator, None)
-        height = height or self.default_sample_size * self.vae_scale_factor      # :189-190
-        width = width or self.default_sample_size * self.vae_scale_factor
-        if prompt_embeds is None:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
-        if pooled_prompt_embeds is None:
+        return self._run(_Call(locals()))
+
+    def _run(self, c: _Call):
+        """The call sequence of every pipeline class, once; c: the __call__'s arguments and hooks.  Refusals of arguments that only one
+        __call__ has come before, in that __call__."""
+        self._refuse(c.output_type, c.eta, c.kwargs)
+        self.step_seed_table(c.step_noise, c.generator, None)
+        c.begin(self)
+        if c.prompt_embeds is None:
+            c.prompt_embeds, c.negative_prompt_embeds, c.pooled_prompt_embeds, c.negative_pooled_prompt_embeds = \
+                self.encode_prompt(c.prompt, c.num_images_per_prompt, c.guidance_scale > 1.0, c.negative_prompt)
+        if c.pooled_prompt_embeds is None:
             raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
-        S = prompt_embeds.shape[0]
+        S = c.prompt_embeds.shape[0]
+        schedule_kw = c.schedule_kw(self, S)
         eng = self.engine
-        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
-                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
-                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
-        seed_tab = self.step_seed_table(step_noise, generator, S)
-        eng.set_schedule(self.scheduler, num_inference_steps, control_guidance_start, control_guidance_end,
-                         denoising_end=denoising_end, **({"seeded_noise": True} if seed_tab else {}))
-        if latents is None:
-            latents = randn_latents((S, 4, height // 8, width // 8), generator)       # prepare_latents :255-265
-        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
-        out = self._output(out, output_type)
-        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+        c.condition(self, eng)
+        seed_tab = self.step_seed_table(c.step_noise, c.generator, S)
+        eng.set_schedule(self.scheduler, c.num_inference_steps, c.control_guidance_start, c.control_guidance_end,
+                         denoising_end=c.denoising_end, **schedule_kw, **({"seeded_noise": True} if seed_tab else {}))
+        latents = c.start(self, eng, S)
+        out = eng.denoise(latents, callback=c.callback, callback_steps=c.callback_steps, **self._noise_kw(eng, seed_tab, c.generator)).clone()
+        out = self._output(out, c.output_type)
+        return StableDiffusionXLPipelineOutput(images=out) if c.return_dict else (out,)
 
     @staticmethod
     def step_seed_table(step_noise, generator, S):
@@ -158,16 +295,7 @@ class StableDiffusionXLCustomPipeline:
                 raise NotImplementedError(f"{k} is not supported on this path (custom_pipelines.py:23-56 accepts it for diffusers' sake)")
 
     def _output(self, out, output_type):
-        if output_type != "latent":                                       # custom_pipelines.py:365-386
-            if self.vae is not None:
-                from .vae import decode_latents, postprocess
-                image = decode_latents(self.vae, out)
-                if self.watermark is not None:
-                    image = self.watermark.apply_watermark(image)
-                out = postprocess(image, output_type)
-            else:
-                out = self.vae_decode(out)
-        return out
+        return out if output_type == "latent" else decode_output(self.vae, self.vae_decode, out, output_type, self.watermark)
 
 
 class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
@@ -196,59 +324,7 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
         strength outside [0, 1] or a schedule that truncates to no step (ValueError)."""
         if denoising_start is not None:
             raise NotImplementedError("denoising_start (the refiner hand-off) is not supported on this path")
-        self._refuse(output_type, eta, kwargs)
-        self.step_seed_table(step_noise, generator, None)
-        if latents is not None:
-            raise NotImplementedError("latents= is not supported by the image-to-image path: the initial latents come from `image`")
-        if image is None:
-            raise ValueError("image-to-image needs `image` (PIL, a list of PIL images or a tensor [B, 3, H, W])")
-        if torch.is_tensor(image) and image.dim() >= 3 and image.shape[-3] == 4:
-            raise NotImplementedError("a 4-channel latent `image` is not supported: pass the image itself")
-        if not 0.0 <= float(strength) <= 1.0:
-            raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
-        from .vae import preprocess
-        img = preprocess(image)
-        if self.vae is None or not getattr(self.vae, "with_encoder", False):
-            raise NotImplementedError("image-to-image needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
-        height, width = img.shape[2], img.shape[3]
-        if prompt_embeds is None:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
-        if pooled_prompt_embeds is None:
-            raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
-        S = prompt_embeds.shape[0]
-        B = img.shape[0]
-        if isinstance(generator, (list, tuple)) and len(generator) != S:
-            raise ValueError(f"got {len(generator)} generators for a batch of {S}")
-        if S < B or S % B:
-            raise ValueError(f"cannot duplicate an image batch of {B} to {S} samples")
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        _, t_start = get_timesteps(sch, num_inference_steps, strength)
-        eng = self.engine
-        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
-                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
-                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
-        seed_tab = self.step_seed_table(step_noise, generator, S)
-        eng.set_schedule(sch, num_inference_steps, control_guidance_start, control_guidance_end, denoising_end=denoising_end,
-                         t_start=t_start, **({"seeded_noise": True} if seed_tab else {}))
-        # prepare_latents: the posterior sample of every sample's image, then the add-noise noise, drawn in diffusers' order
-        h, w = height // 8, width // 8
-        vae = self.vae
-        if isinstance(generator, (list, tuple)):
-            # sample i encodes image[i % B] (the image batch repeated) and samples its posterior with generator[i]; the B distinct images
-            # are encoded once each, at batch 1 as diffusers encodes them, and read by index
-            moments = torch.cat([vae.encode_moments(img[j:j + 1]) for j in range(B)], 0)
-            n1 = randn_latents((S, 4, h, w), generator)
-        else:
-            moments = vae.encode_moments(img)
-            n1 = randn_latents((B, 4, h, w), generator)                     # one posterior draw per image, repeated S // B times
-        n2 = randn_latents((S, 4, h, w), generator)
-        a, b = sch.add_noise_coefficients(t_start)
-        eng.prepare_img2img(moments, n1, n2, vae.config.scaling_factor, a, b)
-        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
-        out = self._output(out, output_type)
-        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+        return self._run(_EditCall(locals()))
 
 
 class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
@@ -294,77 +370,7 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
             raise NotImplementedError("padding_mask_crop (crop, inpaint, overlay) is not supported on this path")
         if masked_image_latents is not None:
             raise NotImplementedError("masked_image_latents= is not supported: the masked image is encoded from `image` and `mask_image`")
-        self._refuse(output_type, eta, kwargs)
-        self.step_seed_table(step_noise, generator, None)
-        if latents is not None:
-            raise NotImplementedError("latents= is not supported by the inpainting path: the initial latents come from `image`")
-        if image is None:
-            raise ValueError("inpainting needs `image` (PIL, a list of PIL images or a tensor [B, 3, H, W])")
-        if mask_image is None:
-            raise ValueError("inpainting needs `mask_image` (PIL, a list of PIL images or a tensor; white = repaint)")
-        if torch.is_tensor(image) and image.dim() >= 3 and image.shape[-3] == 4:
-            raise NotImplementedError("a 4-channel latent `image` is not supported: pass the image itself")
-        if not 0.0 <= float(strength) <= 1.0:
-            raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
-        from .vae import latent_mask, preprocess, preprocess_mask
-        img = preprocess(image)                                              # image_processor.preprocess
-        if (height or img.shape[2], width or img.shape[3]) != tuple(img.shape[2:]):
-            raise NotImplementedError(f"height / width {height} x {width} differ from the image's {img.shape[2]} x {img.shape[3]}: resize the image first")
-        height, width = img.shape[2], img.shape[3]
-        mask = preprocess_mask(mask_image, height, width)                    # mask_processor.preprocess
-        cin = self.unet.config.in_channels                                   # num_channels_unet
-        if self.vae is None or not getattr(self.vae, "with_encoder", False):
-            raise NotImplementedError("inpainting needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
-        if prompt_embeds is None:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
-        if pooled_prompt_embeds is None:
-            raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
-        S = prompt_embeds.shape[0]
-        B, Mb = img.shape[0], mask.shape[0]
-        if isinstance(generator, (list, tuple)) and len(generator) != S:
-            raise ValueError(f"got {len(generator)} generators for a batch of {S}")
-        if S < B or S % B:
-            raise ValueError(f"cannot duplicate an image batch of {B} to {S} samples")
-        if S < Mb or S % Mb:                                                 # prepare_mask_latents
-            raise ValueError(f"cannot duplicate a mask batch of {Mb} to {S} samples")
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        _, t_start = get_timesteps(sch, num_inference_steps, strength)
-        strength_max = float(strength) == 1.0                                # is_strength_max
-        eng = self.engine
-        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
-                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
-                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
-        seed_tab = self.step_seed_table(step_noise, generator, S)
-        eng.set_schedule(sch, num_inference_steps, control_guidance_start, control_guidance_end, denoising_end=denoising_end,
-                         t_start=t_start, inpaint=True, **({"seeded_noise": True} if seed_tab else {}))
-        h, w = height // 8, width // 8
-        vae = self.vae
-        per_sample = isinstance(generator, (list, tuple))
-        # prepare_latents: posterior sample of the image, then the add-noise noise (the image-to-image order)
-        need_z = cin == 4 or not strength_max
-        moments = None
-        if need_z:
-            moments = torch.cat([vae.encode_moments(img[j:j + 1]) for j in range(B)], 0) if per_sample else vae.encode_moments(img)
-        n1 = randn_latents((S if per_sample else B, 4, h, w), generator)
-        n2 = randn_latents((S, 4, h, w), generator)
-        masked_moments = n3 = None
-        if cin == 9:
-            # prepare_mask_latents: masked_image = init_image * (mask < 0.5), encoded and sampled after the two draws above
-            Bm = max(B, Mb)
-            if Bm % B or Bm % Mb:
-                raise ValueError(f"cannot pair an image batch of {B} with a mask batch of {Mb}")
-            masked = img.repeat(Bm // B, 1, 1, 1) * (mask.repeat(Bm // Mb, 1, 1, 1) < 0.5)
-            masked_moments = torch.cat([vae.encode_moments(masked[j:j + 1]) for j in range(Bm)], 0) if per_sample \
-                else vae.encode_moments(masked)
-            n3 = randn_latents((S if per_sample else Bm, 4, h, w), generator)
-        a, b = sch.add_noise_coefficients(t_start)
-        eng.prepare_inpaint(moments, n1, n2, vae.config.scaling_factor, a, b, latent_mask(mask, h, w), strength_max=strength_max,
-                            masked_moments=masked_moments, n3=n3)
-        out = eng.denoise(None, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
-        out = self._output(out, output_type)
-        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+        return self._run(_EditCall(locals(), "inpainting"))
 
 
 def prepare_control_image(image, height, width):
@@ -392,6 +398,24 @@ def prepare_control_image(image, height, width):
             im = im.resize((width, height), resample=Image.LANCZOS)
         out.append(torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0).permute(2, 0, 1))
     return torch.stack(out, 0).contiguous()
+
+
+class _ControlNetCall(_Call):
+    """text-to-image under a ControlNet: the control image, the ControlNet's window, the branch's engine calls"""
+
+    def begin(self, pipe):
+        super().begin(pipe)
+        self.cond = prepare_control_image(self.image, self.height, self.width)
+
+    def schedule_kw(self, pipe, S):
+        if self.cond.shape[0] not in (1, S):
+            raise ValueError(f"{self.cond.shape[0]} control images for {S} samples: one image, or one per sample")
+        return dict(controlnet_guidance_start=float(self.controlnet_guidance_start), controlnet_guidance_end=float(self.controlnet_guidance_end))
+
+    def condition(self, pipe, eng):
+        eng.set_controlnet(pipe.controlnet)
+        super().condition(pipe, eng)
+        eng.set_control_image(self.cond, conditioning_scale=float(self.controlnet_conditioning_scale))
 
 
 class StableDiffusionXLControlNetCustomPipeline(StableDiffusionXLCustomPipeline):
@@ -443,31 +467,4 @@ class StableDiffusionXLControlNetCustomPipeline(StableDiffusionXLCustomPipeline)
             raise ValueError("the ControlNet pipeline needs `image`: the control image (PIL or a float tensor [n, 3, H, W] in [0, 1])")
         if not 0.0 <= float(controlnet_guidance_start) <= float(controlnet_guidance_end) <= 1.0:
             raise ValueError(f"controlnet guidance window [{controlnet_guidance_start}, {controlnet_guidance_end}] must satisfy 0 <= start <= end <= 1")
-        self._refuse(output_type, eta, kwargs)
-        seed_tab = self.step_seed_table(step_noise, generator, None)
-        height = height or self.default_sample_size * self.vae_scale_factor
-        width = width or self.default_sample_size * self.vae_scale_factor
-        cond = prepare_control_image(image, height, width)
-        if prompt_embeds is None:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, num_images_per_prompt, guidance_scale > 1.0, negative_prompt)
-        if pooled_prompt_embeds is None:
-            raise ValueError("pooled_prompt_embeds must be passed together with prompt_embeds")     # check_inputs
-        S = prompt_embeds.shape[0]
-        if cond.shape[0] not in (1, S):
-            raise ValueError(f"{cond.shape[0]} control images for {S} samples: one image, or one per sample")
-        eng = self.engine
-        eng.set_controlnet(self.controlnet)
-        eng.set_conditioning(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
-                             height, width, guidance_scale, guidance_rescale=guidance_rescale, original_size=original_size,
-                             crops_coords_top_left=crops_coords_top_left, target_size=target_size)
-        eng.set_control_image(cond, conditioning_scale=float(controlnet_conditioning_scale))
-        seed_tab = self.step_seed_table(step_noise, generator, S)
-        eng.set_schedule(self.scheduler, num_inference_steps, control_guidance_start, control_guidance_end,
-                         denoising_end=denoising_end, controlnet_guidance_start=float(controlnet_guidance_start),
-                         controlnet_guidance_end=float(controlnet_guidance_end), **({"seeded_noise": True} if seed_tab else {}))
-        if latents is None:
-            latents = randn_latents((S, 4, height // 8, width // 8), generator)
-        out = eng.denoise(latents, callback=callback, callback_steps=callback_steps, **self._noise_kw(eng, seed_tab, generator)).clone()
-        out = self._output(out, output_type)
-        return StableDiffusionXLPipelineOutput(images=out) if return_dict else (out,)
+        return self._run(_ControlNetCall(locals()))

@@ -22,6 +22,8 @@ from typing import Callable, List, Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from . import pipeline as _pipe
+
 
 def default_scorer(latents: torch.Tensor) -> torch.Tensor:
     """[S, 4, h, w] -> [S] deterministic score (higher is better): negative deviation of the per-channel
@@ -145,6 +147,42 @@ class ClipPreferenceJudge:
         return (emb * self.target.to(emb.device)).sum(-1)
 
 
+def _stage_fns(engine, scheduler, preview_steps, final_steps, step_noise, schedule_kw, strength=None, prepare=None, inpaint=False):
+    """(preview_fn, final_fn) of two_stage_fns and -- ``prepare`` given -- edit_two_stage_fns: per stage set_schedule, for an edit truncated
+    by ``strength`` and followed by ``prepare(seeds, t_start)``, then the denoise: of the noise handed in, or (an edit) of what prepare
+    left in the engine"""
+    from .schedulers import get_timesteps
+    if step_noise not in ("global", "seed"):
+        raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
+    seeded, edit = step_noise == "seed", prepare is not None
+
+    def run(steps, noise, seeds):
+        kw = {"seeded_noise": True} if seeded else {}    # (unseeded text-to-image: today's calls, keyword for keyword)
+        if edit:
+            if seeds is None:
+                raise ValueError("an edit candidate is defined by its seed: run_pns(..., pass_seeds=True)")
+            seeds, noise = [int(s) for s in seeds], None
+            scheduler.set_timesteps(steps)
+            _, t_start = get_timesteps(scheduler, steps, strength)
+            kw.update(t_start=t_start, inpaint=inpaint)
+        engine.set_schedule(scheduler, steps, **kw, **schedule_kw)
+        if edit:
+            prepare(seeds, t_start)
+        if seeded and engine.seeded:                     # (a deterministic sampler ignores the flag: it draws no noise)
+            if seeds is None:
+                raise ValueError('step_noise="seed" needs the candidates\' seeds: run_pns(..., pass_seeds=True)')
+            return engine.denoise(noise, step_seeds=list(seeds)).clone()
+        return engine.denoise(noise).clone()
+
+    def preview(noise=None, seeds=None):
+        return run(preview_steps, noise, seeds)
+
+    def final(noise=None, seeds=None):
+        return run(final_steps, noise, seeds)
+
+    return preview, final
+
+
 def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, step_noise="global", **schedule_kw):
     """The two-stage schedule of assets/1.png on a ``DenoiseEngine`` whose conditioning is set: every candidate seed
     gets a ``preview_steps`` denoise ("+10 steps"), the judged-best noise the full ``final_steps`` one ("+30 steps").
@@ -158,28 +196,7 @@ def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, step_nois
     final run read the same noise rows 0 .. preview_steps - 1 (at different sigmas).  The functions then take ``seeds=`` (the
     candidates' seeds in stacking order): use ``run_pns(..., pass_seeds=True)``.
     The deterministic samplers (DDIM, Euler, DPM++ 2M with or without Karras sigmas) draw no noise and are unaffected either way."""
-    if step_noise not in ("global", "seed"):
-        raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
-    seeded = step_noise == "seed"
-
-    def run(steps, noise, seeds):
-        if not seeded:                                   # today's calls, unchanged
-            engine.set_schedule(scheduler, steps, **schedule_kw)
-            return engine.denoise(noise).clone()
-        engine.set_schedule(scheduler, steps, seeded_noise=True, **schedule_kw)
-        if engine.seeded:                                # (a deterministic sampler ignores the flag: it draws no noise)
-            if seeds is None:
-                raise ValueError('step_noise="seed" needs the candidates\' seeds: run_pns(..., pass_seeds=True)')
-            return engine.denoise(noise, step_seeds=list(seeds)).clone()
-        return engine.denoise(noise).clone()
-
-    def preview(noise, seeds=None):
-        return run(preview_steps, noise, seeds)
-
-    def final(noise, seeds=None):
-        return run(final_steps, noise, seeds)
-
-    return preview, final
+    return _stage_fns(engine, scheduler, preview_steps, final_steps, step_noise, schedule_kw)
 
 
 def edit_draws(seeds, h, w, third=False):
@@ -187,10 +204,7 @@ def edit_draws(seeds, h, w, third=False):
     ``torch.Generator("cpu").manual_seed(seed)`` -- the posterior noise of the image, the add-noise noise and, ``third`` (9-channel
     inpainting UNet), the posterior noise of the masked image.  -> (n1, n2, n3 or None), each fp32 [len(seeds), 4, h, w] on the CPU: the
     tensors ``pipe(..., generator=[that generator])`` draws for a batch of one, stacked."""
-    gens = [torch.Generator("cpu").manual_seed(int(s)) for s in seeds]
-    draw = lambda: torch.cat([torch.randn((1, 4, int(h), int(w)), generator=g, dtype=torch.float32) for g in gens], 0)      # noqa: E731
-    n1, n2 = draw(), draw()
-    return n1, n2, (draw() if third else None)
+    return _pipe.edit_draws([torch.Generator("cpu").manual_seed(int(s)) for s in seeds], len(seeds), 1, int(h), int(w), Bm=1 if third else None)
 
 
 def edit_prepare_fn(engine, scheduler, scaling, moments, h, w, strength, mask=None, masked_moments=None, concat=False):
@@ -198,14 +212,9 @@ def edit_prepare_fn(engine, scheduler, scaling, moments, h, w, strength, mask=No
     latents -- and, inpainting, the blend / conv_in state -- into the engine under its current schedule.  moments: the image's encoder
     moments (one image, every candidate reads it; None where nothing reads them: a 9-channel UNet at strength 1.0); mask: the latent mask
     [1, 1, h, w] (inpainting, else None); concat: a 9-channel UNet, with masked_moments the masked image's encoder moments."""
-    strength_max = float(strength) == 1.0
-
     def prepare(seeds, t_start):
-        n1, n2, n3 = edit_draws(seeds, h, w, third=concat)
-        a, b = scheduler.add_noise_coefficients(t_start)
-        if mask is None:
-            return engine.prepare_img2img(moments, n1, n2, scaling, a, b)
-        return engine.prepare_inpaint(moments, n1, n2, scaling, a, b, mask, strength_max=strength_max, masked_moments=masked_moments, n3=n3)
+        return _pipe.edit_prepare(engine, scheduler, t_start, scaling, moments, edit_draws(seeds, h, w, third=concat), mask,
+                                  float(strength) == 1.0, masked_moments)
 
     return prepare
 
@@ -219,30 +228,7 @@ def edit_two_stage_fns(engine, scheduler, prepare, strength, preview_steps=10, f
     ``prepare(seeds, t_start)`` puts the stacked initial latents in place (edit_prepare_fn); engine.denoise(None, ...).
     step_noise as in two_stage_fns; with "seed" the step noise rows read are the schedule's rows t_start .. (the device step counter), as
     in the pipelines' ``step_noise="seeded"`` call with one generator per sample."""
-    from .schedulers import get_timesteps
-    if step_noise not in ("global", "seed"):
-        raise ValueError(f'step_noise must be "global" or "seed", not {step_noise!r}')
-    seeded = step_noise == "seed"
-
-    def run(steps, seeds):
-        if seeds is None:
-            raise ValueError("an edit candidate is defined by its seed: run_pns(..., pass_seeds=True)")
-        seeds = [int(s) for s in seeds]
-        scheduler.set_timesteps(steps)
-        _, t_start = get_timesteps(scheduler, steps, strength)
-        engine.set_schedule(scheduler, steps, t_start=t_start, inpaint=inpaint, **({"seeded_noise": True} if seeded else {}), **schedule_kw)
-        prepare(seeds, t_start)
-        if seeded and engine.seeded:                     # (a deterministic sampler ignores the flag: it draws no noise)
-            return engine.denoise(None, step_seeds=seeds).clone()
-        return engine.denoise(None).clone()
-
-    def preview(noise=None, seeds=None):
-        return run(preview_steps, seeds)
-
-    def final(noise=None, seeds=None):
-        return run(final_steps, seeds)
-
-    return preview, final
+    return _stage_fns(engine, scheduler, preview_steps, final_steps, step_noise, schedule_kw, strength, prepare, inpaint)
 
 
 def pair_groups():
