@@ -16,7 +16,8 @@ _CLIP_TEXT = ("CLIPTextEncoder", "CLIPTextEncoderConfig")
 
 # the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
 _PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline",
-              "StableDiffusionXLControlNetCustomPipeline")
+              "StableDiffusionXLControlNetCustomPipeline", "StableDiffusionXLControlNetImg2ImgCustomPipeline",
+              "StableDiffusionXLControlNetInpaintCustomPipeline")
 # the SDXL ControlNet (controlnet.py): the model whose residuals the UNet forward adds to its skips
 _CONTROLNET = ("ControlNetModel",)
 # the schedulers of the device-resident loop (schedulers.py): the two linear ones and the multistep / ancestral ones

@@ -10,7 +10,8 @@ state-dict names) plus
   * ``controlnet_down_blocks`` (nine 1 x 1 "zero convs", one per UNet skip) and ``controlnet_mid_block``: the residuals the UNet adds to
     its skips and to its mid-block output (``UNet2DConditionModel.emit_forward(control=...)``, imh_control_add).
 
-``emit_forward`` records the branch into the SAME plan as the UNet forward that consumes it.  Not built: ``guess_mode``,
+``emit_forward`` records the branch into the SAME plan as the UNet forward that consumes it -- a text-to-image step, an image-to-image
+one or either inpainting mode: the branch reads the 4-channel latents whatever the UNet's ``in_channels``.  Not built: ``guess_mode``,
 ``global_pool_conditions``, class embeddings, ``MultiControlNetModel`` (NotImplementedError).
 """
 import math

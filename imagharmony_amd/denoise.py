@@ -7,7 +7,8 @@ scale and the per-step IP-scale gate (control_guidance_start/end, custom_pipelin
 device tables indexed by a device-resident step counter.  Inpainting (diffusers StableDiffusionXLInpaintPipeline) keeps that shape: the
 masked blend upstream applies on the host after every scheduler.step is part of the recorded step (it rides in the CFG + scheduler
 launch and reads its add_noise pair from one more table), and a 9-channel UNet reads [mask | masked-image latents] from a
-step-invariant buffer inside conv_in.
+step-invariant buffer inside conv_in.  A ControlNet branch (set_controlnet) is recorded in front of the UNet in any of these modes: it reads the
+4-channel latents alone, and neither inpainting mode adds a launch to it.
 """
 import hashlib
 import os
@@ -155,7 +156,12 @@ class DenoiseEngine:
         self._cond_in = (ehs, text, ids)
         if self.cn is not None:
             self.cn["hint"] = self.cn["cond"] = None      # the ControlNet's caches belong to the previous conditioning (and size)
-            if self.controlnet is not None:
+            img = self.cn["image"]
+            if img.dim() == 4 and (tuple(img.shape[2:]) != (height, width) or img.shape[0] not in (1, S)):
+                # the previous call's control image does not fit this conditioning (an edit's size follows its image): it is dropped,
+                # not prepared at the wrong size; set_control_image sets this call's (set_schedule insists on one)
+                self.cn = None
+            elif self.controlnet is not None:
                 self._prepare_control()
         return st
 
@@ -323,12 +329,13 @@ class DenoiseEngine:
         if self.controlnet is not None:
             if split:
                 raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
-            if self.inpaint or self.unet.config.in_channels != 4:
-                raise NotImplementedError("the ControlNet branch runs text-to-image schedules (no inpainting mode)")
             if self.cn is None or self.cn.get("hint") is None or self.cn.get("cond") is None or self.cn_scale_tab is None:
                 raise L.ImhError("the ControlNet branch needs set_conditioning, set_control_image and then set_schedule")
             from .controlnet import control_state
-            cst = control_state(st, self.cn["cond"])       # the UNet's latents / counter / tables, the ControlNet's conditioning
+            # the UNet's latents / counter / tables, the ControlNet's conditioning.  Under an inpainting schedule too the branch reads the
+            # 4-channel latents alone: a 9-channel UNet's conv_in_extra is not part of its state (diffusers' ControlNet inpainting pipeline
+            # takes control_model_input before the concat), and the blend rides in the CFG + scheduler launch below as without a branch
+            cst = control_state(st, self.cn["cond"])
             self.controlnet.precompute_temb(self._temb_ctx, cst, st.t_table)
             self._cn_temb = cst.temb_table
         if not split and self.use_graph and len(self.xcd_candidates) > 1 and self.xcd_cells is None:

@@ -271,7 +271,7 @@ class IPAdapterXL(IPAdapter):
                      preview_steps=10, num_inference_steps=30, guidance_scale=5.0, scorer=None, batch=None,
                      clip_image_embeds=None, prompt_embeds=None, extra_prompt_embeds=None, height=None, width=None,
                      output_type="pil", step_noise="global", image=None, mask_image=None, strength=None, judge_preprocess="torch",
-                     **schedule_kw):
+                     control_image=None, controlnet_conditioning_scale=1.0, **schedule_kw):
         """Preference-guided noise selection (README.md:27, assets/1.png) around ``generate``: every candidate seed gets
         a ``preview_steps`` denoise, a judge scores the previews, the best NOISE gets the full ``num_inference_steps``
         denoise.  Candidates are sharded over the ranks of an initialised torch.distributed group (one process per
@@ -294,10 +294,16 @@ class IPAdapterXL(IPAdapter):
         bits of ``pipe(image=, [mask_image=,] strength=, num_inference_steps=num_inference_steps, generator=[that generator],
         output_type="latent")`` -- with ``step_noise="seed"`` under a stochastic scheduler, of that call with ``step_noise="seeded"``.
         height / width follow the image there.
+        On a pipe with a ControlNet (``pipe.controlnet``: the text-to-image, image-to-image and inpainting ControlNet pipelines)
+        ``control_image`` is required -- on the text-to-image one too, where ``image=`` stays refused -- and steers every candidate at
+        ``controlnet_conditioning_scale``: it is prepared at the call's height / width and set on the engine once per call, one image for
+        every stacked candidate; the ControlNet's window travels in ``controlnet_guidance_start / controlnet_guidance_end``.  A ControlNet
+        makes no draws, so the contract above holds with ``control_image=`` (and the scale and window) added to the pipe's call.  On a
+        pipe without a ControlNet ``control_image`` is refused (ValueError).
         Returns dict(images, best_seed, scores, latents)."""
         from . import pns
-        from .pipeline import (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline, decode_output,
-                               edit_moments)
+        from .pipeline import (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline, _ControlNetPipe,
+                               check_controlnet_args, decode_output, edit_moments, prepare_control_image)
         seeds = list(seeds)                       # consumed more than once below: a generator passed as `seeds` must survive that
         if judge_preprocess not in ("torch", "hip"):
             raise ValueError(f"judge_preprocess={judge_preprocess!r}: 'torch' or 'hip'")
@@ -305,6 +311,12 @@ class IPAdapterXL(IPAdapter):
             raise ValueError('judge_preprocess="hip" needs the HIP CLIP vision tower as the image encoder '
                              '(image_encoder_backend="hip" / image_encoder=CLIPVisionEncoder)')
         pipe = self.pipe
+        controlnet = pipe.controlnet if isinstance(pipe, _ControlNetPipe) else None          # (the three classes that carry .controlnet)
+        if controlnet is None and control_image is not None:
+            raise ValueError("control_image= belongs to a ControlNet pipeline: this pipe has no .controlnet")
+        if controlnet is not None:
+            check_controlnet_args(control_image, "control_image", controlnet_conditioning_scale, schedule_kw.pop("guess_mode", False),
+                                  schedule_kw.get("controlnet_guidance_start", 0.0), schedule_kw.get("controlnet_guidance_end", 1.0))
         inpaint = isinstance(pipe, StableDiffusionXLInpaintCustomPipeline)
         edit = inpaint or isinstance(pipe, StableDiffusionXLImg2ImgCustomPipeline)
         if edit:
@@ -318,9 +330,14 @@ class IPAdapterXL(IPAdapter):
             height = height or pipe.default_sample_size * pipe.vae_scale_factor
             width = width or pipe.default_sample_size * pipe.vae_scale_factor
         h, w = height // 8, width // 8
+        control = prepare_control_image(control_image, height, width) if controlnet is not None else None
+        if control is not None and control.shape[0] != 1:
+            raise ValueError(f"PNS runs its candidates under one control image, got a batch of {control.shape[0]}")
         fused, cond = self._pns_setup(scale, pil_image, clip_image_embeds, prompt, negative_prompt, extra_text, prompt_embeds, extra_prompt_embeds)
         S = max(1, int(_default_batch(len(seeds)) if batch is None else batch))
         eng = pipe.engine
+        if controlnet is not None:
+            eng.set_controlnet(controlnet)
         if edit:
             # everything a candidate shares is computed once, the moments at batch 1 as the pipelines encode a per-sample-generator call;
             # a candidate costs its draws, one fused initial-latents launch (stacked ``batch`` per call) and the truncated denoise
@@ -343,6 +360,10 @@ class IPAdapterXL(IPAdapter):
                 n = noise.shape[0]
                 if state["n"] != n:
                     eng.set_conditioning(*(t.repeat(*([n] + [1] * (t.ndim - 1))) for t in cond), height, width, guidance_scale=guidance_scale)
+                    if control is not None and state["n"] is None:
+                        # once per call, behind the first conditioning; later re-conditionings prepare the hint and the ControlNet's
+                        # caches again for their stack size themselves (DenoiseEngine.set_conditioning -> _prepare_control)
+                        eng.set_control_image(control, conditioning_scale=float(controlnet_conditioning_scale))
                     state["n"] = n
                 return stage(noise, **kw)
             return fn

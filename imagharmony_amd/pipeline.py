@@ -401,16 +401,19 @@ def prepare_control_image(image, height, width):
 
 
 class _ControlNetCall(_Call):
-    """text-to-image under a ControlNet: the control image, the ControlNet's window, the branch's engine calls"""
+    """text-to-image under a ControlNet: the control image (the call's ``image``), the ControlNet's window, the branch's engine calls.
+    Every hook goes through super(), so the class also stacks in front of _EditCall (_ControlNetEditCall)."""
+    control_arg = "image"
 
     def begin(self, pipe):
         super().begin(pipe)
-        self.cond = prepare_control_image(self.image, self.height, self.width)
+        self.cond = prepare_control_image(getattr(self, self.control_arg), self.height, self.width)
 
     def schedule_kw(self, pipe, S):
         if self.cond.shape[0] not in (1, S):
             raise ValueError(f"{self.cond.shape[0]} control images for {S} samples: one image, or one per sample")
-        return dict(controlnet_guidance_start=float(self.controlnet_guidance_start), controlnet_guidance_end=float(self.controlnet_guidance_end))
+        return dict(super().schedule_kw(pipe, S), controlnet_guidance_start=float(self.controlnet_guidance_start),
+                    controlnet_guidance_end=float(self.controlnet_guidance_end))
 
     def condition(self, pipe, eng):
         eng.set_controlnet(pipe.controlnet)
@@ -418,18 +421,28 @@ class _ControlNetCall(_Call):
         eng.set_control_image(self.cond, conditioning_scale=float(self.controlnet_conditioning_scale))
 
 
-class StableDiffusionXLControlNetCustomPipeline(StableDiffusionXLCustomPipeline):
-    """Text-to-image under a ControlNet, with diffusers' ``StableDiffusionXLControlNetPipeline`` call surface (0.30) for what this path
-    builds: one ``controlnet.ControlNetModel``, one control image (or one per sample), ``controlnet_conditioning_scale`` and a guidance
-    window.  The pipe exposes ``.controlnet``, so ``IPAdapterXL(pipe, ...)`` installs ``CNAttnProcessor2_0`` on it (ip_adapter/ip_adapter.py:
-    126-133) and ``IPAdapterXL.generate(..., image=, controlnet_conditioning_scale=)`` reaches ``__call__`` through its **kwargs.
+class _ControlNetEditCall(_ControlNetCall, _EditCall):
+    """an edit under a ControlNet: _EditCall's image / mask / strength and preparation, _ControlNetCall's branch.  The control image is
+    ``control_image``, at the edit's height and width; the window travels next to t_start, so it counts the steps that run.  A ControlNet
+    makes no draws: the generator order is the edit's own."""
+    control_arg = "control_image"
 
-    Naming: upstream's ControlNet pipelines call their window ``control_guidance_start / _end``; the reference's custom pipeline uses those
-    names for the IP-scale window (custom_pipelines.py:326-329) and they keep that meaning here.  The ControlNet's window is
-    ``controlnet_guidance_start / controlnet_guidance_end``.
 
-    Not built: ``guess_mode``, several ControlNets (``MultiControlNetModel`` / a list), ControlNet variants of the image-to-image and
-    inpainting pipelines (NotImplementedError)."""
+def check_controlnet_args(control, name, scale, guess_mode, start, end):
+    """what every ControlNet __call__ (and generate_pns) refuses before any GPU work"""
+    if guess_mode:
+        raise NotImplementedError("guess_mode is not supported on this path")
+    if isinstance(scale, (list, tuple)):
+        raise NotImplementedError("a list of conditioning scales belongs to MultiControlNetModel, which is not supported")
+    if control is None:
+        raise ValueError(f"the ControlNet pipeline needs `{name}`: the control image (PIL or a float tensor [n, 3, H, W] in [0, 1])")
+    if not 0.0 <= float(start) <= float(end) <= 1.0:
+        raise ValueError(f"controlnet guidance window [{start}, {end}] must satisfy 0 <= start <= end <= 1")
+
+
+class _ControlNetPipe:
+    """what the ControlNet pipeline classes share, in front of their base in the MRO: the ``.controlnet`` attribute (which IPAdapterXL
+    looks for), the constructor's refusal of several nets, to() and the engine's set_controlnet"""
 
     def __init__(self, unet, controlnet, scheduler=None, device="cuda:0", dtype=torch.bfloat16, **kw):
         if isinstance(controlnet, (list, tuple)) or hasattr(controlnet, "nets"):
@@ -443,6 +456,20 @@ class StableDiffusionXLControlNetCustomPipeline(StableDiffusionXLCustomPipeline)
         self.controlnet.to(self.device)
         self.engine.set_controlnet(self.controlnet)
         return self
+
+
+class StableDiffusionXLControlNetCustomPipeline(_ControlNetPipe, StableDiffusionXLCustomPipeline):
+    """Text-to-image under a ControlNet, with diffusers' ``StableDiffusionXLControlNetPipeline`` call surface (0.30) for what this path
+    builds: one ``controlnet.ControlNetModel``, one control image (or one per sample), ``controlnet_conditioning_scale`` and a guidance
+    window.  The pipe exposes ``.controlnet``, so ``IPAdapterXL(pipe, ...)`` installs ``CNAttnProcessor2_0`` on it (ip_adapter/ip_adapter.py:
+    126-133) and ``IPAdapterXL.generate(..., image=, controlnet_conditioning_scale=)`` reaches ``__call__`` through its **kwargs.
+
+    Naming: upstream's ControlNet pipelines call their window ``control_guidance_start / _end``; the reference's custom pipeline uses those
+    names for the IP-scale window (custom_pipelines.py:326-329) and they keep that meaning here.  The ControlNet's window is
+    ``controlnet_guidance_start / controlnet_guidance_end``.
+
+    The image-to-image and inpainting variants are StableDiffusionXLControlNetImg2ImgCustomPipeline / ...InpaintCustomPipeline below.
+    Not built: ``guess_mode``, several ControlNets (``MultiControlNetModel`` / a list) (NotImplementedError)."""
 
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, height=None, width=None, num_inference_steps: int = 50, guidance_scale: float = 5.0,
@@ -459,12 +486,77 @@ class StableDiffusionXLControlNetCustomPipeline(StableDiffusionXLCustomPipeline)
         not normalised; one image serves every sample.  Everything else as StableDiffusionXLCustomPipeline.__call__.
         Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no image, a window outside 0 <= start <= end <= 1
         (ValueError)."""
-        if guess_mode:
-            raise NotImplementedError("guess_mode is not supported on this path")
-        if isinstance(controlnet_conditioning_scale, (list, tuple)):
-            raise NotImplementedError("a list of conditioning scales belongs to MultiControlNetModel, which is not supported")
-        if image is None:
-            raise ValueError("the ControlNet pipeline needs `image`: the control image (PIL or a float tensor [n, 3, H, W] in [0, 1])")
-        if not 0.0 <= float(controlnet_guidance_start) <= float(controlnet_guidance_end) <= 1.0:
-            raise ValueError(f"controlnet guidance window [{controlnet_guidance_start}, {controlnet_guidance_end}] must satisfy 0 <= start <= end <= 1")
+        check_controlnet_args(image, "image", controlnet_conditioning_scale, guess_mode, controlnet_guidance_start, controlnet_guidance_end)
         return self._run(_ControlNetCall(locals()))
+
+
+class StableDiffusionXLControlNetImg2ImgCustomPipeline(_ControlNetPipe, StableDiffusionXLImg2ImgCustomPipeline):
+    """Image-to-image under a ControlNet, with diffusers' ``StableDiffusionXLControlNetImg2ImgPipeline`` call surface (0.30) for what this
+    path builds: ``image`` is the init image, encoded and noised to step t_start as in StableDiffusionXLImg2ImgCustomPipeline;
+    ``control_image`` steers the steps that run through one ``controlnet.ControlNetModel``.  The recorded step is the text-to-image
+    ControlNet step -- the branch over the 4-channel latents, then the UNet with the gated injections -- started at row t_start.
+
+    The ControlNet's window is ``controlnet_guidance_start / controlnet_guidance_end`` (``control_guidance_*`` stays the IP-scale
+    window) and counts the m = steps - t_start steps that run: diffusers' ``controlnet_keep`` over ``len(timesteps)``.
+    Not built: ``guess_mode``, several ControlNets, a list of scales (NotImplementedError)."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, control_image=None, strength: float = 0.3, num_inference_steps: int = 50,
+                 denoising_start=None, denoising_end: Optional[float] = None, guidance_scale: float = 5.0, negative_prompt=None,
+                 num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents=None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
+                 controlnet_guidance_start: float = 0.0, controlnet_guidance_end: float = 1.0,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+                 callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
+        """control_image: PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1], brought to the init image's height and
+        width, not normalised; one image serves every sample.  Everything else as StableDiffusionXLImg2ImgCustomPipeline.__call__.
+        Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no control_image, a window outside
+        0 <= start <= end <= 1 (ValueError); and what the image-to-image call refuses."""
+        check_controlnet_args(control_image, "control_image", controlnet_conditioning_scale, guess_mode, controlnet_guidance_start,
+                              controlnet_guidance_end)
+        if denoising_start is not None:
+            raise NotImplementedError("denoising_start (the refiner hand-off) is not supported on this path")
+        return self._run(_ControlNetEditCall(locals()))
+
+
+class StableDiffusionXLControlNetInpaintCustomPipeline(_ControlNetPipe, StableDiffusionXLInpaintCustomPipeline):
+    """Inpainting under a ControlNet, with diffusers' ``StableDiffusionXLControlNetInpaintPipeline`` call surface (0.30) for what this
+    path builds.  Both modes of StableDiffusionXLInpaintCustomPipeline run next to the branch, in one recorded step and with no launch
+    more than the text-to-image ControlNet step: with a 4-channel UNet the masked blend rides in the CFG + scheduler launch; with a
+    9-channel UNet only the UNet's conv_in reads [mask | masked-image latents] -- the ControlNet is a 4-channel model and reads the
+    scaled latents alone (upstream: ``control_model_input = latent_model_input``, taken before the concat).  ``ControlNetModel.from_unet``
+    on a 9-channel UNet stays refused: build the ControlNet from a 4-channel config of the same widths.
+
+    Window naming and counting as in StableDiffusionXLControlNetImg2ImgCustomPipeline.
+    Not built: ``guess_mode``, several ControlNets, a list of scales (NotImplementedError)."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, mask_image=None, control_image=None, masked_image_latents=None, height=None, width=None,
+                 padding_mask_crop=None, strength: float = 0.9999, num_inference_steps: int = 50, denoising_start=None,
+                 denoising_end: Optional[float] = None, guidance_scale: float = 7.5, negative_prompt=None,
+                 num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents=None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
+                 controlnet_guidance_start: float = 0.0, controlnet_guidance_end: float = 1.0,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+                 callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
+        """control_image: as for StableDiffusionXLControlNetImg2ImgCustomPipeline, at the init image's height and width.  Everything else
+        as StableDiffusionXLInpaintCustomPipeline.__call__, defaults included.
+        Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no control_image, a window outside
+        0 <= start <= end <= 1 (ValueError); and what the inpainting call refuses."""
+        check_controlnet_args(control_image, "control_image", controlnet_conditioning_scale, guess_mode, controlnet_guidance_start,
+                              controlnet_guidance_end)
+        if denoising_start is not None:
+            raise NotImplementedError("denoising_start (the refiner hand-off) is not supported on this path")
+        if padding_mask_crop is not None:
+            raise NotImplementedError("padding_mask_crop (crop, inpaint, overlay) is not supported on this path")
+        if masked_image_latents is not None:
+            raise NotImplementedError("masked_image_latents= is not supported: the masked image is encoded from `image` and `mask_image`")
+        return self._run(_ControlNetEditCall(locals(), "inpainting"))

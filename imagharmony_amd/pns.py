@@ -195,7 +195,9 @@ def two_stage_fns(engine, scheduler, preview_steps=10, final_steps=30, step_nois
     the device from its own seed with lane 0 -- a seed then reproduces its latent alone or stacked, on any rank, and its preview and
     final run read the same noise rows 0 .. preview_steps - 1 (at different sigmas).  The functions then take ``seeds=`` (the
     candidates' seeds in stacking order): use ``run_pns(..., pass_seeds=True)``.
-    The deterministic samplers (DDIM, Euler, DPM++ 2M with or without Karras sigmas) draw no noise and are unaffected either way."""
+    The deterministic samplers (DDIM, Euler, DPM++ 2M with or without Karras sigmas) draw no noise and are unaffected either way.
+    ``schedule_kw`` goes to set_schedule at both stages: the IP-scale window and, on an engine with a ControlNet and its control image
+    set, ``controlnet_guidance_start / controlnet_guidance_end`` (counted per stage over the steps that run)."""
     return _stage_fns(engine, scheduler, preview_steps, final_steps, step_noise, schedule_kw)
 
 
