@@ -17,9 +17,11 @@ _CLIP_TEXT = ("CLIPTextEncoder", "CLIPTextEncoderConfig")
 # the pipelines, lazily too: text-to-image (custom_pipelines.py), image-to-image and inpainting (diffusers' SDXL img2img / inpaint call surfaces)
 _PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustomPipeline", "StableDiffusionXLInpaintCustomPipeline",
               "StableDiffusionXLControlNetCustomPipeline", "StableDiffusionXLControlNetImg2ImgCustomPipeline",
-              "StableDiffusionXLControlNetInpaintCustomPipeline")
+              "StableDiffusionXLControlNetInpaintCustomPipeline", "StableDiffusionXLAdapterCustomPipeline")
 # the SDXL ControlNet (controlnet.py): the model whose residuals the UNet forward adds to its skips
 _CONTROLNET = ("ControlNetModel",)
+# the SDXL T2I-Adapter (t2i_adapter.py): the once-per-image net whose four features the UNet's down path adds
+_T2I_ADAPTER = ("T2IAdapter",)
 # the schedulers of the device-resident loop (schedulers.py): the two linear ones and the multistep / ancestral ones
 _SCHEDULERS = ("DDIMScheduler", "EulerDiscreteScheduler", "DPMSolverMultistepScheduler", "EulerAncestralDiscreteScheduler")
 # the seeded step noise restated in numpy (noise.py): seeded_randn / seed_rows, the yardstick of the device generator
@@ -44,6 +46,9 @@ def __getattr__(name):
     if name in _CONTROLNET:
         from . import controlnet
         return getattr(controlnet, name)
+    if name in _T2I_ADAPTER:
+        from . import t2i_adapter
+        return getattr(t2i_adapter, name)
     if name in _SCHEDULERS:
         from . import schedulers
         return getattr(schedulers, name)

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/imh.h"
+#include "../../include/imh_adapter.h"
 #include "imh_common.h"
 #include "imh_kernels.h"
 
@@ -295,6 +296,46 @@ static int do_control_add(const imh_control_add_args* a, hipStream_t s) {
     return control_add_launch(p, a->dtype, s);
 }
 
+static int do_adapter_op(const imh_adapter_args* a, hipStream_t s) {
+    const char* who = "imh_adapter_op";
+    if (!a || !a->x || !a->y) { set_error("%s: null pointer argument", who); return IMH_ERR_ARG; }
+    if (a->mode != IMH_ADAPTER_UNSHUFFLE && a->mode != IMH_ADAPTER_RELU && a->mode != IMH_ADAPTER_AVGPOOL2) {
+        set_error("%s: unknown mode %d", who, a->mode); return IMH_ERR_ARG;
+    }
+    if (((uintptr_t)a->y & 15) || ((uintptr_t)a->x & (a->mode == IMH_ADAPTER_UNSHUFFLE ? 3 : 15))) {
+        set_error("%s: y (and x, unshuffle: to 4 bytes) must be 16-byte aligned", who); return IMH_ERR_ARG;
+    }
+    if (a->dtype != IMH_DT_BF16 && a->dtype != IMH_DT_F16) { set_error("%s: unknown dtype %d", who, a->dtype); return IMH_ERR_DTYPE; }
+    const long long lim = 0x7fffffffLL;
+    long long xe, ye;                        // elements of x and of y
+    if (a->mode == IMH_ADAPTER_RELU) {
+        if (a->n <= 0 || a->n > lim) { set_error("%s: relu over n=%lld elements (0 < n < 2^31)", who, (long long)a->n); return IMH_ERR_SHAPE; }
+        xe = ye = a->n;
+    } else {
+        if (a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) { set_error("%s: N=%d C=%d H=%d W=%d must be positive", who, a->N, a->C, a->H, a->W); return IMH_ERR_SHAPE; }
+        xe = (long long)a->N * a->C;
+        if (xe > lim || (xe *= a->H) > lim || (xe *= a->W) > lim) { set_error("%s: N=%d C=%d H=%d W=%d: an operand of 2^31 elements or more", who, a->N, a->C, a->H, a->W); return IMH_ERR_SHAPE; }
+        if (a->mode == IMH_ADAPTER_UNSHUFFLE) {
+            if (a->f < 1 || a->H % a->f || a->W % a->f) { set_error("%s: unshuffle of %d x %d by f=%d (f >= 1 divides both sides)", who, a->H, a->W, a->f); return IMH_ERR_SHAPE; }
+            const long long K = (long long)a->C * a->f * a->f;
+            if (a->Cp <= 0 || a->Cp % 8 || a->Cp < K) { set_error("%s: Cp=%d must be a multiple of 8 and at least C f^2 = %lld", who, a->Cp, K); return IMH_ERR_SHAPE; }
+            ye = (long long)a->N * (a->H / a->f) * (a->W / a->f);
+            if (ye > lim || (ye *= a->Cp) > lim) { set_error("%s: Cp=%d: an operand of 2^31 elements or more", who, a->Cp); return IMH_ERR_SHAPE; }
+        } else {
+            if (a->C % 8) { set_error("%s: avgpool2 over C=%d channels (a multiple of 8)", who, a->C); return IMH_ERR_SHAPE; }
+            ye = (long long)a->N * ((a->H + 1) / 2) * ((a->W + 1) / 2) * a->C;
+        }
+    }
+    const uintptr_t x0 = (uintptr_t)a->x, y0 = (uintptr_t)a->y;
+    const size_t xb = (size_t)xe * (a->mode == IMH_ADAPTER_UNSHUFFLE ? 4 : 2), yb = (size_t)ye * 2;
+    if (y0 < x0 + xb && x0 < y0 + yb && !(a->mode == IMH_ADAPTER_RELU && x0 == y0)) {
+        set_error("%s: y must not overlap x (relu: except y == x)", who); return IMH_ERR_ARG;
+    }
+    AdapterParams p;
+    p.x = a->x; p.y = a->y; p.n = a->n; p.mode = a->mode; p.N = a->N; p.C = a->C; p.H = a->H; p.W = a->W; p.f = a->f; p.Cp = a->Cp;
+    return adapter_launch(p, a->dtype, s);
+}
+
 }  // namespace imh
 
 using namespace imh;
@@ -464,6 +505,7 @@ int imh_step_seeded(const imh_seeded_args* a, void* stream) { return do_step_see
 int imh_randn_seeded(const imh_randn_args* a, void* stream) { return do_randn_seeded(a, (hipStream_t)stream); }
 int imh_clip_preprocess(const imh_clip_preprocess_args* a, void* stream) { return do_clip_preprocess(a, (hipStream_t)stream); }
 int imh_control_add(const imh_control_add_args* a, void* stream) { return do_control_add(a, (hipStream_t)stream); }
+int imh_adapter_op(const imh_adapter_args* a, void* stream) { return do_adapter_op(a, (hipStream_t)stream); }
 int imh_randn_seeded_host(const imh_randn_args* a) {
     RandnParams p;
     const int rc = to_randn(a, "imh_randn_seeded_host", &p);

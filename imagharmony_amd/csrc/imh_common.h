@@ -248,6 +248,9 @@ __device__ __forceinline__ float wave_max(float v) {
 #define IMH_DT_BF16 0
 #define IMH_DT_F16 1
 #define IMH_CLIP_DT_F32 2      // imh_clip_preprocess's fp32 rows only (include/imh.h)
+#define IMH_ADAPTER_UNSHUFFLE 0    // imh_adapter_op's modes (include/imh_adapter.h)
+#define IMH_ADAPTER_RELU 1
+#define IMH_ADAPTER_AVGPOOL2 2
 
 namespace imh {
 // Dynamic-LDS opt-in (> 64 KB) is a per-DEVICE function attribute: remember it per device ordinal, so a process that drives a

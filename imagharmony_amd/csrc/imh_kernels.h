@@ -175,6 +175,15 @@ struct ControlAddParams {
 };
 int control_add_launch(const ControlAddParams& p, int dtype, hipStream_t stream);
 
+// imh_adapter_op (adapter.hip): the T2I-Adapter's pixel-unshuffle (fp32 NCHW [N, C, H, W] -> T NHWC [N, H / f, W / f, Cp]), ReLU (n elements)
+// and AvgPool2d(2, 2, ceil_mode=True) (NHWC [N, H, W, C] -> [N, ceil(H / 2), ceil(W / 2), C]); api.hip validates, the launcher launches
+struct AdapterParams {
+    const void* x; void* y;
+    long long n;
+    int mode, N, C, H, W, f, Cp;
+};
+int adapter_launch(const AdapterParams& p, int dtype, hipStream_t stream);
+
 // fp32 (reference-precision) kernels of the VAE decode tail (f32.hip).  op 0: GEMM / conv3x3 (X, W, Y, bias, residual; conv fields);
 // 1: GroupNorm statistics (X [B, HW, C] -> ws [B, nblk, groups, 2]); 2: table (ws, gamma, beta -> Y [B, C, 2]); 3: apply (X, ws = table -> Y);
 // 4: row softmax (X [M, ldx] -> Y [M, ldy], N columns, scale); 5: img2img initial latents (imh.h IMH_F32_IMG2IMG_INIT)

@@ -1083,6 +1083,57 @@ class Ctx:
                    keep=(x, r, y, tab, step) + ((gs.t,) if gs else ()), shape=(B, HW, Cc, Br), epi=dict(tab=tab is not None, gn_sub=gn_sub))
         return (y, gs) if gn_sub is not None else y
 
+    # ------------------------------------------------------------------ T2I-Adapter passes (imh_adapter_op: eager, once per control image)
+    def _adapter_op(self, a, descr):
+        if self.record:
+            raise L.ImhError(f"{descr}: imh_adapter_op is no plan kind: the adapter's features are step-invariant and computed eagerly")
+        a.dtype = self.dt
+        L.check(self.lib.imh_adapter_op(C.byref(a), self.stream()), descr)
+
+    def pixel_unshuffle(self, image, f, Cp=None, descr="pixel_unshuffle"):
+        """image fp32 [N, Cin, H, W] (dense) -> NHWC [N, H / f, W / f, Cp] in the compute dtype: channel c f^2 + dy f + dx of pixel (y, x) is
+        image[n, c, y f + dy, x f + dx] (torch's F.pixel_unshuffle, channels last); Cp (default: Cin f^2 rounded up to 8) pads with zeros."""
+        self._chk(image, descr + ".image", torch.float32)
+        if image.dim() != 4 or not image.is_contiguous():
+            raise L.ImhError(f"{descr}: image {tuple(image.shape)} must be dense [N, Cin, H, W]")
+        N, Cin, H, W = (int(v) for v in image.shape)
+        f = int(f)
+        if f < 1 or H % f or W % f:
+            raise L.ImhError(f"{descr}: f={f} must divide both sides of {H} x {W}")
+        Cp = (Cin * f * f + 7) // 8 * 8 if Cp is None else int(Cp)
+        if Cp % 8 or Cp < Cin * f * f:
+            raise L.ImhError(f"{descr}: Cp={Cp} must be a multiple of 8 and at least Cin f^2 = {Cin * f * f}")
+        out = self.new(N, H // f, W // f, Cp)
+        a = L.AdapterArgs()
+        a.x, a.y, a.mode, a.N, a.C, a.H, a.W, a.f, a.Cp = image.data_ptr(), out.data_ptr(), L.ADAPTER_UNSHUFFLE, N, Cin, H, W, f, Cp
+        self._adapter_op(a, descr)
+        return out
+
+    def relu(self, x, out=None, descr="relu"):
+        """max(x, 0) over a dense tensor of the compute dtype; out=x runs in place"""
+        self._chk(x, descr + ".x"); self._chk(out, descr + ".out")
+        if not x.is_contiguous() or x.numel() == 0 or (out is not None and (not out.is_contiguous() or out.shape != x.shape)):
+            raise L.ImhError(f"{descr}: x {tuple(x.shape)} (and out) must be dense and of one shape")
+        if out is None:
+            out = self.new(*x.shape)
+        a = L.AdapterArgs()
+        a.x, a.y, a.n, a.mode = x.data_ptr(), out.data_ptr(), x.numel(), L.ADAPTER_RELU
+        self._adapter_op(a, descr)
+        return out
+
+    def avgpool2(self, x, descr="avgpool2"):
+        """AvgPool2d(2, 2, ceil_mode=True) over NHWC [N, H, W, C] (dense, C % 8 == 0) -> [N, ceil(H / 2), ceil(W / 2), C]: an edge window
+        averages its in-bounds pixels only"""
+        self._chk(x, descr + ".x")
+        if x.dim() != 4 or not x.is_contiguous() or x.shape[-1] % 8 or x.numel() == 0:
+            raise L.ImhError(f"{descr}: x {tuple(x.shape)} must be dense NHWC with C a multiple of 8")
+        N, H, W, Cc = (int(v) for v in x.shape)
+        out = self.new(N, (H + 1) // 2, (W + 1) // 2, Cc)
+        a = L.AdapterArgs()
+        a.x, a.y, a.mode, a.N, a.C, a.H, a.W = x.data_ptr(), out.data_ptr(), L.ADAPTER_AVGPOOL2, N, Cc, H, W
+        self._adapter_op(a, descr)
+        return out
+
     def gather_rows(self, table, idx, add=None, out=None, descr="gather_rows"):
         """out[r] = table[idx[r]] (+ add[r % P]) (IMH_EW_GATHER_ROWS): table [rows, C] and add [P, C] row-major in the compute dtype, idx
         int32 [n] on the device.  The caller has validated the indices on the host (the CLIP text towers' ids and EOS rows are host-known)."""

@@ -54,6 +54,59 @@ class DenoiseEngine:
     cn = None                # its state: dict(image, scale, hint, cond = StepState with its aug_emb / K,V caches) (set_control_image)
     cn_scale_tab = None      # fp32 [steps] conditioning_scale * keep(i) of the current schedule (set_schedule)
 
+    # the T2I-Adapter state, likewise
+    adapter = None           # a t2i_adapter.T2IAdapter whose four features are added inside the UNet's down path (set_adapter)
+    ad = None                # its state: dict(image, scale, feats = four NHWC tensors, ctx) (set_adapter_image)
+    ad_gate_tab = None       # fp32 [steps] 1 / 0 per step of the current schedule (set_schedule(adapter_conditioning_factor=))
+
+    # -- T2I-Adapter (opt-in, like the ControlNet; the two exclude each other) --
+    def set_adapter(self, adapter):
+        """adapter: an imagharmony_amd.t2i_adapter.T2IAdapter on the engine's device, or None to switch the injections off.  The next
+        set_schedule picks (or records) the plan of that mode: the plans with and without the adapter of one schedule coexist."""
+        if adapter is not None:
+            if isinstance(adapter, (list, tuple)) or hasattr(adapter, "adapters"):
+                raise NotImplementedError("several adapters (MultiAdapter / a list of adapters) are not supported: one T2IAdapter")
+            if not hasattr(adapter, "prepare_features"):
+                raise TypeError(f"set_adapter takes an imagharmony_amd.t2i_adapter.T2IAdapter, not {type(adapter).__name__}")
+            if self.controlnet is not None:
+                raise NotImplementedError("a T2I-Adapter together with a ControlNet is not built")
+            if getattr(self, "cfg_role", None) is not None:
+                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a T2I-Adapter")
+        if adapter is not self.adapter:
+            if self.adapter is not None and adapter is not None:
+                self.ad = None                           # another model: its features go, and every plan recorded with them
+                self._plans = {k: v for k, v in self._plans.items() if k[11] is None}
+            self.plan, self._sched_key = None, None
+        self.adapter = adapter
+
+    @torch.no_grad()
+    def set_adapter_image(self, image, conditioning_scale=1.0):
+        """The per-image state of the adapter: its four features, computed here, once, outside the step, and kept until the image
+        changes (a call with the same image and another scale computes nothing).  image: float [1 | S, 3, height, width] in [0, 1]: one
+        control image may serve every stacked sample.  conditioning_scale is part of the plan key, so set_schedule follows this call."""
+        if self.adapter is None:
+            raise L.ImhError("set_adapter_image needs an adapter: set_adapter first")
+        self.adapter.check_image(image)
+        old = self.ad
+        if old is not None and old["image"].shape == image.shape and torch.equal(old["image"], image.detach().to("cpu", torch.float32)):
+            old["scale"] = float(conditioning_scale)     # the same image: the features (and the plans that point at them) stay
+        else:
+            img = image.detach().to("cpu", torch.float32).clone()
+            ctx = Ctx(self.device, self.dtype)           # fresh context: the features must outlive pooled buffers
+            feats = self.adapter.prepare_features(ctx, img, img.shape[2] // 8, img.shape[3] // 8)
+            self.ad = dict(image=img, scale=float(conditioning_scale), feats=feats, ctx=ctx)
+            self._plans = {k: v for k, v in self._plans.items() if k[11] is None}      # a plan recorded with the adapter points at the previous features
+        self.plan, self._sched_key = None, None
+
+    @staticmethod
+    def adapter_gate_table(n, t_start, factor):
+        """[n] floats: 1 where loop index i of the m = n - t_start steps that run satisfies i < int(m * factor) (diffusers
+        StableDiffusionXLAdapterPipeline: ``if i < int(num_inference_steps * adapter_conditioning_factor)``), else 0, at rows t_start + i;
+        rows before t_start (never read) hold 1, as in gate_table"""
+        m = n - t_start
+        k = int(m * float(factor))
+        return [1.0] * t_start + [1.0 if i < k else 0.0 for i in range(m)]
+
     # -- ControlNet (opt-in; an engine without one records, launches and returns what it always did) --
     def set_controlnet(self, controlnet):
         """controlnet: an imagharmony_amd.controlnet.ControlNetModel on the engine's device, or None to switch the branch off.  The next
@@ -65,6 +118,8 @@ class DenoiseEngine:
                 raise TypeError(f"set_controlnet takes an imagharmony_amd.controlnet.ControlNetModel, not {type(controlnet).__name__}")
             if getattr(self, "cfg_role", None) is not None:
                 raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+            if self.adapter is not None:
+                raise NotImplementedError("a ControlNet together with a T2I-Adapter is not built")
         if controlnet is not self.controlnet:
             if self.controlnet is not None and controlnet is not None:
                 self.cn, self._plans = None, {}          # another model: its caches and every plan recorded with the old one go
@@ -122,6 +177,8 @@ class DenoiseEngine:
             raise ValueError("cfg_role must be None, 0 (unconditional half) or 1 (conditional half)")
         if cfg_role is not None and self.controlnet is not None:
             raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+        if cfg_role is not None and self.adapter is not None:
+            raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a T2I-Adapter")
         if cfg_role != getattr(self, "cfg_role", None):
             self.plan = None
         self._plans = {}                          # every recorded plan points into the previous conditioning's caches
@@ -163,6 +220,8 @@ class DenoiseEngine:
                 self.cn = None
             elif self.controlnet is not None:
                 self._prepare_control()
+        if self.ad is not None and (tuple(self.ad["image"].shape[2:]) != (height, width) or self.ad["image"].shape[0] not in (1, S)):
+            self.ad = None                        # the previous call's control image does not fit this size or batch: set_adapter_image sets this call's
         return st
 
     # inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
@@ -174,7 +233,7 @@ class DenoiseEngine:
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
                      denoising_end=None, t_start=0, inpaint=False, seeded_noise=False, controlnet_guidance_start=0.0,
-                     controlnet_guidance_end=1.0):
+                     controlnet_guidance_end=1.0, adapter_conditioning_factor=1.0):
         """inpaint: the schedule of an inpainting call (prepare_inpaint).  On a 4-channel UNet every step then ends with upstream's masked
         blend, latents = (1 - m) * add_noise(z, n, timesteps[i + 1]) + m * latents, whose add_noise pair comes from blend_tab: row r holds
         scheduler.add_noise_coefficients(r + 1), the last row that runs (1, 0) -- the image latents themselves.  On a 9-channel UNet there is
@@ -192,6 +251,8 @@ class DenoiseEngine:
         about 8 MB per sample for 30 steps.
         seeded_noise=True (a stochastic scheduler; ignored by a deterministic one, whose plan is what it was): no bank.  The plan ends
         with the seeded step (imh.h imh_step_seeded, same launch count), which generates row *step's noise from st.seed_rows, int32 bits of
+        adapter_conditioning_factor (an engine with a T2I-Adapter and its image set): the adapter's features are added in the first
+        int(steps that run * factor) steps (adapter_gate_table); the table and the conditioning scale are part of the plan key.
         uint32 [S, 4] = (seed low, seed high, lane, 0) per sample (noise.seed_rows) -- 16 bytes per sample that denoise(step_seeds=...)
         fills before the loop.  The noise is then a pure function of (seed, lane, table row, element): the same on any rank, alone or
         stacked, eager or graph.  The flag is part of the plan key; the bank plan and the seeded plan of one schedule coexist."""
@@ -234,7 +295,15 @@ class DenoiseEngine:
                 raise L.ImhError("a ControlNet is set but no control image: set_control_image before set_schedule")
             cn_gate = self.gate_table(n, t_start, controlnet_guidance_start, controlnet_guidance_end, self.cn["scale"])
             cn_key = hashlib.sha1(torch.tensor(cn_gate, dtype=torch.float32).numpy().tobytes()).hexdigest()
-        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), cn_key, mode, seeded)
+        ad_gate = ad_key = None
+        if self.adapter is not None:
+            if self.ad is None:
+                raise L.ImhError("a T2I-Adapter is set but no control image: set_adapter_image before set_schedule")
+            if inpaint or t_start:
+                raise NotImplementedError("the T2I-Adapter runs text-to-image schedules (image-to-image / inpainting with an adapter are not built)")
+            ad_gate = self.adapter_gate_table(n, t_start, adapter_conditioning_factor)
+            ad_key = (hashlib.sha1(torch.tensor(ad_gate, dtype=torch.float32).numpy().tobytes()).hexdigest(), self.ad["scale"])
+        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), cn_key, mode, ad_key, seeded)
         self.t_start = t_start
         self.inpaint = mode
         self.general = general
@@ -250,6 +319,7 @@ class DenoiseEngine:
             self.plan, self.noise_pred, self._temb_ctx = hit["plan"], hit["noise_pred"], hit["temb_ctx"]
             self.plan_tail, self.np_full = hit.get("plan_tail"), hit.get("np_full")
             self.cn_scale_tab, self._cn_temb = hit.get("cn_scale_tab"), hit.get("cn_temb")
+            self.ad_gate_tab = hit.get("ad_gate_tab")
             self._sched_key = key
             return
         st.t_table = tab["timesteps"].to(dev)
@@ -269,6 +339,7 @@ class DenoiseEngine:
         st.ip_scale_tab = torch.tensor(gate, dtype=torch.float32, device=dev)
         st.blend_tab = self.blend_table(scheduler, num_inference_steps, n).to(dev) if mode == "blend" else None
         self.cn_scale_tab = torch.tensor(cn_gate, dtype=torch.float32, device=dev) if cn_gate is not None else None
+        self.ad_gate_tab = torch.tensor(ad_gate, dtype=torch.float32, device=dev) if ad_gate is not None else None
         if st.step is None:
             st.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.steps = n
@@ -296,6 +367,7 @@ class DenoiseEngine:
             setattr(e, k, getattr(self, k))
         e.general, e.stochastic, e.seeded = self.general, self.stochastic, self.seeded
         e.controlnet, e.cn, e.cn_scale_tab = self.controlnet, self.cn, self.cn_scale_tab      # shared, read-only during denoising: hint, caches, table
+        e.adapter, e.ad, e.ad_gate_tab = self.adapter, self.ad, self.ad_gate_tab              # likewise: the adapter's features and its gate table
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
@@ -352,7 +424,18 @@ class DenoiseEngine:
             # the ControlNet branch, then the UNet that consumes its residuals, in ONE plan on one stream: a linear capture
             control = self.controlnet.emit_forward(rec, cst, self.S, self.H, self.W, cfg_dup=self.do_cfg, hint=self.cn["hint"],
                                                    tab=self.cn_scale_tab)
-        out = self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg and not split, **({"control": control} if control is not None else {}))
+        extra = {"control": control} if control is not None else {}
+        if self.adapter is not None:
+            if split:
+                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a T2I-Adapter")
+            if self.ad is None or self.ad_gate_tab is None:
+                raise L.ImhError("the T2I-Adapter needs set_adapter_image and then set_schedule")
+            img = self.ad["image"]
+            if tuple(img.shape[2:]) != (8 * self.H, 8 * self.W) or img.shape[0] not in (1, self.S):
+                raise L.ImhError(f"adapter image {tuple(img.shape)}: one image or one per sample ({self.S}) at {8 * self.H} x {8 * self.W}")
+            from .t2i_adapter import AdapterResiduals
+            extra["adapter"] = AdapterResiduals(self.ad["feats"], scale=self.ad["scale"], tab=self.ad_gate_tab, step=st.step)
+        out = self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg and not split, **extra)
         if split:
             # this rank's half of the noise prediction ends the forward plan; the CFG combine + scheduler step + step counter are a
             # second tiny plan over BOTH halves ([uncond | cond] = the layout the fused step reads), run after the per-step exchange
@@ -417,7 +500,7 @@ class DenoiseEngine:
             st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + self._GENERAL_STEP},
             steps=self.steps, init_noise_sigma=self.init_noise_sigma, plan=self.plan, noise_pred=self.noise_pred,
             temb_ctx=self._temb_ctx, plan_tail=getattr(self, "plan_tail", None), np_full=getattr(self, "np_full", None),
-            cn_scale_tab=self.cn_scale_tab, cn_temb=getattr(self, "_cn_temb", None))
+            cn_scale_tab=self.cn_scale_tab, cn_temb=getattr(self, "_cn_temb", None), ad_gate_tab=self.ad_gate_tab)
         while len(self._plans) > self.max_cached_plans:              # (each plan keeps ~2 GB of activation buffers alive at 1024^2)
             self._plans.pop(next(iter(self._plans)))
 

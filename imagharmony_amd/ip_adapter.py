@@ -271,7 +271,8 @@ class IPAdapterXL(IPAdapter):
                      preview_steps=10, num_inference_steps=30, guidance_scale=5.0, scorer=None, batch=None,
                      clip_image_embeds=None, prompt_embeds=None, extra_prompt_embeds=None, height=None, width=None,
                      output_type="pil", step_noise="global", image=None, mask_image=None, strength=None, judge_preprocess="torch",
-                     control_image=None, controlnet_conditioning_scale=1.0, **schedule_kw):
+                     control_image=None, controlnet_conditioning_scale=1.0, adapter_image=None, adapter_conditioning_scale=1.0,
+                     adapter_conditioning_factor=1.0, **schedule_kw):
         """Preference-guided noise selection (README.md:27, assets/1.png) around ``generate``: every candidate seed gets
         a ``preview_steps`` denoise, a judge scores the previews, the best NOISE gets the full ``num_inference_steps``
         denoise.  Candidates are sharded over the ranks of an initialised torch.distributed group (one process per
@@ -300,6 +301,11 @@ class IPAdapterXL(IPAdapter):
         every stacked candidate; the ControlNet's window travels in ``controlnet_guidance_start / controlnet_guidance_end``.  A ControlNet
         makes no draws, so the contract above holds with ``control_image=`` (and the scale and window) added to the pipe's call.  On a
         pipe without a ControlNet ``control_image`` is refused (ValueError).
+        On a pipe with a T2I-Adapter (``pipe.adapter``: StableDiffusionXLAdapterCustomPipeline) ``adapter_image`` is required (``image=`` stays
+        refused) and steers the previews and the final denoise at ``adapter_conditioning_scale`` / ``adapter_conditioning_factor`` (counted
+        per stage): one control image serves every candidate, its features are computed once per call.  An adapter makes no draws, so the
+        winner's latents are the bits of the pipe's own call with ``image=adapter_image``, the scale and the factor, and that seed's
+        generator.  On a pipe without an adapter ``adapter_image`` is refused (ValueError).
         Returns dict(images, best_seed, scores, latents)."""
         from . import pns
         from .pipeline import (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline, _ControlNetPipe,
@@ -317,6 +323,20 @@ class IPAdapterXL(IPAdapter):
         if controlnet is not None:
             check_controlnet_args(control_image, "control_image", controlnet_conditioning_scale, schedule_kw.pop("guess_mode", False),
                                   schedule_kw.get("controlnet_guidance_start", 0.0), schedule_kw.get("controlnet_guidance_end", 1.0))
+        t2i = getattr(pipe, "adapter", None)
+        if t2i is None and adapter_image is not None:
+            raise ValueError("adapter_image= belongs to a T2I-Adapter pipeline: this pipe has no .adapter")
+        if t2i is not None:
+            from .pipeline import check_adapter_args, prepare_adapter_image
+            if adapter_image is None:
+                raise ValueError("PNS on a T2I-Adapter pipe needs adapter_image= (the control image)")
+            check_adapter_args(adapter_image, adapter_conditioning_scale, adapter_conditioning_factor)
+            ad_img = prepare_adapter_image(adapter_image)
+            if ad_img.dim() != 4 or ad_img.shape[0] != 1:
+                raise ValueError(f"PNS runs its candidates under one adapter image, got {tuple(ad_img.shape)}")
+            height, width = height or int(ad_img.shape[2]), width or int(ad_img.shape[3])
+            t2i.check_image(ad_img, height, width)
+            schedule_kw["adapter_conditioning_factor"] = float(adapter_conditioning_factor)
         inpaint = isinstance(pipe, StableDiffusionXLInpaintCustomPipeline)
         edit = inpaint or isinstance(pipe, StableDiffusionXLImg2ImgCustomPipeline)
         if edit:
@@ -338,6 +358,8 @@ class IPAdapterXL(IPAdapter):
         eng = pipe.engine
         if controlnet is not None:
             eng.set_controlnet(controlnet)
+        if t2i is not None:
+            eng.set_adapter(t2i)
         if edit:
             # everything a candidate shares is computed once, the moments at batch 1 as the pipelines encode a per-sample-generator call;
             # a candidate costs its draws, one fused initial-latents launch (stacked ``batch`` per call) and the truncated denoise
@@ -364,6 +386,9 @@ class IPAdapterXL(IPAdapter):
                         # once per call, behind the first conditioning; later re-conditionings prepare the hint and the ControlNet's
                         # caches again for their stack size themselves (DenoiseEngine.set_conditioning -> _prepare_control)
                         eng.set_control_image(control, conditioning_scale=float(controlnet_conditioning_scale))
+                    if t2i is not None:
+                        # the same image at every re-conditioning: the features are computed at the first and kept (set_adapter_image)
+                        eng.set_adapter_image(ad_img, conditioning_scale=float(adapter_conditioning_scale))
                     state["n"] = n
                 return stage(noise, **kw)
             return fn

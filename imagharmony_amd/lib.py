@@ -125,6 +125,14 @@ class ControlAddArgs(C.Structure):
                 ("B", _i32), ("Br", _i32), ("HW", _i32), ("C", _i32), ("sub", _i32), ("dtype", _i32)]
 
 
+class AdapterArgs(C.Structure):
+    _fields_ = [("x", _vp), ("y", _vp), ("n", C.c_int64), ("mode", _i32), ("N", _i32), ("C", _i32), ("H", _i32), ("W", _i32),
+                ("f", _i32), ("Cp", _i32), ("dtype", _i32)]
+
+
+ADAPTER_UNSHUFFLE, ADAPTER_RELU, ADAPTER_AVGPOOL2 = range(3)      # imh_adapter_op's modes (eager only: no plan kind)
+
+
 class F32Args(C.Structure):
     _fields_ = [("X", _vp), ("W", _vp), ("Y", _vp), ("bias", _vp), ("residual", _vp), ("gamma", _vp), ("beta", _vp), ("ws", _vp),
                 ("M", _i32), ("N", _i32), ("K", _i32), ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32),
@@ -180,6 +188,12 @@ SYMBOLS = [
     ("imh_plan_get_kind", C.c_int, [_vp, C.c_int]),
 ]
 
+# the one symbol include/imh_adapter.h declares (the T2I-Adapter's per-image passes): a companion header, a companion list -- SYMBOLS is
+# what include/imh.h declares, name for name
+ADAPTER_SYMBOLS = [
+    ("imh_adapter_op", C.c_int, [C.POINTER(AdapterArgs), _vp]),
+]
+
 _lib = None
 
 
@@ -196,7 +210,7 @@ def load():
         raise ImhError(f"{LIB_PATH} is missing: build the HIP extension first "
                        f"(python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -560,3 +560,103 @@ class StableDiffusionXLControlNetInpaintCustomPipeline(_ControlNetPipe, StableDi
         if masked_image_latents is not None:
             raise NotImplementedError("masked_image_latents= is not supported: the masked image is encoded from `image` and `mask_image`")
         return self._run(_ControlNetEditCall(locals(), "inpainting"))
+
+
+def prepare_adapter_image(image):
+    """diffusers ``_preprocess_adapter_image``: a PIL image (or a list of them) -> float32 [n, 3, H, W] in [0, 1] (``/ 255``, not normalised);
+    a float tensor [n, 3, H, W] / [3, H, W] in [0, 1] passes through.  Nothing is resized: the adapter's features are tied to the pixels,
+    and a control image of another size than the call's is refused (T2IAdapter.check_image)."""
+    if torch.is_tensor(image):
+        img = image.detach().to("cpu", torch.float32)
+        return (img[None] if img.dim() == 3 else img).contiguous()
+    import numpy as np
+    from PIL import Image
+    imgs = list(image) if isinstance(image, (list, tuple)) else [image]
+    out = []
+    for im in imgs:
+        if torch.is_tensor(im):
+            out.append(im.detach().to("cpu", torch.float32).reshape((-1,) + tuple(im.shape[-2:])))
+            continue
+        if not isinstance(im, Image.Image):
+            raise ValueError(f"adapter image of type {type(im).__name__}: a PIL image, a list of PIL images or a float tensor")
+        out.append(torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.float32) / 255.0).permute(2, 0, 1))
+    if len({tuple(t.shape) for t in out}) != 1:
+        raise ValueError("the adapter images of one call must share one size")
+    return torch.stack(out, 0).contiguous()
+
+
+def check_adapter_args(image, scale, factor):
+    """what the adapter __call__ (and generate_pns) refuses before any GPU work"""
+    if image is None:
+        raise ValueError("the T2I-Adapter pipeline needs `image`: the control image (PIL or a float tensor [n, 3, H, W] in [0, 1])")
+    if isinstance(scale, (list, tuple)):
+        raise NotImplementedError("a list of conditioning scales belongs to MultiAdapter, which is not supported")
+    if not 0.0 <= float(factor) <= 1.0:
+        raise ValueError(f"adapter_conditioning_factor {factor} must lie in [0, 1]")
+
+
+class _AdapterCall(_Call):
+    """text-to-image under a T2I-Adapter: the control image (the call's ``image``) fixes height / width unless they are given, the
+    adapter's scale and factor travel to the engine"""
+
+    def begin(self, pipe):
+        self.cond = prepare_adapter_image(self.image)
+        if self.cond.dim() != 4:
+            raise ValueError(f"adapter image {tuple(self.cond.shape)}: expected [n, 3, H, W]")
+        self.height = self.height or int(self.cond.shape[2])               # upstream's _default_height_width: the image's
+        self.width = self.width or int(self.cond.shape[3])
+        pipe.adapter.check_image(self.cond, self.height, self.width)
+        super().begin(pipe)
+
+    def schedule_kw(self, pipe, S):
+        if self.cond.shape[0] not in (1, S):
+            raise ValueError(f"{self.cond.shape[0]} adapter images for {S} samples: one image, or one per sample")
+        return dict(super().schedule_kw(pipe, S), adapter_conditioning_factor=float(self.adapter_conditioning_factor))
+
+    def condition(self, pipe, eng):
+        eng.set_adapter(pipe.adapter)
+        super().condition(pipe, eng)
+        eng.set_adapter_image(self.cond, conditioning_scale=float(self.adapter_conditioning_scale))
+
+
+class StableDiffusionXLAdapterCustomPipeline(StableDiffusionXLCustomPipeline):
+    """Text-to-image under a T2I-Adapter, with diffusers' ``StableDiffusionXLAdapterPipeline`` call surface (0.30) for what this path
+    builds: one ``t2i_adapter.T2IAdapter`` ("full_adapter_xl"), one control image (or one per sample), ``adapter_conditioning_scale`` and
+    ``adapter_conditioning_factor`` (the fraction of the steps, from the first, that get the features).  The adapter runs once per
+    control image -- a second call with the same image computes nothing --; the recorded step is the text-to-image step plus four gated
+    adds.  The pipe exposes ``.adapter``; ``IPAdapterXL.generate(..., image=, adapter_conditioning_scale=, adapter_conditioning_factor=)``
+    reaches ``__call__`` through its **kwargs.  Every sampler and ``step_noise`` mode of the base pipeline works unchanged.
+
+    Not built: the adapter in image-to-image / inpainting, together with a ControlNet, several adapters (``MultiAdapter`` / a list), the
+    SD-1.x adapter types (NotImplementedError)."""
+
+    def __init__(self, unet, adapter, scheduler=None, device="cuda:0", dtype=torch.bfloat16, **kw):
+        if isinstance(adapter, (list, tuple)) or hasattr(adapter, "adapters"):
+            raise NotImplementedError("several adapters (MultiAdapter / a list of adapters) are not supported: pass one T2IAdapter")
+        super().__init__(unet, scheduler=scheduler, device=device, dtype=dtype, **kw)
+        self.adapter = adapter
+        self.engine.set_adapter(adapter)
+
+    def to(self, device):
+        super().to(device)
+        self.adapter.to(self.device)
+        self.engine.set_adapter(self.adapter)
+        return self
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, height=None, width=None, num_inference_steps: int = 50, guidance_scale: float = 5.0,
+                 negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents=None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+                 callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
+                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator", **kwargs):
+        """image: the control image -- PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1] --, not normalised and not
+        resized: its sides are multiples of 2 x the adapter's downscale factor (32) and equal height / width (which default to the
+        image's); one image serves every sample.  Everything else as StableDiffusionXLCustomPipeline.__call__.
+        Refused before any GPU work: a list of scales (NotImplementedError); no image, an image of another size, a factor outside
+        [0, 1] (ValueError)."""
+        check_adapter_args(image, adapter_conditioning_scale, adapter_conditioning_factor)
+        return self._run(_AdapterCall(locals()))

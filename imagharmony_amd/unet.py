@@ -763,14 +763,39 @@ class UNet2DConditionModel(nn.Module):
             ctx.free(tsin)
 
     # ---- the encoder (down path + mid block), shared with controlnet.ControlNetModel ----
-    def _emit_encoder(self, ctx, st, h, tags, tag_step=0, prefix=""):
+    def _emit_encoder(self, ctx, st, h, tags, tag_step=0, prefix="", adapter=None):
         """h: the Feat after conv_in -> (the mid block's output, [h and every down-path output in skip order]).
         tags = (down ResNets / downsamplers, down transformers, mid ResNets, mid transformer); the first two advance by tag_step per
-        down block; prefix goes in front of the downsamplers' descr."""
+        down block; prefix goes in front of the downsamplers' descr.
+        adapter: a t2i_adapter.AdapterResiduals (diffusers UNet2DConditionModel.forward with down_intrablock_additional_residuals on the
+        SDXL layout; restated from its published source): feature 0 is added to the output of down block 0's downsampler, features 1 and
+        2 to the output of the last attention of down blocks 1 and 2 (before block 1's downsampler), feature 3 to the mid block's output
+        when the shapes match.  The sum REPLACES the tensor for every later reader, the skip connection included: upstream adds features
+        1 and 2 before it appends the skip, and writes ``sample += r`` for 0 and 3 into the tensor it has already appended.  Each
+        injection is one Ctx.control_add into a fresh buffer whose partials stand in for the superseded tensor's.  None: the launch
+        list is what it is without the argument (the ControlNet's walk never passes one)."""
         t_res, t_attn, t_mid_res, t_mid_attn = tags
         feats = [h]
         ho = GN_STATS_HANDOVER
         kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
+        nb = len(self.down_blocks)
+        if adapter is not None and (nb != 3 or self.down_blocks[0].has_attn or not (self.down_blocks[1].has_attn and self.down_blocks[2].has_attn)):
+            raise NotImplementedError("the adapter's injection points are those of the SDXL layout: DownBlock2D, CrossAttnDownBlock2D x 2, mid block")
+
+        def inject(f, k):
+            r = adapter.feats[k]
+            if r.dim() != 4 or tuple(r.shape[1:]) != tuple(f.t.shape[1:]) or f.t.shape[0] % r.shape[0] or not r.is_contiguous():
+                raise L.ImhError(f"adapter feature {k} {tuple(r.shape)} does not serve {tuple(f.t.shape)} (same pixels and channels, a batch that divides)")
+            tag, ctx.tag = ctx.tag, 33
+            # the partials of the sum stand in for the ones the superseded tensor's writer left (the ControlNet injections' gn_sub rule);
+            # a tensor that had none keeps getting them from its readers' statistics pass: the step grows by these four launches exactly
+            sub = math.gcd(f.t.shape[-1] // self.config.norm_num_groups, 10) if f.gs is not None else None
+            y = ctx.control_add(f.t, r, scale=adapter.scale, tab=adapter.tab, step=adapter.step, gn_sub=sub, descr=f"adapter.{k}")
+            y = Feat(*y) if sub is not None else Feat(y)
+            f.free(ctx)
+            ctx.tag = tag
+            return y
+
         for bi, blk in enumerate(self.down_blocks):
             for i, r in enumerate(blk.resnets):
                 ctx.tag = t_res + bi * tag_step
@@ -778,12 +803,16 @@ class UNet2DConditionModel(nn.Module):
                 if blk.has_attn:
                     ctx.tag = t_attn + bi * tag_step
                     h = blk.attentions[i].emit(ctx, h, kv_of(blk.attentions[i]), st)
+                    if adapter is not None and i == len(blk.resnets) - 1:
+                        h = inject(h, bi)
                 feats.append(h)
             if blk.downsamplers is not None:
                 ctx.tag = t_res + bi * tag_step
                 d = blk.downsamplers[0].conv
                 r_ = ctx.conv3x3(h.t, d.packed(ctx), bias=_b(d, ctx), stride=2, descr=prefix + "downsample", gn_groups=1 if ho else 0)
                 h = Feat(*r_) if ho else Feat(r_)
+                if adapter is not None and bi == 0:
+                    h = inject(h, 0)
                 feats.append(h)
         ctx.tag = t_mid_res
         mb = self.mid_block
@@ -792,17 +821,23 @@ class UNet2DConditionModel(nn.Module):
         h = mb.attentions[0].emit(ctx, h, kv_of(mb.attentions[0]), st)
         ctx.tag = t_mid_res
         h = mb.resnets[1].emit(ctx, h, st)
+        if adapter is not None and tuple(adapter.feats[3].shape[1:]) == tuple(h.t.shape[1:]):
+            h = inject(h, 3)
         return h, feats
 
     # ---- the forward, as emitted ops ----
-    def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None):
+    def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None, adapter=None):
         """Records one UNet forward.  Reads st.latents (fp32 NCHW [S,4,Hl,Wl]); batch B = 2S when
         cfg_dup (CFG halves share the latent, custom_pipelines.py:332).  Returns the noise prediction
         as NHWC [B, Hl*Wl, 4] in the compute dtype.
         control: a controlnet.ControlResiduals (diffusers down_block_additional_residuals / mid_block_additional_residual): after the
         mid block and before the up path every skip and the mid output are replaced by x + g * r (Ctx.control_add, whose partials
         take the place of the superseded tensor's); the down path and the mid block have read the unmodified tensors, as upstream.
-        The residuals are consumed.  None: the launch list is what it is without the argument."""
+        The residuals are consumed.  None: the launch list is what it is without the argument.
+        adapter: a t2i_adapter.AdapterResiduals (diffusers down_intrablock_additional_residuals): four gated adds inside the down path and
+        behind the mid block (_emit_encoder); the features are per-image state and are not consumed.  Not together with control."""
+        if adapter is not None and control is not None:
+            raise NotImplementedError("a T2I-Adapter together with a ControlNet is not built")
         cfg = self.config
         B = 2 * S if cfg_dup else S
         boc = cfg.block_out_channels
@@ -831,7 +866,7 @@ class UNet2DConditionModel(nn.Module):
                i=(S, Hl, Wl, boc[0], B, 9 if cin == 9 else 0), f=(1.0, 0, 0, 0), descr="conv_in", x2=extra,
                nbytes=2.0 * B * Hl * Wl * boc[0])
         h = Feat(x)                      # (conv_in has no statistics epilogue: Feat.stats() takes one pass, shared by both readers)
-        h, skips = self._emit_encoder(ctx, st, h, (10, 20, 30, 31), 1)
+        h, skips = self._emit_encoder(ctx, st, h, (10, 20, 30, 31), 1, **({"adapter": adapter} if adapter is not None else {}))
         ho = GN_STATS_HANDOVER
         kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
         if control is not None:
@@ -901,10 +936,20 @@ class UNet2DConditionModel(nn.Module):
         dev = sample.device
         dtype = self.conv_in.weight.dtype if self.conv_in.weight.dtype in (torch.bfloat16, torch.float16) \
             else (sample.dtype if sample.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16)
+        intra = kw.pop("down_intrablock_additional_residuals", None)
+        if intra is not None:                    # a T2I-Adapter's features: four NCHW tensors, already scaled (diffusers T2IAdapter.forward's outputs)
+            if kw.get("down_block_additional_residuals") is not None or kw.get("mid_block_additional_residual") is not None:
+                raise NotImplementedError("down_intrablock_additional_residuals together with the ControlNet pair is not built")
+            if not isinstance(intra, (list, tuple)) or len(intra) != 4:
+                raise NotImplementedError("down_intrablock_additional_residuals is the list of the XL adapter's four features")
         ctx = Ctx(dev, dtype)
         B, _, Hl, Wl = sample.shape
         st = self.prepare_conditioning(ctx, encoder_hidden_states, added_cond_kwargs["text_embeds"],
                                        added_cond_kwargs["time_ids"])
+        adapter = None
+        if intra is not None:
+            from .t2i_adapter import AdapterResiduals
+            adapter = AdapterResiduals([t.to(device=dev, dtype=dtype).permute(0, 2, 3, 1).contiguous() for t in intra])
         t = timestep if torch.is_tensor(timestep) else torch.tensor([float(timestep)])
         st.t_value = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
         st.latents = sample[:, :4].to(torch.float32).contiguous()
@@ -918,6 +963,6 @@ class UNet2DConditionModel(nn.Module):
             from .controlnet import ControlResiduals
             nhwc = lambda t: t.to(device=dev, dtype=dtype).permute(0, 2, 3, 1).contiguous()
             control = ControlResiduals([nhwc(t) for t in down_res], nhwc(mid_res))
-        out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, control=control)
+        out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, control=control, **({"adapter": adapter} if adapter is not None else {}))
         y = out.view(B, Hl, Wl, -1).permute(0, 3, 1, 2).to(sample.dtype)
         return (y,)

@@ -46,7 +46,8 @@ extern "C" {
  * three entries (imh_step_seeded, imh_randn_seeded, imh_randn_seeded_host) with argument structs of their own and two plan kinds
  * (IMH_OP_STEP_SEEDED = 10, IMH_OP_RANDN_SEEDED = 11); enum imh_ew_op and imh_ew_args are as they were.  And for the image op of the PNS
  * judge: one entry (imh_clip_preprocess) with an argument struct of its own and one plan kind (IMH_OP_CLIP_PREPROCESS = 13).  And for the
- * ControlNet's gated residual add: one entry (imh_control_add), an argument struct of its own, one plan kind (IMH_OP_CONTROL_ADD = 15; 12 and 14 stay refused). */
+ * ControlNet's gated residual add: one entry (imh_control_add), an argument struct of its own, one plan kind (IMH_OP_CONTROL_ADD = 15; 12 and 14 stay refused).
+ * The T2I-Adapter's per-image passes have a header of their own, include/imh_adapter.h: this one is as it was. */
 #define IMH_ABI_VERSION 13
 
 enum imh_status {
