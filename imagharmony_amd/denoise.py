@@ -10,6 +10,8 @@ launch and reads its add_noise pair from one more table), and a 9-channel UNet r
 step-invariant buffer inside conv_in.  A ControlNet branch (set_controlnet) is recorded in front of the UNet in any of these modes: it reads the
 4-channel latents alone, and neither inpainting mode adds a launch to it.
 """
+import collections
+import functools
 import hashlib
 import os
 
@@ -22,42 +24,117 @@ from .unet import StepState
 # XCD cell policy measured once per (device, UNet batch, latent size, dtype) and process: every engine (and fork) of that shape reuses it
 _XCD_PICK = {}
 
+# inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
+INPAINT_BUFFERS = ("inp_z", "inp_noise", "inp_mask", "conv_in_extra")
+# what a plan that ends with the general step (EW_CFG_MSTEP) points at besides: the six-column table, the history slot and the noise
+# bank -- or, under a seeded schedule, the samples' seed rows
+GENERAL_STEP = ("coef6_tab", "hist", "noise_bank", "seed_rows")
+# THE list of StepState members that are valid exactly as long as one recorded plan is: what the plan cache stores and restores.  The
+# other two places that move such members from one StepState to another are written as differences from it:
+PLAN_STATE = ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + GENERAL_STEP
+# - a new conditioning (set_conditioning) keeps the schedule's tables, the latents, the counter and the inpainting buffers, but not the
+#   time-embedding rows: they were computed from the previous conditioning's aug_emb
+_CARRIED = (set(PLAN_STATE) - {"temb_table"}) | {"latents", "step"} | set(INPAINT_BUFFERS)
+# - a fork has its own (zeroed) general-step state, like its latents, shares the other tables and records its own time-embedding rows
+_FORK_OWN = ("hist", "noise_bank", "seed_rows")
+_FORK_SHARED = set(PLAN_STATE) - set(_FORK_OWN) - {"temb_table"}
+# ... and the engine's members of the same lifetime: the step count, the plan(s) and what they write, the context that owns the
+# time-embedding rows of the UNet and of the ControlNet, the conditioners' per-schedule tables
+_PLAN_ENGINE = ("steps", "init_noise_sigma", "plan", "noise_pred", "plan_tail", "np_full", "_temb_ctx", "cn_scale_tab", "_cn_temb", "ad_gate_tab")
+
+
+# What tells one recorded plan of a conditioning from another (set_schedule); used by name, compared and hashed as the tuple it is:
+#   scheduler (the class name), num_train_timesteps, num_inference_steps, control_guidance_start / _end (the IP-scale window),
+#   denoising_end, ip_scale (the IP processors' scale, the value of the gating table), steps (the row behind the last step that runs),
+#   tables (SHA-1 of every table the plan reads, the IP gating table included), controlnet (SHA-1 of cn_scale_tab; None: no branch),
+#   inpaint (None | "blend" | "concat"), adapter ((SHA-1 of ad_gate_tab, conditioning scale); None: no T2I-Adapter), seeded
+PlanKey = collections.namedtuple("PlanKey", "scheduler num_train_timesteps num_inference_steps control_guidance_start control_guidance_end "
+                                 "denoising_end ip_scale steps tables controlnet inpaint adapter seeded")
+
+
+def _move(names, src, dst):
+    for k in names:
+        setattr(dst, k, getattr(src, k, None))       # (None: a StepState has no coef_tab until set_schedule gives it one)
+
+
+class PlanRecord:
+    """One entry of the plan cache: every member of PLAN_STATE and _PLAN_ENGINE as it was when the plan was recorded."""
+    __slots__ = PLAN_STATE + _PLAN_ENGINE
+
+    def __init__(self, eng):
+        _move(PLAN_STATE, eng.st, self)
+        _move(_PLAN_ENGINE, eng, self)
+
+    def restore(self, eng):
+        _move(PLAN_STATE, self, eng.st)
+        _move(_PLAN_ENGINE, self, eng)
+
 
 class DenoiseEngine:
-    def __init__(self, unet, device, dtype=torch.bfloat16, use_graph=True):
-        self.unet = unet
-        self.device = torch.device(device)
-        self.dtype = dtype
-        self.use_graph = use_graph
-        self.eager = Ctx(self.device, dtype)
-        self.st = None
-        self.plan = None
-        self.key = None
-        self.noise_pred = None
-        # XCD cell shapes tried when the plan is first recorded (_pick_xcd_cells): the byte-count model, 4 x 2 and 8 x 1 cells, and
-        # 4 x 2 with the GEGLU launches left to the model (13); the choice sticks for the life of the engine
-        # (IMH_XCD_AUTOTUNE=0: model only)
-        self.xcd_candidates = (0, 3, 2, 13) if os.environ.get("IMH_XCD_AUTOTUNE", "1") != "0" else (0,)
-        self.xcd_cells = None
-        self._is_fork = False
-        self._plans = {}         # recorded plans by schedule key (two-stage PNS alternates a preview and a final schedule per image)
-        self.max_cached_plans = int(os.environ.get("IMH_MAX_CACHED_PLANS", "3"))      # each pins ~2 GB of activation buffers at 1024^2
-        self._sched_key = None
-        self.t_start = 0         # image-to-image: the first step of the schedule that runs (set_schedule)
-        self.inpaint = None      # None | "blend" (4-channel UNet: masked blend in the step) | "concat" (9-channel UNet: conv_in reads the mask)
-        self.general = False     # the schedule steps through the six-column table (EW_CFG_MSTEP): multistep / ancestral samplers (set_schedule)
-        self.stochastic = False  # ... and reads a noise row per step
-        self.seeded = False      # ... which the step generates from st.seed_rows instead of reading a bank (set_schedule(seeded_noise=True))
-
-    # the ControlNet state (class-level defaults: an engine without one carries nothing)
+    # Every member the engine reads exists on every engine: the ones below start from these defaults (immutable values, so the class can
+    # hold them -- an engine put together without the constructor reads them too), the rest is set by the constructor.
+    # the conditioning (set_conditioning)
+    st = None
+    S = H = W = T_total = None
+    do_cfg, guidance, guidance_rescale = False, None, 0.0
+    cfg_role = None          # 0 / 1: this engine computes one half of the CFG pair (denoise_cfg_split)
+    _cond_ctx = None         # the context that owns aug_emb and the K / V caches
+    _cond_in = None          # (ehs, text, ids) as the UNet got them: the ControlNet's caches are computed from the same
+    # the current plan and what lives as long as it does (_PLAN_ENGINE; set_schedule, _record)
+    plan = noise_pred = None
+    plan_tail = None         # cfg_role engines: the second plan (CFG combine + scheduler step + step++) ...
+    np_full = None           # ... and the [2, S, ...] buffer of both halves it reads
+    steps = init_noise_sigma = None
+    _temb_ctx = _cn_temb = None      # the context that owns the time-embedding rows; the ControlNet's rows in it
+    _sched_key = None
+    xcd_cells = None         # the XCD cell shape picked when the plan is first recorded (_pick_xcd_cells) ...
+    xcd_times_ms = None      # ... and {candidate: median forward ms} of the pick it came from
+    _is_fork = False
+    t_start = 0              # image-to-image: the first step of the schedule that runs (set_schedule)
+    inpaint = None           # None | "blend" (4-channel UNet: masked blend in the step) | "concat" (9-channel UNet: conv_in reads the mask)
+    general = False          # the schedule steps through the six-column table (EW_CFG_MSTEP): multistep / ancestral samplers (set_schedule)
+    stochastic = False       # ... and reads a noise row per step
+    seeded = False           # ... which the step generates from st.seed_rows instead of reading a bank (set_schedule(seeded_noise=True))
+    # the ControlNet state (an engine without one carries nothing)
     controlnet = None        # a controlnet.ControlNetModel whose branch is recorded in front of the UNet (set_controlnet)
     cn = None                # its state: dict(image, scale, hint, cond = StepState with its aug_emb / K,V caches) (set_control_image)
     cn_scale_tab = None      # fp32 [steps] conditioning_scale * keep(i) of the current schedule (set_schedule)
-
     # the T2I-Adapter state, likewise
     adapter = None           # a t2i_adapter.T2IAdapter whose four features are added inside the UNet's down path (set_adapter)
     ad = None                # its state: dict(image, scale, feats = four NHWC tensors, ctx) (set_adapter_image)
     ad_gate_tab = None       # fp32 [steps] 1 / 0 per step of the current schedule (set_schedule(adapter_conditioning_factor=))
+
+    def __init__(self, unet, device, dtype=torch.bfloat16, use_graph=True):
+        """Touches no device: the eager context is made on first use, so the "no CPU path" ImhError of a non-ROCm device surfaces at the
+        first launch (or the first set_conditioning), not here."""
+        self.unet, self.device, self.dtype, self.use_graph = unet, torch.device(device), dtype, use_graph
+        # XCD cell shapes tried when the plan is first recorded (_pick_xcd_cells): the byte-count model, 4 x 2 and 8 x 1 cells, and
+        # 4 x 2 with the GEGLU launches left to the model (13); the choice sticks for the life of the engine
+        # (IMH_XCD_AUTOTUNE=0: model only)
+        self.xcd_candidates = (0, 3, 2, 13) if os.environ.get("IMH_XCD_AUTOTUNE", "1") != "0" else (0,)
+        self._plans = {}         # recorded plans by schedule key (two-stage PNS alternates a preview and a final schedule per image)
+        self.max_cached_plans = int(os.environ.get("IMH_MAX_CACHED_PLANS", "3"))      # each pins ~2 GB of activation buffers at 1024^2
+
+    @functools.cached_property
+    def eager(self):
+        """the context of the few launches outside a plan (the step counter's reset, the initial latents): made on first use"""
+        return Ctx(self.device, self.dtype)
+
+    # -- what the two conditioners (ControlNet, T2I-Adapter) share --
+    @staticmethod
+    def _whole_pair_only(half, what):
+        if half:
+            raise NotImplementedError(f"an engine that holds one half of the CFG pair (cfg_role) does not run a {what}")
+
+    def _drop_plans(self, doomed):
+        """drops the current plan and the cached plans whose key `doomed` holds for: they point at state that is going away"""
+        self._plans = {k: v for k, v in self._plans.items() if not doomed(k)}
+        self.plan, self._sched_key = None, None
+
+    @staticmethod
+    def _image_fits(image, S, height, width):
+        """a stored control image serves S samples at height x width: one image or one per sample, at that size"""
+        return tuple(image.shape[2:]) == (height, width) and image.shape[0] in (1, S)
 
     # -- T2I-Adapter (opt-in, like the ControlNet; the two exclude each other) --
     def set_adapter(self, adapter):
@@ -70,13 +147,12 @@ class DenoiseEngine:
                 raise TypeError(f"set_adapter takes an imagharmony_amd.t2i_adapter.T2IAdapter, not {type(adapter).__name__}")
             if self.controlnet is not None:
                 raise NotImplementedError("a T2I-Adapter together with a ControlNet is not built")
-            if getattr(self, "cfg_role", None) is not None:
-                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a T2I-Adapter")
+            self._whole_pair_only(self.cfg_role is not None, "T2I-Adapter")
         if adapter is not self.adapter:
-            if self.adapter is not None and adapter is not None:
+            swap = self.adapter is not None and adapter is not None
+            if swap:
                 self.ad = None                           # another model: its features go, and every plan recorded with them
-                self._plans = {k: v for k, v in self._plans.items() if k[11] is None}
-            self.plan, self._sched_key = None, None
+            self._drop_plans(lambda k: swap and k.adapter is not None)
         self.adapter = adapter
 
     @torch.no_grad()
@@ -88,15 +164,15 @@ class DenoiseEngine:
             raise L.ImhError("set_adapter_image needs an adapter: set_adapter first")
         self.adapter.check_image(image)
         old = self.ad
-        if old is not None and old["image"].shape == image.shape and torch.equal(old["image"], image.detach().to("cpu", torch.float32)):
+        same = old is not None and old["image"].shape == image.shape and torch.equal(old["image"], image.detach().to("cpu", torch.float32))
+        if same:
             old["scale"] = float(conditioning_scale)     # the same image: the features (and the plans that point at them) stay
         else:
             img = image.detach().to("cpu", torch.float32).clone()
             ctx = Ctx(self.device, self.dtype)           # fresh context: the features must outlive pooled buffers
             feats = self.adapter.prepare_features(ctx, img, img.shape[2] // 8, img.shape[3] // 8)
             self.ad = dict(image=img, scale=float(conditioning_scale), feats=feats, ctx=ctx)
-            self._plans = {k: v for k, v in self._plans.items() if k[11] is None}      # a plan recorded with the adapter points at the previous features
-        self.plan, self._sched_key = None, None
+        self._drop_plans(lambda k: not same and k.adapter is not None)     # a plan recorded with the adapter points at the previous features
 
     @staticmethod
     def adapter_gate_table(n, t_start, factor):
@@ -116,14 +192,14 @@ class DenoiseEngine:
                 raise NotImplementedError("several ControlNets (MultiControlNetModel) are not supported: one ControlNetModel")
             if not hasattr(controlnet, "controlnet_down_blocks") or not hasattr(controlnet, "prepare_hint"):
                 raise TypeError(f"set_controlnet takes an imagharmony_amd.controlnet.ControlNetModel, not {type(controlnet).__name__}")
-            if getattr(self, "cfg_role", None) is not None:
-                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+            self._whole_pair_only(self.cfg_role is not None, "ControlNet")
             if self.adapter is not None:
                 raise NotImplementedError("a ControlNet together with a T2I-Adapter is not built")
         if controlnet is not self.controlnet:
-            if self.controlnet is not None and controlnet is not None:
-                self.cn, self._plans = None, {}          # another model: its caches and every plan recorded with the old one go
-            self.plan, self._sched_key = None, None
+            swap = self.controlnet is not None and controlnet is not None
+            if swap:
+                self.cn = None                           # another model: its caches go, and every cached plan
+            self._drop_plans(lambda k: swap)
         self.controlnet = controlnet
 
     @torch.no_grad()
@@ -136,15 +212,13 @@ class DenoiseEngine:
         if self.controlnet is None:
             raise L.ImhError("set_control_image needs a ControlNet: set_controlnet first")
         self.cn = dict(image=image, scale=float(conditioning_scale), hint=None, cond=None)
-        self._plans = {k: v for k, v in self._plans.items() if k[9] is None}      # a plan recorded with the branch points at the previous hint
-        self.plan, self._sched_key = None, None
-        if self.st is not None and getattr(self, "_cond_in", None) is not None:
+        self._drop_plans(lambda k: k.controlnet is not None)      # a plan recorded with the branch points at the previous hint
+        if self.st is not None and self._cond_in is not None:
             self._prepare_control()
 
     def _prepare_control(self):
         cn, net = self.cn, self.controlnet
-        if getattr(self, "cfg_role", None) is not None:
-            raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+        self._whole_pair_only(self.cfg_role is not None, "ControlNet")
         img = cn["image"]
         if img.dim() != 4 or img.shape[0] not in (1, self.S):
             raise L.ImhError(f"control image {tuple(img.shape)}: one image or one per sample ({self.S}) as [n, 3, H, W]")
@@ -175,18 +249,12 @@ class DenoiseEngine:
         the serial tail of the two-stage PNS schedule)."""
         if cfg_role not in (None, 0, 1):
             raise ValueError("cfg_role must be None, 0 (unconditional half) or 1 (conditional half)")
-        if cfg_role is not None and self.controlnet is not None:
-            raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
-        if cfg_role is not None and self.adapter is not None:
-            raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a T2I-Adapter")
-        if cfg_role != getattr(self, "cfg_role", None):
-            self.plan = None
-        self._plans = {}                          # every recorded plan points into the previous conditioning's caches
+        self._whole_pair_only(cfg_role is not None and self.controlnet is not None, "ControlNet")
+        self._whole_pair_only(cfg_role is not None and self.adapter is not None, "T2I-Adapter")
+        self._plans, self.plan = {}, None         # every recorded plan points into the previous conditioning's caches
         self.cfg_role = cfg_role
         self.do_cfg = guidance_scale > 1.0                                   # custom_pipelines.py:223
         self.guidance = float(guidance_scale)
-        if float(guidance_rescale) != getattr(self, "guidance_rescale", 0.0):
-            self.plan = None
         self.guidance_rescale = float(guidance_rescale)                      # :351-354 (only with CFG)
         S = prompt_embeds.shape[0]
         osz, tsz = tuple(original_size or (height, width)), tuple(target_size or (height, width))
@@ -207,28 +275,20 @@ class DenoiseEngine:
         old = self.st
         self.st = st
         if old is not None:                      # keep per-run tables
-            for k in ("latents", "t_table", "step", "in_scale_tab", "ip_scale_tab", "coef_tab", "blend_tab") + self._GENERAL_STEP + self._INPAINT_BUFFERS:
-                setattr(st, k, getattr(old, k, None))
-        self.plan = None                         # conditioning buffers changed -> re-record
+            _move(_CARRIED, old, st)
         self._cond_in = (ehs, text, ids)
         if self.cn is not None:
             self.cn["hint"] = self.cn["cond"] = None      # the ControlNet's caches belong to the previous conditioning (and size)
             img = self.cn["image"]
-            if img.dim() == 4 and (tuple(img.shape[2:]) != (height, width) or img.shape[0] not in (1, S)):
+            if img.dim() == 4 and not self._image_fits(img, S, height, width):
                 # the previous call's control image does not fit this conditioning (an edit's size follows its image): it is dropped,
                 # not prepared at the wrong size; set_control_image sets this call's (set_schedule insists on one)
                 self.cn = None
             elif self.controlnet is not None:
                 self._prepare_control()
-        if self.ad is not None and (tuple(self.ad["image"].shape[2:]) != (height, width) or self.ad["image"].shape[0] not in (1, S)):
+        if self.ad is not None and not self._image_fits(self.ad["image"], S, height, width):
             self.ad = None                        # the previous call's control image does not fit this size or batch: set_adapter_image sets this call's
         return st
-
-    # inpainting state the recorded plan points at; a call copies into them (prepare_inpaint) and re-records nothing
-    _INPAINT_BUFFERS = ("inp_z", "inp_noise", "inp_mask", "conv_in_extra")
-    # what a plan that ends with the general step (EW_CFG_MSTEP) points at besides: the six-column table, the history slot and the noise
-    # bank -- or, under a seeded schedule, the samples' seed rows
-    _GENERAL_STEP = ("coef6_tab", "hist", "noise_bank", "seed_rows")
 
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
@@ -303,7 +363,9 @@ class DenoiseEngine:
                 raise NotImplementedError("the T2I-Adapter runs text-to-image schedules (image-to-image / inpainting with an adapter are not built)")
             ad_gate = self.adapter_gate_table(n, t_start, adapter_conditioning_factor)
             ad_key = (hashlib.sha1(torch.tensor(ad_gate, dtype=torch.float32).numpy().tobytes()).hexdigest(), self.ad["scale"])
-        key = (type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps), float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(), cn_key, mode, ad_key, seeded)
+        key = PlanKey(type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps),
+                      float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(),
+                      controlnet=cn_key, inpaint=mode, adapter=ad_key, seeded=seeded)
         self.t_start = t_start
         self.inpaint = mode
         self.general = general
@@ -313,13 +375,7 @@ class DenoiseEngine:
         if hit is not None:
             # a schedule this engine has run under this conditioning: its tables, time-embedding rows and recorded plan are still there
             # (the plan's launches point at them), so a preview / final alternation re-records nothing
-            for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + self._GENERAL_STEP:
-                setattr(st, k, hit["st"][k])
-            self.steps, self.init_noise_sigma = hit["steps"], hit["init_noise_sigma"]
-            self.plan, self.noise_pred, self._temb_ctx = hit["plan"], hit["noise_pred"], hit["temb_ctx"]
-            self.plan_tail, self.np_full = hit.get("plan_tail"), hit.get("np_full")
-            self.cn_scale_tab, self._cn_temb = hit.get("cn_scale_tab"), hit.get("cn_temb")
-            self.ad_gate_tab = hit.get("ad_gate_tab")
+            hit.restore(self)
             self._sched_key = key
             return
         st.t_table = tab["timesteps"].to(dev)
@@ -362,20 +418,16 @@ class DenoiseEngine:
         stream each), so that kernels of independent candidates fill the CUs a batch-1 kernel leaves idle."""
         e = DenoiseEngine(self.unet, self.device, self.dtype, self.use_graph)
         e._is_fork = True                        # never tunes: it may record while its parent is running on another stream
-        for k in ("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
-                  "xcd_candidates", "xcd_cells", "t_start", "inpaint"):
-            setattr(e, k, getattr(self, k))
-        e.general, e.stochastic, e.seeded = self.general, self.stochastic, self.seeded
-        e.controlnet, e.cn, e.cn_scale_tab = self.controlnet, self.cn, self.cn_scale_tab      # shared, read-only during denoising: hint, caches, table
-        e.adapter, e.ad, e.ad_gate_tab = self.adapter, self.ad, self.ad_gate_tab              # likewise: the adapter's features and its gate table
+        _move(("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
+               "xcd_candidates", "xcd_cells", "t_start", "inpaint", "general", "stochastic", "seeded"), self, e)
+        # shared, read-only during denoising: the ControlNet's hint, caches and table, the adapter's features and gate table
+        _move(("controlnet", "cn", "cn_scale_tab", "adapter", "ad", "ad_gate_tab"), self, e)
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
-        st.t_table, st.coef_tab, st.in_scale_tab, st.ip_scale_tab = src.t_table, src.coef_tab, src.in_scale_tab, src.ip_scale_tab
-        st.blend_tab = getattr(src, "blend_tab", None)               # (the mask, image latents and noise are the fork's own: _record)
-        st.coef6_tab = getattr(src, "coef6_tab", None)
-        for k in ("hist", "noise_bank", "seed_rows"):                # the general step's state is the fork's own, like its latents
-            v = getattr(src, k, None)
+        _move(_FORK_SHARED, src, st)                                 # (the mask, image latents and noise are the fork's own: _record)
+        for k in _FORK_OWN:                                          # the general step's state is the fork's own, like its latents
+            v = getattr(src, k)
             setattr(st, k, None if v is None else torch.zeros_like(v))
         st.step = torch.zeros(1, dtype=torch.int32, device=self.device)
         e.st = st
@@ -385,22 +437,21 @@ class DenoiseEngine:
         st = self.st
         if st.latents is None or tuple(st.latents.shape) != (self.S, 4, self.H, self.W):
             st.latents = torch.zeros(self.S, 4, self.H, self.W, dtype=torch.float32, device=self.device)
-        split = self.do_cfg and getattr(self, "cfg_role", None) is not None
+        split = self.do_cfg and self.cfg_role is not None
         if self.inpaint and split:
             raise NotImplementedError("inpainting runs on an engine that holds both halves of the CFG pair (cfg_role = None)")
         if self.unet.config.in_channels == 9 and self.inpaint != "concat":
             raise L.ImhError("a UNet with in_channels = 9 runs inpainting schedules only (set_schedule(..., inpaint=True), prepare_inpaint)")
         want = {"blend": (("inp_z", 4), ("inp_noise", 4), ("inp_mask", 1)), "concat": (("conv_in_extra", 5),)}.get(self.inpaint, ())
         for k, c in want:
-            if getattr(st, k, None) is None or tuple(getattr(st, k).shape) != (self.S, c, self.H, self.W):
+            if getattr(st, k) is None or tuple(getattr(st, k).shape) != (self.S, c, self.H, self.W):
                 setattr(st, k, torch.zeros(self.S, c, self.H, self.W, dtype=torch.float32, device=self.device))
         # the time-embedding rows of every step of this schedule under this conditioning: once here, not five launches per step
         self._temb_ctx = Ctx(self.device, self.dtype)          # (its pool owns the table for the life of the plan)
         self.unet.precompute_temb(self._temb_ctx, st, st.t_table)
-        cst = None
+        cst = self._cn_temb = None
         if self.controlnet is not None:
-            if split:
-                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a ControlNet")
+            self._whole_pair_only(split, "ControlNet")
             if self.cn is None or self.cn.get("hint") is None or self.cn.get("cond") is None or self.cn_scale_tab is None:
                 raise L.ImhError("the ControlNet branch needs set_conditioning, set_control_image and then set_schedule")
             from .controlnet import control_state
@@ -426,12 +477,11 @@ class DenoiseEngine:
                                                    tab=self.cn_scale_tab)
         extra = {"control": control} if control is not None else {}
         if self.adapter is not None:
-            if split:
-                raise NotImplementedError("an engine that holds one half of the CFG pair (cfg_role) does not run a T2I-Adapter")
+            self._whole_pair_only(split, "T2I-Adapter")
             if self.ad is None or self.ad_gate_tab is None:
                 raise L.ImhError("the T2I-Adapter needs set_adapter_image and then set_schedule")
             img = self.ad["image"]
-            if tuple(img.shape[2:]) != (8 * self.H, 8 * self.W) or img.shape[0] not in (1, self.S):
+            if not self._image_fits(img, self.S, 8 * self.H, 8 * self.W):
                 raise L.ImhError(f"adapter image {tuple(img.shape)}: one image or one per sample ({self.S}) at {8 * self.H} x {8 * self.W}")
             from .t2i_adapter import AdapterResiduals
             extra["adapter"] = AdapterResiduals(self.ad["feats"], scale=self.ad["scale"], tab=self.ad_gate_tab, step=st.step)
@@ -441,66 +491,45 @@ class DenoiseEngine:
             # second tiny plan over BOTH halves ([uncond | cond] = the layout the fused step reads), run after the per-step exchange
             if self.use_graph:
                 rec.capture()
-            self.plan, self.noise_pred = rec, out
-            self.np_full = torch.empty((2,) + tuple(out.shape), dtype=out.dtype, device=self.device)
+            pred = torch.empty((2,) + tuple(out.shape), dtype=out.dtype, device=self.device)
             tail = Ctx(self.device, self.dtype, record=True)
-            fac = None
-            if getattr(self, "guidance_rescale", 0.0) > 0.0:
-                fac = tail.new(self.S, dtype=torch.float32)
-                tail.ew(L.EW_CFG_RESCALE, fac, a=self.np_full, i=(self.S, self.H * self.W, 0, 0, 0, 0),
-                        f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
-            if self.general:
-                tail.ew(L.EW_CFG_MSTEP, st.latents, a=self.np_full, w=fac, tab=st.coef6_tab, step=st.step, hist=st.hist, bank=st.noise_bank,
-                        seeds=st.seed_rows if self.seeded else None,
-                        i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+mstep+seeded" if self.seeded else "cfg+mstep")
-            else:
-                tail.ew(L.EW_CFG_STEP, st.latents, a=self.np_full, w=fac, tab=st.coef_tab, step=st.step,
-                        i=(self.S, self.H * self.W, 0, 1, 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
-            tail.ew(L.EW_STEP_SET, st.step, i=(0, 0, 0, 0, 0, 0), descr="step++")
-            if self.use_graph:
-                tail.capture()
-            self.plan_tail = tail
-            self._remember_plan()
-            return
-        rec.tag = 70
-        fac = None
-        if self.do_cfg and getattr(self, "guidance_rescale", 0.0) > 0.0:     # rescale_noise_cfg, custom_pipelines.py:351-354
-            fac = rec.new(self.S, dtype=torch.float32)
-            rec.ew(L.EW_CFG_RESCALE, fac, a=out, i=(self.S, self.H * self.W, 0, 0, 0, 0),
-                   f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
-        if self.general:
-            # the multistep / ancestral samplers: the same launch with the six-column row, the history slot and the step's noise row
-            # (imh.h IMH_EW_CFG_MSTEP); the blend rides in it as it rides in EW_CFG_STEP
-            kw = dict(x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab) if self.inpaint == "blend" else {}
-            # a seeded schedule: no bank, the launch generates the row from the samples' seed rows (imh.h imh_step_seeded)
-            rec.ew(L.EW_CFG_MSTEP, st.latents, a=out, w=fac, tab=st.coef6_tab, step=st.step, hist=st.hist, bank=st.noise_bank,
-                   seeds=st.seed_rows if self.seeded else None,
-                   i=(self.S, self.H * self.W, 0, int(self.do_cfg), self.S if kw else 0, 0), f=(0.0, 0.0, self.guidance, 0.0),
-                   descr=("cfg+mstep+seeded" if self.seeded else "cfg+mstep") + ("+blend" if kw else ""), **kw)
-        elif self.inpaint == "blend":
-            # ... and upstream's masked blend in the same launch (imh.h IMH_EW_CFG_STEP): no extra launch, no extra pass over the latents
-            rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
-                   i=(self.S, self.H * self.W, 0, int(self.do_cfg), self.S, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step+blend",
-                   x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab)
+            self._emit_step_tail(tail, pred)
         else:
-            rec.ew(L.EW_CFG_STEP, st.latents, a=out, w=fac, tab=st.coef_tab, step=st.step,
-                   i=(self.S, self.H * self.W, 0, int(self.do_cfg), 0, 0), f=(0.0, 0.0, self.guidance, 0.0), descr="cfg+step")
-        rec.ew(L.EW_STEP_SET, st.step, i=(0, 0, 0, 0, 0, 0), descr="step++")
+            rec.tag = 70
+            pred, tail = out, rec
+            self._emit_step_tail(rec, out)
         if self.use_graph:
-            rec.capture()
-        self.plan = rec
-        self.noise_pred = out
+            tail.capture()
+        self.plan, self.noise_pred = rec, out
+        self.plan_tail, self.np_full = (tail, pred) if split else (None, None)
         self._remember_plan()
+
+    def _emit_step_tail(self, ctx, pred):
+        """The end of a step, recorded into ctx: rescale_noise_cfg's factor where asked for (custom_pipelines.py:351-354), then ONE launch
+        for the CFG combine and the scheduler step -- EW_CFG_STEP, or for the multistep / ancestral samplers EW_CFG_MSTEP with the
+        six-column row, the history slot and the step's noise row (a seeded schedule: no bank, the launch generates the row from the
+        samples' seed rows, imh.h imh_step_seeded); upstream's masked blend rides in either (no extra launch, no extra pass over the
+        latents) -- then step++.  pred: the noise prediction, [uncond | cond] under CFG -- the forward's output, or on a cfg_role engine
+        the buffer of both ranks' halves (such an engine always combines and never blends)."""
+        st, S, HW = self.st, self.S, self.H * self.W
+        fac = None
+        if self.do_cfg and self.guidance_rescale > 0.0:
+            fac = ctx.new(S, dtype=torch.float32)
+            ctx.ew(L.EW_CFG_RESCALE, fac, a=pred, i=(S, HW, 0, 0, 0, 0), f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
+        blend = dict(x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab) if self.inpaint == "blend" else {}
+        if self.general:
+            op, tab, descr = L.EW_CFG_MSTEP, st.coef6_tab, "cfg+mstep+seeded" if self.seeded else "cfg+mstep"
+            more = dict(hist=st.hist, bank=st.noise_bank, seeds=st.seed_rows if self.seeded else None)
+        else:
+            op, tab, descr, more = L.EW_CFG_STEP, st.coef_tab, "cfg+step", {}
+        ctx.ew(op, st.latents, a=pred, w=fac, tab=tab, step=st.step, i=(S, HW, 0, int(self.do_cfg), S if blend else 0, 0),
+               f=(0.0, 0.0, self.guidance, 0.0), descr=descr + ("+blend" if blend else ""), **more, **blend)
+        ctx.ew(L.EW_STEP_SET, st.step, i=(0, 0, 0, 0, 0, 0), descr="step++")
 
     def _remember_plan(self):
         if self._sched_key is None:
             return
-        st = self.st
-        self._plans[self._sched_key] = dict(
-            st={k: getattr(st, k, None) for k in ("t_table", "coef_tab", "in_scale_tab", "ip_scale_tab", "temb_table", "blend_tab") + self._GENERAL_STEP},
-            steps=self.steps, init_noise_sigma=self.init_noise_sigma, plan=self.plan, noise_pred=self.noise_pred,
-            temb_ctx=self._temb_ctx, plan_tail=getattr(self, "plan_tail", None), np_full=getattr(self, "np_full", None),
-            cn_scale_tab=self.cn_scale_tab, cn_temb=getattr(self, "_cn_temb", None), ad_gate_tab=self.ad_gate_tab)
+        self._plans[self._sched_key] = PlanRecord(self)
         while len(self._plans) > self.max_cached_plans:              # (each plan keeps ~2 GB of activation buffers alive at 1024^2)
             self._plans.pop(next(iter(self._plans)))
 
@@ -585,7 +614,7 @@ class DenoiseEngine:
         Euler ancestral) are refused here under a bank schedule: the two ranks would have to fill identical noise banks.  Under a seeded
         schedule (set_schedule(..., seeded_noise=True)) with ``step_seeds`` they run: the tail plan ends with the seeded step on both
         ranks, and each generates the identical noise from the seeds without talking."""
-        if getattr(self, "cfg_role", None) is None or not self.do_cfg:
+        if self.cfg_role is None or not self.do_cfg:
             raise L.ImhError("denoise_cfg_split needs an engine whose conditioning was set with cfg_role = 0 / 1 and guidance > 1")
         if self.stochastic and not (self.seeded and step_seeds is not None):
             raise NotImplementedError("denoise_cfg_split does not run stochastic schedulers: both ranks would need identical noise banks "
@@ -673,7 +702,7 @@ class DenoiseEngine:
         Under a seeded schedule (set_schedule(..., seeded_noise=True)) ``step_seeds`` is required instead: one integer in [0, 2**64) per
         sample, with ``step_lanes`` (default 0 each; the sample indices where one seed serves the batch).  16 bytes per sample are copied,
         nothing is drawn; generator= / step_noise= are refused there, and step_seeds= anywhere else."""
-        if getattr(self, "cfg_role", None) is not None and self.do_cfg:
+        if self.cfg_role is not None and self.do_cfg:
             raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
         if self.inpaint and latents is not None:
             raise L.ImhError("an inpainting schedule starts from prepare_inpaint: denoise(None)")

@@ -202,10 +202,8 @@ def _cpu_engine(S=1, H=8, W=8):
 
         class config:
             in_channels = 4
-    e = DenoiseEngine.__new__(DenoiseEngine)
-    e.unet, e.device, e.dtype, e.st = _U(), torch.device("cpu"), torch.bfloat16, StepState()
-    e._plans, e._sched_key, e.plan, e.max_cached_plans = {}, None, None, 3
-    e.S, e.H, e.W, e.t_start, e.inpaint = S, H, W, 0, None
+    e = DenoiseEngine(_U(), "cpu")
+    e.st, e.S, e.H, e.W, e.max_cached_plans = StepState(), S, H, W, 3
     return e
 
 

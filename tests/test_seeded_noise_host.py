@@ -215,6 +215,7 @@ def test_plan_key_and_state_of_a_seeded_schedule():
     e.set_schedule(ea, 6, seeded_noise=True)
     k_seed = e._sched_key
     assert k_seed != k_bank and k_seed[:-1] == k_bank[:-1]
+    assert k_seed.seeded and not k_bank.seeded and k_seed == k_bank._replace(seeded=True)
     assert e.stochastic and e.seeded and e.st.noise_bank is None
     assert e.st.seed_rows.dtype == torch.int32 and tuple(e.st.seed_rows.shape) == (2, 4)
     assert tuple(e.st.coef6_tab.shape) == (6, 6)

@@ -119,7 +119,7 @@ def test_schedule_builds_the_table_and_keys_it():
     sch = hs.DDIMScheduler()
     e.set_schedule(sch, 30)
     k_plain = e._sched_key
-    assert e.ad_gate_tab is None and k_plain[11] is None
+    assert e.ad_gate_tab is None and k_plain[11] is None and k_plain.adapter is None
     e.adapter = _FakeAdapter()
     with pytest.raises(L.ImhError, match="set_adapter_image"):
         e.set_schedule(sch, 30)
@@ -135,6 +135,7 @@ def test_schedule_builds_the_table_and_keys_it():
     k_scale = e._sched_key
     assert len({k_plain, k_half, k_full, k_scale}) == 4                   # with / without, the factor and the scale are all in the key
     assert k_full[:11] == k_plain[:11] and k_full[12:] == k_plain[12:]    # ... and nothing else moved
+    assert k_full == k_plain._replace(adapter=k_full.adapter) and k_full.adapter[1] == 0.75 and k_scale.adapter == (k_full.adapter[0], 0.5)
     # denoising_end cuts the list first: the factor counts the steps that run (upstream truncates num_inference_steps before its loop)
     e.set_schedule(sch, 30, denoising_end=0.5, adapter_conditioning_factor=0.5)
     n = e.steps

@@ -13,7 +13,7 @@ import torch
 
 sys.path.insert(0, '.')
 import bench
-from imagharmony_amd.denoise import DenoiseEngine
+from imagharmony_amd.denoise import GENERAL_STEP, DenoiseEngine
 from imagharmony_amd.schedulers import EulerAncestralDiscreteScheduler
 
 DEV = torch.device("cuda:0")
@@ -53,7 +53,7 @@ mem = {}
 for name in CASES:
     one(name); one(name)
     st = e.st
-    mem[name] = {k: (0 if getattr(st, k, None) is None else getattr(st, k).numel() * getattr(st, k).element_size()) for k in e._GENERAL_STEP}
+    mem[name] = {k: (0 if getattr(st, k, None) is None else getattr(st, k).numel() * getattr(st, k).element_size()) for k in GENERAL_STEP}
 clk = bench.ClockSampler(period=0.5)
 host, total = {n: [] for n in CASES}, {n: [] for n in CASES}
 for _ in range(reps):
