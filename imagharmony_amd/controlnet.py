@@ -14,14 +14,12 @@ state-dict names) plus
 one or either inpainting mode: the branch reads the 4-channel latents whatever the UNet's ``in_channels``.  Not built: ``guess_mode``,
 ``global_pool_conditions``, class embeddings, ``MultiControlNetModel`` (NotImplementedError).
 """
-import math
-
 import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import _b, _w
-from .unet import Conv2d, DownBlock, Feat, MidBlock, StepState, TimestepEmbedding, UNet2DConditionModel, UNetConfig
+from .attention_processor import _b
+from .unet import Conv2d, DownBlock, Feat, MidBlock, StepState, TimestepEmbedding, UNetConfig, UNetEncoderModel, gn_sub
 
 COND_CHANNELS = (16, 32, 96, 256)       # diffusers conditioning_embedding_out_channels (every published SDXL ControlNet)
 
@@ -47,7 +45,10 @@ class ControlNetConditioningEmbedding(nn.Module):
         self.conv_out = Conv2d(channels[-1], c0, 3)
 
 
-class ControlNetModel(nn.Module):
+class ControlNetModel(UNetEncoderModel):
+    """the processor protocol, the packed / stacked weights, the step-invariant conditioning, the checkpoint loader and the encoder
+    walk are the base class's: the ones the UNet runs"""
+
     def __init__(self, cfg: UNetConfig = None, conditioning_embedding_out_channels=COND_CHANNELS, global_pool_conditions=False,
                  class_embed_type=None, num_class_embeds=None):
         super().__init__()
@@ -76,34 +77,11 @@ class ControlNetModel(nn.Module):
         self.controlnet_down_blocks = nn.ModuleList([Conv2d(c, c, 1) for c in skip_ch])
         self.controlnet_mid_block = Conv2d(boc[-1], boc[-1], 1)
         self.mid_block = MidBlock(boc[-1], cfg.transformer_layers_per_block[-1], cfg.attention_head_dim[-1], cfg)
-        off = 0
-        for r in self.resnets():
-            r.temb_offset = off
-            off += r.time_emb_proj.weight.shape[0]
-        self.temb_total = off
-
-    def resnets(self):
-        for blk in list(self.down_blocks) + [self.mid_block]:
-            for r in blk.resnets:
-                yield r
+        self._number_time_emb_proj()
 
     def zero_convs(self):
         """the convs upstream creates with zero_module: a fresh ControlNet adds nothing to the UNet"""
         return list(self.controlnet_down_blocks) + [self.controlnet_mid_block, self.controlnet_cond_embedding.conv_out]
-
-    # the processor protocol, the packed / stacked weights, the step-invariant conditioning and the checkpoint loader are the UNet's own
-    attn_processors = UNet2DConditionModel.attn_processors
-    set_attn_processor = UNet2DConditionModel.set_attn_processor
-    attn2_modules = UNet2DConditionModel.attn2_modules
-    init_random_ = UNet2DConditionModel.init_random_
-    from_safetensors = classmethod(UNet2DConditionModel.from_safetensors.__func__)
-    _temb_stack = UNet2DConditionModel._temb_stack
-    _temb_chain = UNet2DConditionModel._temb_chain
-    _emit_time_embedding = UNet2DConditionModel._emit_time_embedding
-    _emit_encoder = UNet2DConditionModel._emit_encoder
-    precompute_temb = UNet2DConditionModel.precompute_temb
-    prepare_conditioning = UNet2DConditionModel.prepare_conditioning
-    _pname = UNet2DConditionModel._pname
 
     @classmethod
     @torch.no_grad()
@@ -169,25 +147,18 @@ class ControlNetModel(nn.Module):
         if guess_mode:
             raise NotImplementedError("guess_mode is not built")
         cfg = self.config
-        B = 2 * S if cfg_dup else S
-        boc = cfg.block_out_channels
-        div = 1 << (len(boc) - 1)
-        if Hl % div or Wl % div:
-            raise L.ImhError(f"latent {Hl}x{Wl}: sides must be multiples of {div} (image sides multiples of {8 * div})")
-        if hint is None or hint.dim() != 4 or tuple(hint.shape[1:]) != (Hl, Wl, boc[0]) or hint.shape[0] not in (1, S) or not hint.is_contiguous():
-            raise L.ImhError(f"hint {None if hint is None else tuple(hint.shape)}: expected contiguous [1 | {S}, {Hl}, {Wl}, {boc[0]}] (prepare_hint)")
-        groups = cfg.norm_num_groups
+        B = self._latent_batch(S, Hl, Wl, cfg_dup)
+        c0 = cfg.block_out_channels[0]
+        if hint is None or hint.dim() != 4 or tuple(hint.shape[1:]) != (Hl, Wl, c0) or hint.shape[0] not in (1, S) or not hint.is_contiguous():
+            raise L.ImhError(f"hint {None if hint is None else tuple(hint.shape)}: expected contiguous [1 | {S}, {Hl}, {Wl}, {c0}] (prepare_hint)")
         ctx.tag = 81
         self._emit_time_embedding(ctx, st, B)
         ctx.tag = 82
-        x = ctx.new(B, Hl, Wl, boc[0])
-        ctx.ew(L.EW_CONV_IN, x, a=st.latents, w=_w(self.conv_in, ctx), bias=_b(self.conv_in, ctx),
-               tab=st.in_scale_tab, step=st.step if st.in_scale_tab is not None else None,
-               i=(S, Hl, Wl, boc[0], B, 0), f=(1.0, 0, 0, 0), descr="cn.conv_in", nbytes=2.0 * B * Hl * Wl * boc[0])
+        x = self._emit_conv_in(ctx, st, S, B, Hl, Wl, "cn.conv_in")
         # sample = conv_in(sample) + controlnet_cond_embedding(cond): the hint add leaves the GroupNorm partials a conv_in output needs
-        y, gs = ctx.control_add(x, hint, gn_sub=math.gcd(boc[0] // groups, 10), descr="cn.hint_add")
+        y = Feat.of(ctx.control_add(x, hint, gn_sub=gn_sub(c0, cfg.norm_num_groups), descr="cn.hint_add"))
         ctx.free(x)
-        h, feats = self._emit_encoder(ctx, st, Feat(y, gs), (83, 84, 85, 86), prefix="cn.")
+        h, feats = self._emit_encoder(ctx, st, y, (83, 84, 85, 86), prefix="cn.")
         # the zero convs: 1 x 1 convs are Linears over the pixels
         ctx.tag = 87
         down = []
@@ -209,18 +180,10 @@ class ControlNetModel(nn.Module):
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale=1.0, added_cond_kwargs=None,
                 guess_mode=False, return_dict=False, **kw):
         """-> (down_block_res_samples: nine NCHW tensors, mid_block_res_sample), each times conditioning_scale, as upstream"""
-        from .ctx import Ctx
         if guess_mode:
             raise NotImplementedError("guess_mode is not built")
-        dev = sample.device
-        dtype = self.conv_in.weight.dtype if self.conv_in.weight.dtype in (torch.bfloat16, torch.float16) \
-            else (sample.dtype if sample.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16)
-        ctx = Ctx(dev, dtype)
+        ctx, st = self._eager_state(sample, timestep, encoder_hidden_states, added_cond_kwargs)
         B, _, Hl, Wl = sample.shape
-        st = self.prepare_conditioning(ctx, encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"])
-        t = timestep if torch.is_tensor(timestep) else torch.tensor([float(timestep)])
-        st.t_value = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
-        st.latents = sample.to(torch.float32).contiguous()
         hint = self.prepare_hint(ctx, controlnet_cond, Hl, Wl)
         res = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, hint=hint)
         out = [(r.permute(0, 3, 1, 2).float() * float(conditioning_scale)).to(sample.dtype) for r in res.down + [res.mid]]

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import AttnProcessor2_0, CNAttnProcessor2_0, IPAttnProcessor2_0, _b, _vkey, _w
+from .attention_processor import AttnProcessor2_0, CNAttnProcessor2_0, IPAttnProcessor2_0, _b, _vkey, _w, fold_ln
 from .ctx import Ctx, GnSpec
 
 
@@ -39,32 +39,35 @@ FOLD_LAYERNORM = True
 # ff.out + residual) leaves (sum, M2) slot partials behind from its epilogue (csrc/imh_lnstats.h) and every consumer -- the
 # [Q|K] + V^T pair (norm1), the fused cross-attention's to_q (norm2), ff.net.0 (norm3) -- merges them in its prologue:
 # Welford / Chan all the way, like torch.nn.LayerNorm (which the reference runs ahead of attn.to_q,
-# ip_adapter/attention_processor.py:396).  The in-loop E[x^2] - mean^2 form of rounds 2-3 no longer exists in the library;
-# False here (IMH_LN_STATS=0, A/B) makes every consumer take its statistics from a stand-alone row-statistics launch instead.
-LN_STATS_HANDOVER = os.environ.get("IMH_LN_STATS", "1") != "0"
+# ip_adapter/attention_processor.py:396).  The in-loop E[x^2] - mean^2 form of rounds 2-3 no longer exists in the library; rows no
+# epilogue covers get their statistics from a stand-alone row-statistics launch (Ctx.gemm / Ctx.gemm_dual supply it).
 # GroupNorm statistics the same way: the conv / GEMM that writes a GroupNorm input (conv1 -> norm2, conv2 / proj_out / the
 # stride-2 downsampler -> the next block's norm1 / Transformer2DModel.norm / conv_norm_out, ALSO through the up path's channel
 # concats: the two producers' partials are merged) leaves (sum, M2) partials per 10-channel sub-run behind from its epilogue
-# (imh_gemm_args.gn_out); a tiny launch turns them into the per-sample (scale, shift) table of the GroupNorm.  Tensors no epilogue
+# (imh_gemm_args.gn_out), from which the per-sample (scale, shift) table of the GroupNorm is built (below).  Tensors no epilogue
 # covers (conv_in, split-K / ring variants) get theirs from one statistics pass.  False = every tensor takes the pass (A/B;
 # IMH_GN_STATS=0).
 GN_STATS_HANDOVER = os.environ.get("IMH_GN_STATS", "1") != "0"
-UPSAMPLE_PHASE = os.environ.get("IMH_UPSAMPLE_PHASE", "1") != "0"     # Upsample2D's conv in the phase form (Ctx.conv3x3 up=2) where it qualifies
 # ... and the GroupNorm itself -- diffusers ResnetBlock2D: norm -> SiLU -> conv -- is applied INSIDE the consuming
 # conv3x3's halo staging wherever that conv runs on the LDS-halo kernel (the 128 x 128 and 64 x 64 levels): no normalised tensor in
 # memory, and the up path's torch.cat([hidden, skip], 1) is read from its two producers by the same kernel (and by conv_shortcut's
-# GEMM): no concat pass either.  False = table + apply pass + materialised concat everywhere (A/B; IMH_GN_FUSE=0).
+# GEMM): no concat pass either.  False = apply pass + materialised concat everywhere (A/B; IMH_GN_FUSE=0).
 GN_FUSE = os.environ.get("IMH_GN_FUSE", "1") != "0"
-# ... and (round 5) the table step has no launch of its own either: the consumer -- the fused conv, or the apply pass in front of a
-# Linear -- builds its sample's (scale, shift) table in its prologue from the producers' partials (imh_gemm_args.gn_part,
-# IMH_GN_TABLE_APPLY; csrc/imh_gntable.h: the same routine as the table launch, bit-identical).  False = one table launch per
-# GroupNorm (A/B; IMH_GN_TABLE_FOLD=0).
-GN_TABLE_FOLD = os.environ.get("IMH_GN_TABLE_FOLD", "1") != "0"
+# The table step has no launch of its own in either form: the consumer -- the fused conv, or the apply pass in front of a Linear --
+# builds its sample's (scale, shift) table in its prologue from the producers' partials (imh_gemm_args.gn_part, IMH_GN_TABLE_APPLY;
+# csrc/imh_gntable.h: the same routine as Ctx.gn_table's launch, bit-identical).
 
 
 # a ControlNet carries ONE CNAttnProcessor2_0 object on all its layers (ip_adapter/ip_adapter.py:126-133): on attn1 it is plain
 # self-attention, which this processor records (no parameters, no state); on attn2 it is IPAttnProcessor2_0(skip=True) by its own emit
 _SELF_ATTN = AttnProcessor2_0()
+
+
+def gn_sub(C_, groups):
+    """channels per sub-run of the GroupNorm partials of a C-channel tensor no conv / GEMM epilogue covers: sub-runs of
+    gcd(C / groups, 10) channels tile the groups of every reader, alone or through a concat with a tensor of a multiple of C channels
+    (SDXL: 10, like the producers' epilogues)"""
+    return math.gcd(C_ // groups, 10)
 
 
 class Feat:
@@ -74,13 +77,17 @@ class Feat:
     def __init__(self, t, gs=None):
         self.t, self.gs = t, gs
 
+    @classmethod
+    def of(cls, r):
+        """what Ctx.conv3x3(gn_groups=), Ctx.gemm(gn_out=) and Ctx.control_add(gn_sub=) return -- (tensor, GnStats or None) where the
+        partials were asked for, else the tensor alone -- as a Feat"""
+        return cls(*r) if isinstance(r, tuple) else cls(r)
+
     def stats(self, ctx, groups):
-        """the tensor's GroupNorm partials: the producer's, else one statistics pass (kept: skip tensors are normalised twice).
-        Sub-runs of gcd(C / groups, 10) channels tile the groups of every reader, alone or through a concat with a tensor of a
-        multiple of C channels (SDXL: 10, like the producers' epilogues)"""
+        """the tensor's GroupNorm partials: the producer's, else one statistics pass (kept: skip tensors are normalised twice)"""
         if self.gs is None:
             B, C_ = self.t.shape[0], self.t.shape[-1]
-            self.gs = ctx.gn_stats(self.t.view(B, -1, C_), sub=math.gcd(C_ // groups, 10))
+            self.gs = ctx.gn_stats(self.t.view(B, -1, C_), sub=gn_sub(C_, groups))
         return self.gs
 
     def free(self, ctx):
@@ -243,24 +250,19 @@ class GEGLU(nn.Module):
             self._imh_packed = c
         return c[1], c[2]
 
-
-def _geglu_packed_ln(self, ctx, norm):
-    """GEGLU projection with LayerNorm folded in (see attention_processor.fold_ln), rows interleaved in quads (geglu_interleave)."""
-    from .attention_processor import fold_ln
-    key = (_vkey(self.proj.weight, self.proj.bias, norm.weight, norm.bias), ctx.dtype, str(ctx.device))
-    c = getattr(self, "_imh_packed_ln", None)
-    if c is None or c[0] != key:
-        wg, s, cc = fold_ln(self.proj.weight, norm, ctx)
-        il = geglu_interleave
-        # the Linear's bias rides in the fold's constant term, c = W beta + b (fp32): one epilogue operand (and twenty live
-        # registers per lane of the 256 x 160 kernel's epilogue) less than a separate bias vector
-        b = self.proj.bias.detach().to(device=ctx.device, dtype=torch.float32)
-        c = (key, il(wg), None, il(s), il(cc + b))
-        self._imh_packed_ln = c
-    return c[1], c[2], c[3], c[4]
-
-
-GEGLU.packed_ln = _geglu_packed_ln
+    def packed_ln(self, ctx, norm):
+        """GEGLU projection with LayerNorm folded in (see attention_processor.fold_ln), rows interleaved in quads (geglu_interleave)."""
+        key = (_vkey(self.proj.weight, self.proj.bias, norm.weight, norm.bias), ctx.dtype, str(ctx.device))
+        c = getattr(self, "_imh_packed_ln", None)
+        if c is None or c[0] != key:
+            wg, s, cc = fold_ln(self.proj.weight, norm, ctx)
+            il = geglu_interleave
+            # the Linear's bias rides in the fold's constant term, c = W beta + b (fp32): one epilogue operand (and twenty live
+            # registers per lane of the 256 x 160 kernel's epilogue) less than a separate bias vector
+            b = self.proj.bias.detach().to(device=ctx.device, dtype=torch.float32)
+            c = (key, il(wg), None, il(s), il(cc + b))
+            self._imh_packed_ln = c
+        return c[1], c[2], c[3], c[4]
 
 
 class FeedForward(nn.Module):
@@ -269,19 +271,60 @@ class FeedForward(nn.Module):
         self.net = nn.ModuleList([GEGLU(dim, dim * 4), Dropout(), Linear(dim * 4, dim)])
 
     def emit(self, ctx, x, residual, ln=None, ln_stats=None, want_stats=False):
+        """-> (out, the row statistics of out where want_stats, else None)"""
         if ln is None:
             w1, b1 = self.net[0].packed(ctx)
             g = ctx.gemm(x, w1, bias=b1, flags=L.GF_GEGLU, descr="ff.geglu")
         else:       # x un-normalised, LayerNorm `ln` folded into the (interleaved) GEGLU projection
             w1, b1, s1, c1 = self.net[0].packed_ln(ctx, ln)
             g = ctx.gemm(x, w1, bias=b1, flags=L.GF_GEGLU | L.GF_LN_ROW, ln=(s1, c1, ln.eps, ln_stats), descr="ff.geglu")
-        out = ctx.gemm(g, _w(self.net[2], ctx), bias=_b(self.net[2], ctx), residual=residual, descr="ff.out", stats_out=want_stats)
+        out = _with_stats(ctx.gemm(g, _w(self.net[2], ctx), bias=_b(self.net[2], ctx), residual=residual, descr="ff.out", stats_out=want_stats))
         ctx.free(g)
         return out
 
 
+def _with_stats(r):
+    """what Ctx.gemm(stats_out=) and a processor's emit(want_stats=) return -- (rows, their LayerNorm statistics) where those were asked
+    for, else the rows alone -- as (rows, statistics or None)"""
+    return r if isinstance(r, tuple) else (r, None)
+
+
+def _free_rows(ctx, h, stats):
+    ctx.free(h)
+    if stats is not None:
+        ctx.free(stats[0])
+
+
 def _ln(ctx, norm, x, descr):
     return ctx.layernorm(x, _w(norm, ctx), _b(norm, ctx), norm.eps, descr=descr)
+
+
+# ------------------------------------------------------------------ the GroupNorm front end
+def _gn_spec(ctx, norm, groups, *srcs):
+    """GroupNorm `norm` over the Feat srcs[0], or over the channel concat of two, as its consumer takes it: the consumer builds its
+    sample's (scale, shift) table itself from the producers' partials (Feat.stats: one statistics pass where a producer left none)"""
+    return GnSpec([f.stats(ctx, groups) for f in srcs], _w(norm, ctx), _b(norm, ctx), groups, norm.eps)
+
+
+def _gn_pass(ctx, spec, x, silu, descr):
+    """the GroupNorm (+ SiLU) of NHWC x as a pass, for the consumers that cannot take it themselves: the Linears, the convs that do not run
+    on the LDS-halo kernel"""
+    return ctx.gn_table_apply(x.view(x.shape[0], -1, x.shape[-1]), spec, silu, descr=descr).view(x.shape)
+
+
+def _gn_conv(ctx, spec, conv, x, x2, descr, norm_descr, **epi):
+    """conv(silu(GroupNorm(cat[x, x2]))), diffusers ResnetBlock2D's norm -> nonlinearity -> conv, x2 = None: of x alone.  Where the conv
+    runs on the LDS-halo kernel (GN_FUSE, Ctx.conv_fuses_gn) the norm and the concat happen inside its halo staging, else as passes
+    in front of it.  epi: the conv's epilogue arguments.  -> (Feat of the output, the concat where it was materialised, else None)"""
+    M, (Cout, Cin) = x.numel() // x.shape[-1], conv.weight.shape[:2]
+    kw = dict(bias=_b(conv, ctx), descr=descr, **epi)
+    if GN_FUSE and ctx.conv_fuses_gn(M, Cout, 9 * Cin):
+        return Feat.of(ctx.conv3x3(x, conv.packed(ctx), gn=(spec, True), x2=x2, **kw)), None
+    xc = ctx.concat(x, x2, descr="skip.concat") if x2 is not None else None
+    n = _gn_pass(ctx, spec, x if xc is None else xc, True, norm_descr)
+    out = Feat.of(ctx.conv3x3(n, conv.packed(ctx), **kw))
+    ctx.free(n)
+    return out, xc
 
 
 class BasicTransformerBlock(nn.Module):
@@ -301,8 +344,8 @@ class BasicTransformerBlock(nn.Module):
             and isinstance(self.attn2.processor, (IPAttnProcessor2_0, CNAttnProcessor2_0)) and L_ % 64 == 0
 
     def emit(self, ctx, h, B, L_, kv, st, stats=None, want_stats=False):
-        """h: the residual stream [B*L, C] (consumed).  stats = row statistics of h from the GEMM that wrote it (or None);
-        want_stats: return (h3, statistics of h3) for the next block's norm1."""
+        """h: the residual stream [B*L, C]; stats: the row statistics of h from the GEMM that wrote it, or None (both consumed)
+        -> (h3, the statistics of h3 for the next block's norm1 where want_stats and this block runs folded, else None)."""
         p1, p2 = self.attn1.processor, self.attn2.processor
         if isinstance(p1, CNAttnProcessor2_0):
             p1 = _SELF_ATTN
@@ -311,28 +354,16 @@ class BasicTransformerBlock(nn.Module):
                              "imagharmony_amd.attention_processor processors")
         ip2 = isinstance(p2, IPAttnProcessor2_0)
         if self.fused(L_):
-            # LayerNorm never materialises: every consumer GEMM reads the residual stream itself, and (LN_STATS_HANDOVER)
-            # takes the rows' statistics from the epilogue of the GEMM that wrote it
-            ho = LN_STATS_HANDOVER
-            if not ho:
-                stats = None
-            r = p1.emit(ctx, self.attn1, h, B, L_, residual=h, ln=self.norm1, ln_stats=stats, want_stats=ho)
-            h1, s1 = r if ho else (r, None)
-            ctx.free(h)
-            if stats is not None:
-                ctx.free(stats[0])
-            r = p2.emit(ctx, self.attn2, h1, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab, ln=self.norm2,
-                        ln_stats=s1, want_stats=ho)
-            h2, s2 = r if ho else (r, None)
-            ctx.free(h1)
-            if s1 is not None:
-                ctx.free(s1[0])
-            r = self.ff.emit(ctx, h2, residual=h2, ln=self.norm3, ln_stats=s2, want_stats=ho and want_stats)
-            h3, s3 = r if (ho and want_stats) else (r, None)
-            ctx.free(h2)
-            if s2 is not None:
-                ctx.free(s2[0])
-            return (h3, s3) if want_stats else h3
+            # LayerNorm never materialises: every consumer GEMM reads the residual stream itself, and takes the rows' statistics
+            # from the epilogue of the GEMM that wrote it
+            h1, s1 = p1.emit(ctx, self.attn1, h, B, L_, residual=h, ln=self.norm1, ln_stats=stats, want_stats=True)
+            _free_rows(ctx, h, stats)
+            h2, s2 = p2.emit(ctx, self.attn2, h1, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab, ln=self.norm2,
+                             ln_stats=s1, want_stats=True)
+            _free_rows(ctx, h1, s1)
+            h3, s3 = self.ff.emit(ctx, h2, residual=h2, ln=self.norm3, ln_stats=s2, want_stats=want_stats)
+            _free_rows(ctx, h2, s2)
+            return h3, s3
         if stats is not None:
             ctx.free(stats[0])
         n = _ln(ctx, self.norm1, h, "norm1")
@@ -343,9 +374,9 @@ class BasicTransformerBlock(nn.Module):
             if ip2 else p2.emit(ctx, self.attn2, n, B, L_, residual=h1, kv=kv)
         ctx.free(n); ctx.free(h1)
         n = _ln(ctx, self.norm3, h2, "norm3")
-        h3 = self.ff.emit(ctx, n, residual=h2)
+        h3, _ = self.ff.emit(ctx, n, residual=h2)
         ctx.free(n); ctx.free(h2)
-        return (h3, None) if want_stats else h3
+        return h3, None
 
 
 class Transformer2DModel(nn.Module):
@@ -365,28 +396,21 @@ class Transformer2DModel(nn.Module):
         B, Hh, Ww, C_ = x.shape
         L_ = Hh * Ww
         x2 = x.view(B * L_, C_)
-        if GN_TABLE_FOLD:
-            n = ctx.gn_table_apply(x.view(B, L_, C_), GnSpec(f.stats(ctx, self.groups), _w(self.norm, ctx), _b(self.norm, ctx), self.groups, self.norm.eps),
-                                   False, descr="t2d.norm")
-        else:
-            tab = ctx.gn_table(f.stats(ctx, self.groups), _w(self.norm, ctx), _b(self.norm, ctx), self.groups, self.norm.eps, L_, descr="t2d.norm.table")
-            n = ctx.gn_apply(x.view(B, L_, C_), tab, False, descr="t2d.norm")
-            ctx.free(tab)
+        n = _gn_pass(ctx, _gn_spec(ctx, self.norm, self.groups, f), x, False, "t2d.norm")
         blocks = list(self.transformer_blocks)
-        ho = LN_STATS_HANDOVER and bool(blocks) and blocks[0].fused(L_)
-        r = ctx.gemm(n.view(B * L_, C_), _w(self.proj_in, ctx), bias=_b(self.proj_in, ctx), descr="t2d.proj_in", stats_out=ho)
-        h, stats = r if ho else (r, None)
+        # the rows' LayerNorm statistics go from each writing GEMM to the next folded block's norm1
+        ho = bool(blocks) and blocks[0].fused(L_)
+        h, stats = _with_stats(ctx.gemm(n.view(B * L_, C_), _w(self.proj_in, ctx), bias=_b(self.proj_in, ctx), descr="t2d.proj_in", stats_out=ho))
         ctx.free(n)
         for i, (blk, kv) in enumerate(zip(blocks, kvs)):
             more = ho and i + 1 < len(blocks) and blocks[i + 1].fused(L_)
-            r = blk.emit(ctx, h, B, L_, kv, st, stats=stats, want_stats=more)
-            h, stats = r if more else (r, None)
-        r = ctx.gemm(h, _w(self.proj_out, ctx), bias=_b(self.proj_out, ctx), residual=x2, descr="t2d.proj_out",
-                     gn_out=L_ if GN_STATS_HANDOVER else None)
-        out, gn = r if GN_STATS_HANDOVER else (r, None)
+            h, stats = blk.emit(ctx, h, B, L_, kv, st, stats=stats, want_stats=more)
+        out = Feat.of(ctx.gemm(h, _w(self.proj_out, ctx), bias=_b(self.proj_out, ctx), residual=x2, descr="t2d.proj_out",
+                               gn_out=L_ if GN_STATS_HANDOVER else None))
         ctx.free(h)
         f.free(ctx)
-        return Feat(out.view(B, Hh, Ww, C_), gn)
+        out.t = out.t.view(B, Hh, Ww, C_)
+        return out
 
 
 class ResnetBlock2D(nn.Module):
@@ -413,29 +437,12 @@ class ResnetBlock2D(nn.Module):
         sk = skip.t if skip is not None else None
         Cin = C1 + (sk.shape[-1] if sk is not None else 0)
         Cout = self.conv1.weight.shape[0]
-        want = 1 if GN_STATS_HANDOVER else 0
-        srcs = [f.stats(ctx, self.groups)] + ([skip.stats(ctx, self.groups)] if skip is not None else [])
+        want = int(GN_STATS_HANDOVER)   # the convs leave the partials of their output behind for the next norm
+        spec1 = _gn_spec(ctx, self.norm1, self.groups, f, *([skip] if skip is not None else []))
         ra = st.temb_all[:, self.temb_offset:self.temb_offset + Cout]
-        fuse1 = GN_FUSE and ctx.conv_fuses_gn(M, Cout, 9 * Cin)
-        spec1 = GnSpec(srcs, _w(self.norm1, ctx), _b(self.norm1, ctx), self.groups, self.norm1.eps)
-        # the table: built by the consumer itself (fold), or by one small launch
-        tab1 = spec1 if GN_TABLE_FOLD else ctx.gn_table(srcs, _w(self.norm1, ctx), _b(self.norm1, ctx), self.groups, self.norm1.eps, HW, descr="res.norm1.table")
-        xc = None                       # the materialised concat, where something still needs it
-        if fuse1:
-            h = ctx.conv3x3(x, self.conv1.packed(ctx), bias=_b(self.conv1, ctx), rowadd=ra, ldra=st.temb_all.stride(0),
-                            descr="res.conv1", gn_groups=want, gn=(tab1, True), x2=sk)
-        else:
-            xc = ctx.concat(x, sk, descr="skip.concat") if sk is not None else x
-            n = (ctx.gn_table_apply(xc.view(B, HW, Cin), tab1, True, descr="res.norm1") if GN_TABLE_FOLD
-                 else ctx.gn_apply(xc.view(B, HW, Cin), tab1, True, descr="res.norm1")).view(B, Hh, Ww, Cin)
-            h = ctx.conv3x3(n, self.conv1.packed(ctx), bias=_b(self.conv1, ctx), rowadd=ra, ldra=st.temb_all.stride(0),
-                            descr="res.conv1", gn_groups=want)
-            ctx.free(n)
-        if not GN_TABLE_FOLD:
-            ctx.free(tab1)
-        hf = Feat(*h) if want else Feat(h)
-        tab2 = (GnSpec(hf.stats(ctx, self.groups), _w(self.norm2, ctx), _b(self.norm2, ctx), self.groups, self.norm2.eps) if GN_TABLE_FOLD
-                else ctx.gn_table(hf.stats(ctx, self.groups), _w(self.norm2, ctx), _b(self.norm2, ctx), self.groups, self.norm2.eps, HW, descr="res.norm2.table"))
+        # xc: the materialised concat, where something still needs it
+        hf, xc = _gn_conv(ctx, spec1, self.conv1, x, sk, "res.conv1", "res.norm1", rowadd=ra, ldra=st.temb_all.stride(0), gn_groups=want)
+        spec2 = _gn_spec(ctx, self.norm2, self.groups, hf)
         if self.conv_shortcut is not None:
             wsc, bsc = self.conv_shortcut.packed(ctx), _b(self.conv_shortcut, ctx)
             if sk is not None and xc is None:
@@ -448,26 +455,17 @@ class ResnetBlock2D(nn.Module):
             if sk is not None and xc is None:
                 xc = ctx.concat(x, sk, descr="skip.concat")
             sc = (xc if xc is not None else x).view(M, Cin)
-        if GN_FUSE and ctx.conv_fuses_gn(M, Cout, 9 * Cout):
-            out = ctx.conv3x3(hf.t, self.conv2.packed(ctx), bias=_b(self.conv2, ctx), residual=sc, descr="res.conv2", gn_groups=want,
-                              gn=(tab2, True))
-        else:
-            n = (ctx.gn_table_apply(hf.t.view(B, HW, Cout), tab2, True, descr="res.norm2") if GN_TABLE_FOLD
-                 else ctx.gn_apply(hf.t.view(B, HW, Cout), tab2, True, descr="res.norm2")).view(B, Hh, Ww, Cout)
-            out = ctx.conv3x3(n, self.conv2.packed(ctx), bias=_b(self.conv2, ctx), residual=sc, descr="res.conv2", gn_groups=want)
-            ctx.free(n)
-        if not GN_TABLE_FOLD:
-            ctx.free(tab2)
+        out, _ = _gn_conv(ctx, spec2, self.conv2, hf.t, None, "res.conv2", "res.norm2", residual=sc, gn_groups=want)
         hf.free(ctx)
         if self.conv_shortcut is not None:
             ctx.free(sc)
-        if xc is not None and sk is not None:
+        if xc is not None:
             ctx.free(xc)
         if not keep_input:
             f.free(ctx)
             if skip is not None:
                 skip.free(ctx)
-        return Feat(*out) if want else Feat(out)
+        return out
 
 
 class Downsample2D(nn.Module):
@@ -552,96 +550,56 @@ class StepState:
         self.t_value = None        # fp32 [B] explicit timestep values (eager forward)
 
 
-class UNet2DConditionModel(nn.Module):
-    def __init__(self, cfg: UNetConfig = None):
-        super().__init__()
-        cfg = cfg or UNetConfig()
-        self.config = cfg
-        boc = cfg.block_out_channels
-        nb = len(boc)
-        if cfg.in_channels not in (4, 9):
-            raise ValueError(f"in_channels must be 4 (SDXL base) or 9 (SDXL inpainting: latents, mask, masked-image latents), got {cfg.in_channels}")
-        self.conv_in = Conv2d(cfg.in_channels, boc[0], 3)
-        self.time_embedding = TimestepEmbedding(boc[0], cfg.time_embed_dim)
-        self.add_embedding = TimestepEmbedding(cfg.projection_class_embeddings_input_dim, cfg.time_embed_dim)
-        self.down_blocks = nn.ModuleList([])
-        self.up_blocks = nn.ModuleList([])     # created before mid_block: fixes the attn_processors order
-        out = boc[0]
-        for i in range(nb):
-            cin, out = out, boc[i]
-            n_tf = 0 if i == 0 else cfg.transformer_layers_per_block[i]
-            self.down_blocks.append(DownBlock(cin, out, cfg.layers_per_block, n_tf, cfg.attention_head_dim[i], cfg,
-                                              add_down=(i != nb - 1)))
-        self.mid_block = MidBlock(boc[-1], cfg.transformer_layers_per_block[-1], cfg.attention_head_dim[-1], cfg)
-        rev, rev_tf = list(reversed(boc)), list(reversed(cfg.transformer_layers_per_block))
-        rev_heads = list(reversed(cfg.attention_head_dim))
-        out = rev[0]
-        for i in range(nb):
-            prev, out = out, rev[i]
-            cin = rev[min(i + 1, nb - 1)]
-            n_tf = 0 if i == nb - 1 else rev_tf[i]
-            self.up_blocks.append(UpBlock(cin, out, prev, cfg.layers_per_block + 1, n_tf, rev_heads[i], cfg,
-                                          add_up=(i != nb - 1)))
-        self.conv_norm_out = Norm(boc[0], cfg.norm_eps)
-        self.conv_out = Conv2d(boc[0], cfg.out_channels, 3)
-        # stacked time_emb_proj bookkeeping
+class UNetEncoderModel(nn.Module):
+    """What UNet2DConditionModel and controlnet.ControlNetModel have in common: a subclass creates conv_in, time_embedding,
+    add_embedding, down_blocks and mid_block under their diffusers names (the order of creation is the order of the state dict and of
+    attn_processors) and numbers its ResNets (_number_time_emb_proj); this class holds the processor protocol, the packed / stacked
+    weights, the checkpoint loader, the step-invariant conditioning, the time-embedding chain, conv_in's launch, the walk over the
+    down path and the mid block, and the set-up of the eager forwards."""
+
+    def resnets(self):
+        for blk in list(self.down_blocks) + [self.mid_block]:
+            for r in blk.resnets:
+                yield r
+
+    def _number_time_emb_proj(self):
+        """the column of every ResNet inside the stacked time_emb_proj output"""
         off = 0
         for r in self.resnets():
             r.temb_offset = off
             off += r.time_emb_proj.weight.shape[0]
         self.temb_total = off
 
-    # ---- iteration helpers ----
-    def resnets(self):
-        for blk in list(self.down_blocks) + [self.mid_block] + list(self.up_blocks):
-            for r in blk.resnets:
-                yield r
-
     # ---- processor protocol (ip_adapter/ip_adapter.py:102,125) ----
+    def _attentions(self):
+        """[(module name, Attention)] in module order (a list: set_processor changes the tree under the walk)"""
+        return [(name, mod) for name, mod in self.named_modules() if hasattr(mod, "set_processor")]
+
     @property
     def attn_processors(self) -> Dict[str, object]:
-        procs = {}
-
-        def rec(name, mod):
-            if hasattr(mod, "get_processor"):
-                procs[f"{name}.processor"] = mod.get_processor()
-            for sub, child in mod.named_children():
-                rec(f"{name}.{sub}", child)
-
-        for name, child in self.named_children():
-            rec(name, child)
-        return procs
+        return {f"{name}.processor": mod.get_processor() for name, mod in self._attentions()}
 
     def set_attn_processor(self, processor):
-        count = len(self.attn_processors)
-        if isinstance(processor, dict) and len(processor) != count:
+        attns = self._attentions()
+        if isinstance(processor, dict) and len(processor) != len(attns):
             raise ValueError(f"A dict of processors was passed, but the number of processors {len(processor)} "
-                             f"does not match the number of attention layers: {count}.")
-        if isinstance(processor, dict):
-            processor = dict(processor)
-
-        def rec(name, mod):
-            if hasattr(mod, "set_processor"):
-                mod.set_processor(processor if not isinstance(processor, dict) else processor.pop(f"{name}.processor"))
-            for sub, child in mod.named_children():
-                rec(f"{name}.{sub}", child)
-
-        for name, child in self.named_children():
-            rec(name, child)
+                             f"does not match the number of attention layers: {len(attns)}.")
+        for name, mod in attns:
+            mod.set_processor(processor[f"{name}.processor"] if isinstance(processor, dict) else processor)
 
     def attn2_modules(self):
         """[(processor name, Attention)] for the cross-attention layers, in attn_processors order."""
-        out = []
+        return [(f"{name}.processor", mod) for name, mod in self._attentions() if name.endswith("attn2")]
 
-        def rec(name, mod):
-            if isinstance(mod, Attention) and name.endswith("attn2"):
-                out.append((f"{name}.processor", mod))
-            for sub, child in mod.named_children():
-                rec(f"{name}.{sub}", child)
+    def _pname(self, attn2):
+        names = getattr(self, "_imh_pnames", None)
+        if names is None or id(attn2) not in names:      # (a deepcopy carries stale ids)
+            names = self._imh_pnames = {id(mod): name for name, mod in self.attn2_modules()}
+        return names[id(attn2)]
 
-        for name, child in self.named_children():
-            rec(name, child)
-        return out
+    def _kv_of(self, st, t2d):
+        """the K / V caches of a Transformer2DModel's cross-attention layers, in block order"""
+        return [st.kv[self._pname(blk.attn2)] for blk in t2d.transformer_blocks]
 
     # ---- random init directly on the device (synthetic-weight benchmarks) ----
     @torch.no_grad()
@@ -762,7 +720,28 @@ class UNet2DConditionModel(nn.Module):
             st.temb_all = self._temb_chain(ctx, tsin, st.aug_emb)
             ctx.free(tsin)
 
-    # ---- the encoder (down path + mid block), shared with controlnet.ControlNetModel ----
+    def _latent_batch(self, S, Hl, Wl, cfg_dup):
+        """the batch of a forward over S latents of Hl x Wl (2S when cfg_dup: the CFG halves share the latent, custom_pipelines.py:332);
+        refuses sides the down path cannot halve"""
+        div = 1 << (len(self.config.block_out_channels) - 1)
+        if Hl % div or Wl % div:
+            # diffusers interpolates the up path to the skip's size in that case (forward_upsample_size); the
+            # fused nearest-x2 upsampling here does not, so refuse instead of producing misaligned skips
+            raise L.ImhError(f"latent {Hl}x{Wl}: sides must be multiples of {div} (image sides multiples of {8 * div})")
+        return 2 * S if cfg_dup else S
+
+    def _emit_conv_in(self, ctx, st, S, B, Hl, Wl, descr, extra=None):
+        """conv_in (+ CFG duplication + scale_model_input) over st.latents, fp32 NCHW [S, 4, Hl, Wl] -> NHWC [B, Hl, Wl, C0] in the compute
+        dtype.  extra: fp32 [S, 5, Hl, Wl], channels 4-8 of a 9-channel conv_in"""
+        c0 = self.config.block_out_channels[0]
+        x = ctx.new(B, Hl, Wl, c0)
+        ctx.ew(L.EW_CONV_IN, x, a=st.latents, w=_w(self.conv_in, ctx), bias=_b(self.conv_in, ctx),
+               tab=st.in_scale_tab, step=st.step if st.in_scale_tab is not None else None,
+               i=(S, Hl, Wl, c0, B, 9 if extra is not None else 0), f=(1.0, 0, 0, 0), descr=descr, x2=extra,
+               nbytes=2.0 * B * Hl * Wl * c0)
+        return x
+
+    # ---- the encoder (down path + mid block) ----
     def _emit_encoder(self, ctx, st, h, tags, tag_step=0, prefix="", adapter=None):
         """h: the Feat after conv_in -> (the mid block's output, [h and every down-path output in skip order]).
         tags = (down ResNets / downsamplers, down transformers, mid ResNets, mid transformer); the first two advance by tag_step per
@@ -776,8 +755,6 @@ class UNet2DConditionModel(nn.Module):
         list is what it is without the argument (the ControlNet's walk never passes one)."""
         t_res, t_attn, t_mid_res, t_mid_attn = tags
         feats = [h]
-        ho = GN_STATS_HANDOVER
-        kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
         nb = len(self.down_blocks)
         if adapter is not None and (nb != 3 or self.down_blocks[0].has_attn or not (self.down_blocks[1].has_attn and self.down_blocks[2].has_attn)):
             raise NotImplementedError("the adapter's injection points are those of the SDXL layout: DownBlock2D, CrossAttnDownBlock2D x 2, mid block")
@@ -789,9 +766,8 @@ class UNet2DConditionModel(nn.Module):
             tag, ctx.tag = ctx.tag, 33
             # the partials of the sum stand in for the ones the superseded tensor's writer left (the ControlNet injections' gn_sub rule);
             # a tensor that had none keeps getting them from its readers' statistics pass: the step grows by these four launches exactly
-            sub = math.gcd(f.t.shape[-1] // self.config.norm_num_groups, 10) if f.gs is not None else None
-            y = ctx.control_add(f.t, r, scale=adapter.scale, tab=adapter.tab, step=adapter.step, gn_sub=sub, descr=f"adapter.{k}")
-            y = Feat(*y) if sub is not None else Feat(y)
+            sub = gn_sub(f.t.shape[-1], self.config.norm_num_groups) if f.gs is not None else None
+            y = Feat.of(ctx.control_add(f.t, r, scale=adapter.scale, tab=adapter.tab, step=adapter.step, gn_sub=sub, descr=f"adapter.{k}"))
             f.free(ctx)
             ctx.tag = tag
             return y
@@ -802,15 +778,14 @@ class UNet2DConditionModel(nn.Module):
                 h = r.emit(ctx, h, st, keep_input=True)       # inputs are skip tensors: keep
                 if blk.has_attn:
                     ctx.tag = t_attn + bi * tag_step
-                    h = blk.attentions[i].emit(ctx, h, kv_of(blk.attentions[i]), st)
+                    h = blk.attentions[i].emit(ctx, h, self._kv_of(st, blk.attentions[i]), st)
                     if adapter is not None and i == len(blk.resnets) - 1:
                         h = inject(h, bi)
                 feats.append(h)
             if blk.downsamplers is not None:
                 ctx.tag = t_res + bi * tag_step
                 d = blk.downsamplers[0].conv
-                r_ = ctx.conv3x3(h.t, d.packed(ctx), bias=_b(d, ctx), stride=2, descr=prefix + "downsample", gn_groups=1 if ho else 0)
-                h = Feat(*r_) if ho else Feat(r_)
+                h = Feat.of(ctx.conv3x3(h.t, d.packed(ctx), bias=_b(d, ctx), stride=2, descr=prefix + "downsample", gn_groups=int(GN_STATS_HANDOVER)))
                 if adapter is not None and bi == 0:
                     h = inject(h, 0)
                 feats.append(h)
@@ -818,12 +793,64 @@ class UNet2DConditionModel(nn.Module):
         mb = self.mid_block
         h = mb.resnets[0].emit(ctx, h, st, keep_input=True)
         ctx.tag = t_mid_attn
-        h = mb.attentions[0].emit(ctx, h, kv_of(mb.attentions[0]), st)
+        h = mb.attentions[0].emit(ctx, h, self._kv_of(st, mb.attentions[0]), st)
         ctx.tag = t_mid_res
         h = mb.resnets[1].emit(ctx, h, st)
         if adapter is not None and tuple(adapter.feats[3].shape[1:]) == tuple(h.t.shape[1:]):
             h = inject(h, 3)
         return h, feats
+
+    # ---- what the eager forwards (the diffusers signatures) start from ----
+    def _eager_state(self, sample, timestep, encoder_hidden_states, added_cond_kwargs):
+        """-> (an eager Ctx in the weights' 16-bit dtype, else the sample's, else bf16; the StepState of this one call: conditioning
+        prepared, the timestep as explicit values, the first four channels of sample as the latents)"""
+        dtype = next((d for d in (self.conv_in.weight.dtype, sample.dtype) if d in (torch.bfloat16, torch.float16)), torch.bfloat16)
+        ctx = Ctx(sample.device, dtype)
+        st = self.prepare_conditioning(ctx, encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"])
+        t = timestep if torch.is_tensor(timestep) else torch.tensor([float(timestep)])
+        st.t_value = t.to(device=sample.device, dtype=torch.float32).reshape(-1).expand(sample.shape[0]).contiguous()
+        st.latents = sample[:, :4].to(torch.float32).contiguous()
+        return ctx, st
+
+
+class UNet2DConditionModel(UNetEncoderModel):
+    def __init__(self, cfg: UNetConfig = None):
+        super().__init__()
+        cfg = cfg or UNetConfig()
+        self.config = cfg
+        boc = cfg.block_out_channels
+        nb = len(boc)
+        if cfg.in_channels not in (4, 9):
+            raise ValueError(f"in_channels must be 4 (SDXL base) or 9 (SDXL inpainting: latents, mask, masked-image latents), got {cfg.in_channels}")
+        self.conv_in = Conv2d(cfg.in_channels, boc[0], 3)
+        self.time_embedding = TimestepEmbedding(boc[0], cfg.time_embed_dim)
+        self.add_embedding = TimestepEmbedding(cfg.projection_class_embeddings_input_dim, cfg.time_embed_dim)
+        self.down_blocks = nn.ModuleList([])
+        self.up_blocks = nn.ModuleList([])     # created before mid_block: fixes the attn_processors order
+        out = boc[0]
+        for i in range(nb):
+            cin, out = out, boc[i]
+            n_tf = 0 if i == 0 else cfg.transformer_layers_per_block[i]
+            self.down_blocks.append(DownBlock(cin, out, cfg.layers_per_block, n_tf, cfg.attention_head_dim[i], cfg,
+                                              add_down=(i != nb - 1)))
+        self.mid_block = MidBlock(boc[-1], cfg.transformer_layers_per_block[-1], cfg.attention_head_dim[-1], cfg)
+        rev, rev_tf = list(reversed(boc)), list(reversed(cfg.transformer_layers_per_block))
+        rev_heads = list(reversed(cfg.attention_head_dim))
+        out = rev[0]
+        for i in range(nb):
+            prev, out = out, rev[i]
+            cin = rev[min(i + 1, nb - 1)]
+            n_tf = 0 if i == nb - 1 else rev_tf[i]
+            self.up_blocks.append(UpBlock(cin, out, prev, cfg.layers_per_block + 1, n_tf, rev_heads[i], cfg,
+                                          add_up=(i != nb - 1)))
+        self.conv_norm_out = Norm(boc[0], cfg.norm_eps)
+        self.conv_out = Conv2d(boc[0], cfg.out_channels, 3)
+        self._number_time_emb_proj()
+
+    def resnets(self):
+        yield from super().resnets()
+        for blk in self.up_blocks:
+            yield from blk.resnets
 
     # ---- the forward, as emitted ops ----
     def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None, adapter=None):
@@ -839,19 +866,12 @@ class UNet2DConditionModel(nn.Module):
         if adapter is not None and control is not None:
             raise NotImplementedError("a T2I-Adapter together with a ControlNet is not built")
         cfg = self.config
-        B = 2 * S if cfg_dup else S
-        boc = cfg.block_out_channels
-        div = 1 << (len(boc) - 1)
-        if Hl % div or Wl % div:
-            # diffusers interpolates the up path to the skip's size in that case (forward_upsample_size); the
-            # fused nearest-x2 upsampling here does not, so refuse instead of producing misaligned skips
-            raise L.ImhError(f"latent {Hl}x{Wl}: sides must be multiples of {div} (image sides multiples of {8 * div})")
+        B = self._latent_batch(S, Hl, Wl, cfg_dup)
         # -- time embedding --
         ctx.tag = 1
         self._emit_time_embedding(ctx, st, B)
         # -- conv_in (+ CFG duplication + scale_model_input) --
         ctx.tag = 2
-        x = ctx.new(B, Hl, Wl, boc[0])
         cin, extra = cfg.in_channels, None
         if cin == 9:
             # diffusers StableDiffusionXLInpaintPipeline (num_channels_unet == 9): cat([scale_model_input(latents), mask, masked_image_latents], 1)
@@ -861,20 +881,15 @@ class UNet2DConditionModel(nn.Module):
                                  f"[{S}, 5, {Hl}, {Wl}]; got {None if extra is None else tuple(extra.shape)}")
         elif cin != 4:
             raise L.ImhError(f"conv_in runs 4 or 9 input channels, not {cin}")
-        ctx.ew(L.EW_CONV_IN, x, a=st.latents, w=_w(self.conv_in, ctx), bias=_b(self.conv_in, ctx),
-               tab=st.in_scale_tab, step=st.step if st.in_scale_tab is not None else None,
-               i=(S, Hl, Wl, boc[0], B, 9 if cin == 9 else 0), f=(1.0, 0, 0, 0), descr="conv_in", x2=extra,
-               nbytes=2.0 * B * Hl * Wl * boc[0])
-        h = Feat(x)                      # (conv_in has no statistics epilogue: Feat.stats() takes one pass, shared by both readers)
+        # (conv_in has no statistics epilogue: Feat.stats() takes one pass, shared by both readers)
+        h = Feat(self._emit_conv_in(ctx, st, S, B, Hl, Wl, "conv_in", extra))
         h, skips = self._emit_encoder(ctx, st, h, (10, 20, 30, 31), 1, **({"adapter": adapter} if adapter is not None else {}))
-        ho = GN_STATS_HANDOVER
-        kv_of = lambda t2d: [st.kv[self._pname(t2d, k)] for k in range(len(t2d.transformer_blocks))]
         if control is not None:
             ctx.tag = 32
             if len(control.down) != len(skips):
                 raise L.ImhError(f"{len(control.down)} ControlNet residuals for {len(skips)} skip connections")
-            inject = lambda f, r, descr: Feat(*ctx.control_add(f.t, r.view(r.shape[0], *f.t.shape[1:]), scale=control.scale, tab=control.tab, step=control.step,
-                                                               gn_sub=math.gcd(f.t.shape[-1] // cfg.norm_num_groups, 10), descr=descr))
+            inject = lambda f, r, descr: Feat.of(ctx.control_add(f.t, r.view(r.shape[0], *f.t.shape[1:]), scale=control.scale, tab=control.tab, step=control.step,
+                                                                 gn_sub=gn_sub(f.t.shape[-1], cfg.norm_num_groups), descr=descr))
             for i, r in enumerate(control.down):
                 f = skips[i]
                 skips[i] = inject(f, r, "control.skip")
@@ -889,70 +904,46 @@ class UNet2DConditionModel(nn.Module):
                 h = r.emit(ctx, h, st, skip=skips.pop())      # torch.cat([hidden, skip], 1) is read from its two producers
                 if blk.has_attn:
                     ctx.tag = 50 + bi
-                    h = blk.attentions[i].emit(ctx, h, kv_of(blk.attentions[i]), st)
+                    h = blk.attentions[i].emit(ctx, h, self._kv_of(st, blk.attentions[i]), st)
             if blk.upsamplers is not None:
                 ctx.tag = 40 + bi
                 u = blk.upsamplers[0].conv
                 Bu, Hu, Wu, Cu = h.t.shape
-                if UPSAMPLE_PHASE and ctx.conv_up_phase_cfg(Bu, Hu, Wu, Cu, u.weight.shape[0]) is not None:
+                kw = dict(bias=_b(u, ctx), descr="upsample", gn_groups=int(GN_STATS_HANDOVER))
+                if ctx.conv_up_phase_cfg(Bu, Hu, Wu, Cu, u.weight.shape[0]) is not None:
                     # four 2 x 2-tap phase convs on the low-res input: 4/9 of the multiply-adds of the conv over the upsampled image
-                    r_ = ctx.conv3x3(h.t, None, bias=_b(u, ctx), up=2, w_phase=u.packed_phase(ctx), descr="upsample", gn_groups=1 if ho else 0)
+                    up = Feat.of(ctx.conv3x3(h.t, None, up=2, w_phase=u.packed_phase(ctx), **kw))
                 else:
-                    r_ = ctx.conv3x3(h.t, u.packed(ctx), bias=_b(u, ctx), up=1, descr="upsample", gn_groups=1 if ho else 0)
+                    up = Feat.of(ctx.conv3x3(h.t, u.packed(ctx), up=1, **kw))
                 h.free(ctx)
-                h = Feat(*r_) if ho else Feat(r_)
+                h = up
         # -- out --
         ctx.tag = 60
         Bh, Hh, Ww, C0 = h.t.shape
-        if GN_TABLE_FOLD:
-            n = ctx.gn_table_apply(h.t.view(B, Hh * Ww, C0), GnSpec(h.stats(ctx, cfg.norm_num_groups), _w(self.conv_norm_out, ctx), _b(self.conv_norm_out, ctx),
-                                                                    cfg.norm_num_groups, cfg.norm_eps), True, descr="conv_norm_out").view(B, Hh, Ww, C0)
-        else:
-            tab = ctx.gn_table(h.stats(ctx, cfg.norm_num_groups), _w(self.conv_norm_out, ctx), _b(self.conv_norm_out, ctx), cfg.norm_num_groups, cfg.norm_eps,
-                               Hh * Ww, descr="conv_norm_out.table")
-            n = ctx.gn_apply(h.t.view(B, Hh * Ww, C0), tab, True, descr="conv_norm_out").view(B, Hh, Ww, C0)
-            ctx.free(tab)
+        n = _gn_pass(ctx, _gn_spec(ctx, self.conv_norm_out, cfg.norm_num_groups, h), h.t, True, "conv_norm_out")
         h.free(ctx)
         out = ctx.conv3x3(n, self.conv_out.packed(ctx), bias=_b(self.conv_out, ctx), descr="conv_out")
         ctx.free(n)
         ctx.tag = 0
         return out.view(B, Hh * Ww, cfg.out_channels)
 
-
-    def _pname(self, t2d, k):
-        names = getattr(self, "_imh_pnames", None)
-        if names is None or id(t2d.transformer_blocks[k].attn2) not in names:      # (a deepcopy carries stale ids)
-            names = {}
-            for name, mod in self.named_modules():
-                if isinstance(mod, Attention) and name.endswith("attn2"):
-                    names[id(mod)] = f"{name}.processor"
-            self._imh_pnames = names
-        return names[id(t2d.transformer_blocks[k].attn2)]
-
     # ---- eager drop-in signature (diffusers UNet2DConditionModel.forward) ----
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, cross_attention_kwargs=None,
                 return_dict=False, **kw):
-        dev = sample.device
-        dtype = self.conv_in.weight.dtype if self.conv_in.weight.dtype in (torch.bfloat16, torch.float16) \
-            else (sample.dtype if sample.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16)
         intra = kw.pop("down_intrablock_additional_residuals", None)
         if intra is not None:                    # a T2I-Adapter's features: four NCHW tensors, already scaled (diffusers T2IAdapter.forward's outputs)
             if kw.get("down_block_additional_residuals") is not None or kw.get("mid_block_additional_residual") is not None:
                 raise NotImplementedError("down_intrablock_additional_residuals together with the ControlNet pair is not built")
             if not isinstance(intra, (list, tuple)) or len(intra) != 4:
                 raise NotImplementedError("down_intrablock_additional_residuals is the list of the XL adapter's four features")
-        ctx = Ctx(dev, dtype)
+        ctx, st = self._eager_state(sample, timestep, encoder_hidden_states, added_cond_kwargs)
         B, _, Hl, Wl = sample.shape
-        st = self.prepare_conditioning(ctx, encoder_hidden_states, added_cond_kwargs["text_embeds"],
-                                       added_cond_kwargs["time_ids"])
+        nhwc = lambda t: t.to(device=ctx.device, dtype=ctx.dtype).permute(0, 2, 3, 1).contiguous()
         adapter = None
         if intra is not None:
             from .t2i_adapter import AdapterResiduals
-            adapter = AdapterResiduals([t.to(device=dev, dtype=dtype).permute(0, 2, 3, 1).contiguous() for t in intra])
-        t = timestep if torch.is_tensor(timestep) else torch.tensor([float(timestep)])
-        st.t_value = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
-        st.latents = sample[:, :4].to(torch.float32).contiguous()
+            adapter = AdapterResiduals([nhwc(t) for t in intra])
         if sample.shape[1] == 9:                 # the inpainting UNet's [latents | mask | masked-image latents]
             st.conv_in_extra = sample[:, 4:].to(torch.float32).contiguous()
         control = None
@@ -961,7 +952,6 @@ class UNet2DConditionModel(nn.Module):
             raise NotImplementedError("ControlNet residuals come as the pair down_block_additional_residuals + mid_block_additional_residual")
         if down_res is not None:                 # NCHW, already scaled (diffusers ControlNetModel.forward's outputs)
             from .controlnet import ControlResiduals
-            nhwc = lambda t: t.to(device=dev, dtype=dtype).permute(0, 2, 3, 1).contiguous()
             control = ControlResiduals([nhwc(t) for t in down_res], nhwc(mid_res))
         out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, control=control, **({"adapter": adapter} if adapter is not None else {}))
         y = out.view(B, Hl, Wl, -1).permute(0, 3, 1, 2).to(sample.dtype)

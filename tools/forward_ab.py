@@ -2,7 +2,6 @@
 rounds inside one process).  Records the 1024^2 CFG-2 SDXL forward once per configuration, then times the recorded plans
 in interleaved rounds: per-op HIP-event times (min over rounds, summed by op family) and the back-to-back wall time of the
 plan (median over rounds).  Knobs per configuration:
-    ln_stats   unet.LN_STATS_HANDOVER (LayerNorm statistics handed over from the producing GEMM's epilogue)
     gn_stats   unet.GN_STATS_HANDOVER (GroupNorm statistics likewise)
     gn_fuse    unet.GN_FUSE (GroupNorm + SiLU + channel concat inside the LDS-halo convs)
     attn       imh_debug_set(4, mode): self-attention key loop
@@ -57,8 +56,6 @@ CONFIGS = collections.OrderedDict([
     ("attn_whole_items", dict(attn=7)),
     ("qkv_256x128", dict(tuning={"2048,3840,1280,0,1": [23256, 128, 1]})),      # the one-launch [Q|K|V] of the L = 1024 layers on 240 tiles
     ("qkv_256x128_all", dict(tuning={"2048,3840,1280,0,1": [23256, 128, 1], "8192,1920,640,0,1": [23256, 128, 1]})),      # the pipelined kernel without the key-quarter workgroups
-    # LayerNorm statistics from stand-alone row-statistics launches instead of the producers' epilogues
-    ("ln_rowstats", dict(ln_stats=False)),
     ("gn_off", dict(gn_stats=False)),
     # GroupNorm + SiLU + concat inside the LDS-halo convs (round 4) vs table + apply passes + materialised concats
     ("gn_unfused", dict(gn_fuse=False)),
@@ -80,7 +77,6 @@ CONFIGS = collections.OrderedDict([
     ("conv32_ws", dict(tuning={f"2048,1280,{k},1": [2464, 160, 1] for k in (5760, 11520, 17280, 23040)})),
     ("conv64_ks80", dict(tuning={f"8192,640,{k},1": [7128, 80, 1] for k in (2880, 5760, 8640, 11520, 17280)})),
     ("conv128_ks80", dict(tuning={f"32768,320,{k},1": [7128, 80, 1] for k in (2880, 5760, 8640)})),
-    ("gn_table_launches", dict(gn_fold=False)),      # round 5: one gn_table launch per GroupNorm instead of the consumers building their sample's table
     ("conv64_p16ks80", dict(tuning={f"8192,640,{k},1": [7256, 80, 1] for k in (2880, 5760, 8640, 11520, 17280)})),      # 16 x 16 patch x 80 couts, K split
     ("conv64_p16ks80_w4", dict(halo=5, tuning={f"8192,640,{k},1": [7256, 80, 1] for k in (2880, 5760, 8640, 11520, 17280)})),
     ("conv128_p16ks80", dict(tuning={f"32768,320,{k},1": [7256, 80, 1] for k in (2880, 5760, 8640)})),
@@ -136,10 +132,8 @@ def main():
     outs = {}
     for n in names:
         c = CONFIGS[n]
-        U.LN_STATS_HANDOVER = bool(c.get("ln_stats", True))
         U.GN_STATS_HANDOVER = bool(c.get("gn_stats", True))
         U.GN_FUSE = bool(c.get("gn_fuse", True))
-        U.GN_TABLE_FOLD = bool(c.get("gn_fold", True))
         AP.DUAL_WS = bool(c.get("dual_ws", False))
         AP.QKV_ONE = bool(c.get("qkv_one", True))
         AP.QKV_ONE_WIDTHS = tuple(c.get("qkv_widths", (640, 1280)))
