@@ -251,23 +251,31 @@ class IPAttnProcessor2_0(nn.Module):
         self.num_tokens = num_tokens
         self.skip = skip
         self.store_attn_map = False     # True: keep the reference's `attn_map` side output (eager __call__ only)
+        # regional image prompts (regions.py; set through ip_adapter.set_ip_regions): the encoder states then end in num_images * num_tokens
+        # image tokens [r0 | r1 | ...] and `regions` (an IPRegions) says where each applies.  Plain attributes, not parameters
+        self.num_images = 1
+        self.regions = None
         self.to_k_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
         self.to_v_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
 
     def prepare_kv(self, ctx, attn, encoder_hidden_states):
         """Step-invariant part: K/V of the text tokens (and of the image tokens if not skip).
-        The last ``num_tokens`` tokens are always sliced off, even when skip (attention_processor.py:402-406)."""
-        end = encoder_hidden_states.shape[1] - self.num_tokens
+        The last ``num_images * num_tokens`` tokens are always sliced off, even when skip (attention_processor.py:402-406); the
+        image tokens are projected as a batch of B * num_images: image i of batch b at key (b * num_images + i) * lk2_pad."""
+        B = encoder_hidden_states.shape[0]
+        end = encoder_hidden_states.shape[1] - self.num_images * self.num_tokens
         text, ip = encoder_hidden_states[:, :end], encoder_hidden_states[:, end:]
         kv = KVCache()
         kv.k, kv.vt, kv.lk, kv.lk_pad = project_kv(ctx, text, _w(attn.to_k, ctx), _w(attn.to_v, ctx))
         if not self.skip:
+            ip = ip.reshape(B * self.num_images, self.num_tokens, ip.shape[-1])
             kv.k2, kv.vt2, kv.lk2, kv.lk2_pad = project_kv(ctx, ip, _w(self.to_k_ip, ctx), _w(self.to_v_ip, ctx))
         return kv
 
     def emit(self, ctx, attn, x, B, L_, residual=None, kv=None, step=None, scale_tab=None, ln=None, ln_stats=None,
-             want_stats=False):
-        """ln / ln_stats / want_stats as in AttnProcessor2_0.emit"""
+             want_stats=False, grid=None):
+        """ln / ln_stats / want_stats as in AttnProcessor2_0.emit; grid = (h, w) of the L_ tokens where the caller knows it (read only
+        with regions set: None -> regions.token_grid)"""
         C_ = x.shape[1]
         H = attn.heads
         if ln is None:
@@ -279,7 +287,24 @@ class IPAttnProcessor2_0(nn.Module):
             wq, lnq = fq[0], (fq[1], fq[2], norm.eps, ln_stats)
         ao = ctx.new(B * L_, C_)
         # to_q + text attention (+ image-prompt attention + text + scale * ip) in ONE launch (csrc/xattn.hip)
-        if kv.k2 is not None:
+        regions = getattr(self, "regions", None)
+        if kv.k2 is None and (regions is not None or getattr(self, "num_images", 1) != 1) and not self.skip:
+            raise L.ImhError("regions are set but the K / V cache holds no image-prompt keys")
+        if kv.k2 is not None and regions is None and getattr(self, "num_images", 1) != 1:
+            raise L.ImhError(f"num_images = {self.num_images} without regions: several image prompts per sample come with their masks")
+        if kv.k2 is not None and regions is not None:
+            # ... with N masked image prompts: the same launch count, csrc/xattn_regions.hip in place of csrc/xattn.hip
+            N = self.num_images
+            if regions.n != N or kv.k2.shape[0] != B * N:
+                raise L.ImhError(f"{regions.n} regions, num_images = {N}, image-prompt K cache of {kv.k2.shape[0]} = B * N = {B} * {N} entries expected")
+            rows, wts = regions.rows(ctx.device, grid=grid, tokens=L_)
+            if rows.shape[1] != L_:
+                raise L.ImhError(f"mask rows of {rows.shape[1]} tokens for a layer of {L_}")
+            ctx.cross_attention_regions(x, wq, kv.k, kv.vt, ao, B, H, L_, kv.lk, kv.lk_pad, C_, B * kv.lk_pad, HEAD_DIM ** -0.5,
+                                        kv.k2.view(-1, C_), kv.vt2, kv.lk2, kv.lk2_pad, C_, B * N * kv.lk2_pad, N, rows, weights=wts,
+                                        ln=lnq, scale2=float(self.scale), scale2_tab=scale_tab,
+                                        step=step if scale_tab is not None else None, descr="cross.fused+regions")
+        elif kv.k2 is not None:
             ctx.cross_attention(x, wq, kv.k, kv.vt, ao, B, H, L_, kv.lk, kv.lk_pad, C_, B * kv.lk_pad, HEAD_DIM ** -0.5, ln=lnq,
                                 k2=kv.k2, vt2=kv.vt2, Lk2=kv.lk2, Lk2_pad=kv.lk2_pad, ldk2=C_, ldvt2=B * kv.lk2_pad,
                                 scale2=float(self.scale), scale2_tab=scale_tab, step=step if scale_tab is not None else None,
@@ -328,8 +353,10 @@ class CNAttnProcessor2_0:
 
     def __init__(self, num_tokens=4):
         self.num_tokens = num_tokens
-        self.skip = True            # prepare_kv / emit below read these three like an IPAttnProcessor2_0(skip=True)
+        self.skip = True            # prepare_kv / emit below read these like an IPAttnProcessor2_0(skip=True)
         self.scale = 0.0
+        self.num_images = 1         # regional image prompts: num_images * num_tokens image tokens are sliced off
+        self.regions = None
 
     prepare_kv = IPAttnProcessor2_0.prepare_kv
     emit = IPAttnProcessor2_0.emit

@@ -8,6 +8,7 @@
 
 #include "../../include/imh.h"
 #include "../../include/imh_adapter.h"
+#include "../../include/imh_regions.h"
 #include "imh_common.h"
 #include "imh_kernels.h"
 
@@ -178,6 +179,33 @@ static int do_xattn(const imh_xattn_args* a, hipStream_t s) {
     if (x.ln_stats && (a->ln_slots <= 0 || a->C % a->ln_slots)) { set_error("cross_attention: ln_slots=%d must divide C=%d", a->ln_slots, a->C); return IMH_ERR_ARG; }
     x.C = a->C; x.ldx = a->ldx; x.ldw = a->ldw; x.split = 0;
     return xattn_launch(x, a->dtype, s);
+}
+
+// imh_cross_attention_regions (include/imh_regions.h): the pointer / alignment rules here, the shape rules in the launcher
+static int do_xattn_regions(const imh_xattn_regions_args* a, hipStream_t s) {
+    const char* who = "cross_attention_regions";
+    if (!a || !a->X || !a->Wq || !a->K || !a->Vt || !a->K2 || !a->Vt2 || !a->O || !a->mask) { set_error("%s: null pointer argument", who); return IMH_ERR_ARG; }
+    if ((a->ln_s == nullptr) != (a->ln_c == nullptr) || (a->ln_s && !(a->ln_eps > 0.f))) {
+        set_error("%s: folded LayerNorm needs ln_s, ln_c and ln_eps > 0", who); return IMH_ERR_ARG;
+    }
+    if (((uintptr_t)a->mask | (uintptr_t)a->weights) & 3) { set_error("%s: mask and weights must be 4-byte aligned", who); return IMH_ERR_ARG; }
+    if ((a->scale2_tab == nullptr) != (a->step == nullptr)) { set_error("%s: scale2_tab and step come together", who); return IMH_ERR_ARG; }
+    if (a->C != a->H * 64) { set_error("%s: C=%d must be H*64 (H=%d)", who, a->C, a->H); return IMH_ERR_SHAPE; }
+    XRegionParams r;
+    XAttnParams& x = r.x;
+    AttnParams& p = x.a;
+    p.Q = nullptr; p.K = a->K; p.Vt = a->Vt; p.K2 = a->K2; p.Vt2 = a->Vt2; p.O = a->O;
+    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.Lk_pad = a->Lk_pad; p.Lk2 = a->Lk2; p.Lk2_pad = a->Lk2_pad;
+    p.ldq = 0; p.ldk = a->ldk; p.ldvt = a->ldvt; p.ldk2 = a->ldk2; p.ldvt2 = a->ldvt2; p.ldo = a->ldo;
+    p.scale = a->scale; p.scale2 = a->scale2; p.scale2_tab = a->scale2_tab; p.step = a->step;
+    p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes; p.split = 0; p.defer_log2 = 0.f;
+    x.X = a->X; x.Wq = a->Wq; x.ln_s = a->ln_s; x.ln_c = a->ln_c; x.ln_eps = a->ln_eps;
+    x.ln_stats = a->ln_s ? a->ln_stats : nullptr; x.ln_slots = a->ln_slots;
+    if (a->ln_s && !a->ln_stats) { set_error("%s: the folded LayerNorm takes the token rows' statistics from ln_stats", who); return IMH_ERR_ARG; }
+    if (x.ln_stats && (a->ln_slots <= 0 || a->C % a->ln_slots)) { set_error("%s: ln_slots=%d must divide C=%d", who, a->ln_slots, a->C); return IMH_ERR_ARG; }
+    x.C = a->C; x.ldx = a->ldx; x.ldw = a->ldw; x.split = 0;
+    r.mask = a->mask; r.weights = a->weights; r.n_img = a->n_img; r.ldm = a->ldm;
+    return xattn_regions_launch(r, a->dtype, s);
 }
 
 static int do_attn_small(const imh_small_attn_args* a, hipStream_t s) {
@@ -357,6 +385,7 @@ struct imh_op {
         imh_randn_args randn;
         imh_clip_preprocess_args clip;
         imh_control_add_args cadd;
+        imh_xattn_regions_args xregions;
     } u;
 };
 
@@ -385,6 +414,7 @@ static int run_op(const imh_op& o, hipStream_t s) {
         case IMH_OP_RANDN_SEEDED: return do_randn_seeded(&o.u.randn, s);
         case IMH_OP_CLIP_PREPROCESS: return do_clip_preprocess(&o.u.clip, s);
         case IMH_OP_CONTROL_ADD: return do_control_add(&o.u.cadd, s);
+        case IMH_OP_XATTN_REGIONS: return do_xattn_regions(&o.u.xregions, s);
     }
     set_error("plan: unknown op kind %d", o.kind);
     return IMH_ERR_ARG;
@@ -411,6 +441,7 @@ static size_t args_size(int kind) {
         case IMH_OP_RANDN_SEEDED: return sizeof(imh_randn_args);
         case IMH_OP_CLIP_PREPROCESS: return sizeof(imh_clip_preprocess_args);
         case IMH_OP_CONTROL_ADD: return sizeof(imh_control_add_args);
+        case IMH_OP_XATTN_REGIONS: return sizeof(imh_xattn_regions_args);
     }
     return 0;
 }
@@ -481,6 +512,8 @@ int imh_gemm_check(const imh_gemm_args* a) {
 int imh_attention(const imh_attn_args* a, void* stream) { return do_attn(a, (hipStream_t)stream); }
 
 int imh_cross_attention(const imh_xattn_args* a, void* stream) { return do_xattn(a, (hipStream_t)stream); }
+
+int imh_cross_attention_regions(const imh_xattn_regions_args* a, void* stream) { return do_xattn_regions(a, (hipStream_t)stream); }
 
 int imh_attention_small(const imh_small_attn_args* a, void* stream) { return do_attn_small(a, (hipStream_t)stream); }
 

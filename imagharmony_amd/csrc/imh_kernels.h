@@ -107,6 +107,17 @@ struct XAttnParams {
     int split;            // (set by the launcher) items per XCD dealt as two 64-query halves
 };
 int xattn_launch(const XAttnParams& p, int dtype, hipStream_t stream);
+
+// the same with n_img masked image prompts (xattn_regions.hip; include/imh_regions.h): x.a.K2 / Vt2 hold image i of batch b at key
+// (b * n_img + i) * Lk2_pad; mask fp32 [n_img][ldm] over the query tokens, weights fp32 [n_img] or null (all 1).  One-head form only
+constexpr int XR_MAX_IMAGES = 8;
+struct XRegionParams {
+    XAttnParams x;
+    const float* mask;
+    const float* weights;
+    int n_img, ldm;
+};
+int xattn_regions_launch(const XRegionParams& p, int dtype, hipStream_t stream);
 extern int g_attn_force_nw;
 extern int g_xattn_mode;
 extern int g_w16_pf;

@@ -200,7 +200,7 @@ class Ctx:
                 L.check(rc, "imh_plan_add")
             self.keep.extend(k for k in keep if k is not None)
             self.tags.append((self.tag, kind, descr, flops, nbytes, shape, epi))
-            self._ops.append((kind, args, self._cold(keep) if kind in (L.OP_GEMM, L.OP_XATTN) else []))
+            self._ops.append((kind, args, self._cold(keep) if kind in (L.OP_GEMM, L.OP_XATTN, L.OP_XATTN_REGIONS) else []))
             return
         s = self.stream()
         if kind == L.OP_GEMM:
@@ -215,6 +215,8 @@ class Ctx:
             rc = self.lib.imh_attention_small(C.byref(args), s)
         elif kind == L.OP_XATTN:
             rc = self.lib.imh_cross_attention(C.byref(args), s)
+        elif kind == L.OP_XATTN_REGIONS:
+            rc = self.lib.imh_cross_attention_regions(C.byref(args), s)
         elif kind == L.OP_ATTN_ENC:
             rc = self.lib.imh_attention_enc(C.byref(args), s)
         elif kind == L.OP_ATTN_ENC_CAUSAL:
@@ -715,6 +717,105 @@ class Ctx:
             self.free(keep_st[0])
         return out
 
+    @staticmethod
+    def regions_refusal(a):
+        """the argument rules of imh_cross_attention_regions (csrc/api.hip do_xattn_regions, csrc/xattn_regions.hip xattn_regions_launch)
+        restated over a filled L.XAttnRegionsArgs: None when the library launches it, else the reason.  imh_plan_add copies a launch's
+        arguments unseen, so the recorder refuses HERE what the library would refuse when the plan first runs."""
+        if not (a.X and a.Wq and a.K and a.Vt and a.K2 and a.Vt2 and a.O and a.mask):
+            return "null pointer argument"
+        if bool(a.ln_s) != bool(a.ln_c) or (a.ln_s and not a.ln_eps > 0.0):
+            return "folded LayerNorm needs ln_s, ln_c and ln_eps > 0"
+        if ((a.mask or 0) | (a.weights or 0)) & 3:
+            return "mask and weights must be 4-byte aligned"
+        if bool(a.scale2_tab) != bool(a.step):
+            return "scale2_tab and step come together"
+        if a.C != a.H * 64:
+            return f"C={a.C} must be H*64 (H={a.H})"
+        if a.ln_s and not a.ln_stats:
+            return "the folded LayerNorm takes the token rows' statistics from ln_stats"
+        if a.ln_s and (a.ln_slots <= 0 or a.C % a.ln_slots):
+            return f"ln_slots={a.ln_slots} must divide C={a.C}"
+        if not 1 <= a.n_img <= L.REGIONS_MAX_IMAGES:
+            return f"n_img={a.n_img} must be 1 .. {L.REGIONS_MAX_IMAGES}"
+        if a.Lk <= 0 or a.Lk_pad % 64 or a.Lk_pad < a.Lk:
+            return f"Lk={a.Lk} Lk_pad={a.Lk_pad} (pad must be a multiple of 64 and >= Lk)"
+        if a.Lk2 <= 0 or a.Lk2_pad % 64 or a.Lk2_pad < a.Lk2:
+            return f"Lk2={a.Lk2} Lk2_pad={a.Lk2_pad} invalid"
+        if a.C <= 0 or a.C % 64:
+            return f"C={a.C} must be a positive multiple of 64"
+        if any(int(v) & 7 for v in (a.ldx, a.ldw, a.ldk, a.ldvt, a.ldo, a.ldk2, a.ldvt2)):
+            return "leading dimensions must be multiples of 8 elements"
+        if a.B <= 0 or a.H <= 0 or a.Lq <= 0:
+            return "empty problem"
+        if a.ldm < a.Lq:
+            return f"ldm={a.ldm} is shorter than a mask row of Lq={a.Lq} values"
+        if a.dtype not in (L.IMH_DT_BF16, L.IMH_DT_F16):
+            return f"unknown dtype {a.dtype}"
+        return None
+
+    def cross_attention_regions(self, x, wq, k, vt, out, B, H, Lq, Lk, Lk_pad, ldk, ldvt, scale, k2, vt2, Lk2, Lk2_pad, ldk2, ldvt2,
+                                n_img, mask, weights=None, ln=None, scale2=1.0, scale2_tab=None, step=None, descr="cross.regions"):
+        """cross_attention() with n_img masked image prompts per sample in one launch (csrc/xattn_regions.hip, include/imh_regions.h):
+        out = attention(to_q(LN?(x)), K, V) + sum_i (g * weights[i]) * mask[i, q] * attention(., K2_i, V2_i), g = scale2_tab[*step] or
+        scale2.  k2 / vt2 hold image i of batch b at key (b * n_img + i) * Lk2_pad (the K / V projection of the image tokens as a batch of
+        B * n_img); mask fp32 [n_img, >= Lq] (rows mask.stride(0) apart), weights fp32 [n_img] or None (all 1), both on the device.
+        What the library refuses is refused here, where the launch is recorded."""
+        self._chk(x, descr + ".x"); self._chk(wq, descr + ".wq")
+        self._chk(mask, descr + ".mask", torch.float32); self._chk(weights, descr + ".weights", torch.float32)
+        self._chk(scale2_tab, descr + ".scale2_tab", torch.float32); self._chk(step, descr + ".step", torch.int32)
+        C_ = H * 64
+        if x.shape[-1] != C_ or tuple(wq.shape) != (C_, C_) or x.stride(-1) != 1 or wq.stride(-1) != 1:
+            raise L.ImhError(f"{descr}: x [.., {C_}] / wq [{C_}, {C_}] expected, got {tuple(x.shape)} / {tuple(wq.shape)}")
+        if mask is None or k2 is None or vt2 is None:
+            raise L.ImhError(f"{descr}: k2, vt2 and mask are required")
+        n_img = int(n_img)
+        if mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] != n_img or mask.shape[1] < Lq:
+            raise L.ImhError(f"{descr}: mask {tuple(mask.shape)} must be fp32 [n_img = {n_img}, >= Lq = {Lq}] with unit column stride")
+        if weights is not None and (weights.dim() != 1 or weights.numel() != n_img or not weights.is_contiguous()):
+            raise L.ImhError(f"{descr}: weights {tuple(weights.shape)} must be a dense fp32 vector of n_img = {n_img}")
+        keys2 = B * n_img * Lk2_pad
+        if k2.dim() != 2 or vt2.dim() != 2 or k2.shape[0] < keys2 or vt2.shape[1] < keys2 or k2.shape[1] < C_ or vt2.shape[0] < C_:
+            raise L.ImhError(f"{descr}: k2 {tuple(k2.shape)} / vt2 {tuple(vt2.shape)} do not hold B * n_img * Lk2_pad = {keys2} keys of {C_} dims")
+        a = L.XAttnRegionsArgs()
+        a.X, a.Wq, a.K, a.Vt, a.O = x.data_ptr(), wq.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
+        a.K2, a.Vt2 = k2.data_ptr(), vt2.data_ptr()
+        a.B, a.H, a.Lq, a.C = B, H, Lq, C_
+        a.Lk, a.Lk_pad, a.Lk2, a.Lk2_pad = Lk, Lk_pad, Lk2, Lk2_pad
+        a.ldx, a.ldw, a.ldk, a.ldvt, a.ldk2, a.ldvt2, a.ldo = x.stride(0), wq.stride(0), ldk, ldvt, ldk2, ldvt2, out.stride(0)
+        a.scale, a.scale2, a.dtype = scale, scale2, self.dt
+        a.scale2_tab, a.step = self._p(scale2_tab), self._p(step)
+        a.n_img, a.mask, a.ldm, a.weights = n_img, mask.data_ptr(), mask.stride(0), self._p(weights)
+        keep_st = ()
+        own = False
+        if ln is not None:
+            a.ln_s, a.ln_c, a.ln_eps = ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2])
+            st_in = ln[3] if len(ln) > 3 and ln[3] is not None else None
+            own = st_in is None
+            if own:
+                a.ln_stats, a.ln_slots = 1, 1           # (row_stats' one slot per row, a placeholder pointer: the statistics launch comes after the rule check)
+            else:
+                a.ln_stats, a.ln_slots = st_in[0].data_ptr(), int(st_in[1])
+        why = self.regions_refusal(a)
+        if why:
+            raise L.ImhError(f"{descr}: {why}")
+        if own:
+            st_in = self.row_stats(x.view(-1, C_), descr=descr + ".ln_row_stats")
+            a.ln_stats, a.ln_slots = st_in[0].data_ptr(), int(st_in[1])
+        if ln is not None:
+            keep_st = (st_in[0],)
+        es = x.element_size()
+        M = B * Lq
+        fl = 2.0 * M * C_ * C_ + 4.0 * B * H * Lq * (Lk + n_img * Lk2) * 64
+        by = es * (2 * M * C_ + C_ * C_ + 2 * B * (Lk + n_img * Lk2) * C_) + 4.0 * n_img * Lq
+        self._emit(L.OP_XATTN_REGIONS, a, descr=descr, flops=fl, nbytes=by,
+                   keep=(x, wq, k, vt, out, k2, vt2, scale2_tab, step, mask, weights) + tuple((ln or ())[:2]) + keep_st,
+                   shape=(B, H, Lq, Lk, Lk_pad), epi=dict(Lk2=Lk2, Lk2_pad=Lk2_pad, tab=scale2_tab is not None, ln=ln is not None,
+                                                          ln_slots=int(a.ln_slots) if ln is not None else 0, n_img=n_img))
+        if own:
+            self.free(keep_st[0])
+        return out
+
     # ------------------------------------------------------------------ fp32 (reference-precision) ops of the VAE decode tail (csrc/f32.hip)
     def _f32(self, op, a, descr):
         if self.record:
@@ -1194,7 +1295,7 @@ class Ctx:
         if self._pf_done or not self.record:
             return
         self._pf_done = True
-        can = (L.OP_GEMM, L.OP_ATTN, L.OP_LAYERNORM, L.OP_GROUPNORM, L.OP_GEMM_DUAL, L.OP_XATTN)
+        can = (L.OP_GEMM, L.OP_ATTN, L.OP_LAYERNORM, L.OP_GROUPNORM, L.OP_GEMM_DUAL, L.OP_XATTN, L.OP_XATTN_REGIONS)
 
         def carries(i):
             kind, a = self._ops[i][0], self._ops[i][1]

@@ -47,9 +47,25 @@ _PLAN_ENGINE = ("steps", "init_noise_sigma", "plan", "noise_pred", "plan_tail", 
 #   scheduler (the class name), num_train_timesteps, num_inference_steps, control_guidance_start / _end (the IP-scale window),
 #   denoising_end, ip_scale (the IP processors' scale, the value of the gating table), steps (the row behind the last step that runs),
 #   tables (SHA-1 of every table the plan reads, the IP gating table included), controlnet (SHA-1 of cn_scale_tab; None: no branch),
-#   inpaint (None | "blend" | "concat"), adapter ((SHA-1 of ad_gate_tab, conditioning scale); None: no T2I-Adapter), seeded
-PlanKey = collections.namedtuple("PlanKey", "scheduler num_train_timesteps num_inference_steps control_guidance_start control_guidance_end "
-                                 "denoising_end ip_scale steps tables controlnet inpaint adapter seeded")
+#   inpaint (None | "blend" | "concat"), adapter ((SHA-1 of ad_gate_tab, conditioning scale); None: no T2I-Adapter), seeded,
+#   regions (IPRegions.digest(): SHA-1 of N, the weights and the mask bytes) -- a trailing field that exists only on the key of a plan
+#   with regional image prompts: a key without them is the thirteen-field tuple it always was (``.regions`` reads None), so it compares,
+#   hashes, slices and serialises as before, and PlanKey(...) equals PlanKey(..., regions=None)
+_KEY_FIELDS = ("scheduler num_train_timesteps num_inference_steps control_guidance_start control_guidance_end "
+               "denoising_end ip_scale steps tables controlnet inpaint adapter seeded")
+PlanKeyRegions = collections.namedtuple("PlanKeyRegions", _KEY_FIELDS + " regions")
+
+
+class PlanKey(collections.namedtuple("PlanKey", _KEY_FIELDS)):
+    __slots__ = ()
+    regions = None
+
+    def __new__(cls, *args, regions=None, **kw):
+        if len(args) == len(cls._fields) + 1:
+            args, regions = args[:-1], args[-1]
+        if regions is None:
+            return super().__new__(cls, *args, **kw)
+        return PlanKeyRegions(*args, **kw, regions=regions)
 
 
 def _move(names, src, dst):
@@ -103,6 +119,8 @@ class DenoiseEngine:
     adapter = None           # a t2i_adapter.T2IAdapter whose four features are added inside the UNet's down path (set_adapter)
     ad = None                # its state: dict(image, scale, feats = four NHWC tensors, ctx) (set_adapter_image)
     ad_gate_tab = None       # fp32 [steps] 1 / 0 per step of the current schedule (set_schedule(adapter_conditioning_factor=))
+    # regional image prompts (regions.py; an engine without them records, launches and returns what it always did)
+    regions = None           # an IPRegions: the cross-attention layers with an image-prompt branch record csrc/xattn_regions.hip's launch (set_ip_regions)
 
     def __init__(self, unet, device, dtype=torch.bfloat16, use_graph=True):
         """Touches no device: the eager context is made on first use, so the "no CPU path" ImhError of a non-ROCm device surfaces at the
@@ -136,6 +154,27 @@ class DenoiseEngine:
         """a stored control image serves S samples at height x width: one image or one per sample, at that size"""
         return tuple(image.shape[2:]) == (height, width) and image.shape[0] in (1, S)
 
+    # -- regional image prompts (opt-in) --
+    def _regions_alone(self, what, other):
+        if self.regions is not None and other:
+            raise NotImplementedError(f"regional image prompts together with {what} are not built")
+
+    def set_ip_regions(self, regions):
+        """regions: a regions.IPRegions (N masks over the picture, N weights), or None to switch them off.  BEFORE set_conditioning: the
+        prompt embeddings of that conditioning end in N * num_tokens image tokens, and the K / V caches are projected per image.  The
+        UNet's IP processors get num_images / regions here (ip_adapter.set_ip_regions); the masks reach the plan as fp32 rows per token
+        grid, resized once per grid on the CPU (IPRegions.rows) and kept alive by the plan that reads them.  The regions' digest is part
+        of the plan key.  Not built, refused here and where the other side is set: cfg_role, a ControlNet, a T2I-Adapter."""
+        from .regions import IPRegions
+        if regions is not None and not isinstance(regions, IPRegions):
+            raise TypeError(f"set_ip_regions takes an imagharmony_amd.regions.IPRegions or None, not {type(regions).__name__}")
+        if regions is not None:
+            for what, other in (("a ControlNet", self.controlnet), ("a T2I-Adapter", self.adapter), ("cfg_role (the CFG split)", self.cfg_role)):
+                if other is not None:
+                    raise NotImplementedError(f"regional image prompts together with {what} are not built")
+        self.regions = regions
+        self._sync_regions()
+
     # -- T2I-Adapter (opt-in, like the ControlNet; the two exclude each other) --
     def set_adapter(self, adapter):
         """adapter: an imagharmony_amd.t2i_adapter.T2IAdapter on the engine's device, or None to switch the injections off.  The next
@@ -148,6 +187,7 @@ class DenoiseEngine:
             if self.controlnet is not None:
                 raise NotImplementedError("a T2I-Adapter together with a ControlNet is not built")
             self._whole_pair_only(self.cfg_role is not None, "T2I-Adapter")
+            self._regions_alone("a T2I-Adapter", True)
         if adapter is not self.adapter:
             swap = self.adapter is not None and adapter is not None
             if swap:
@@ -195,6 +235,7 @@ class DenoiseEngine:
             self._whole_pair_only(self.cfg_role is not None, "ControlNet")
             if self.adapter is not None:
                 raise NotImplementedError("a ControlNet together with a T2I-Adapter is not built")
+            self._regions_alone("a ControlNet", True)
         if controlnet is not self.controlnet:
             swap = self.controlnet is not None and controlnet is not None
             if swap:
@@ -251,6 +292,10 @@ class DenoiseEngine:
             raise ValueError("cfg_role must be None, 0 (unconditional half) or 1 (conditional half)")
         self._whole_pair_only(cfg_role is not None and self.controlnet is not None, "ControlNet")
         self._whole_pair_only(cfg_role is not None and self.adapter is not None, "T2I-Adapter")
+        self._regions_alone("cfg_role (the CFG split)", cfg_role is not None)
+        self._regions_alone("a ControlNet", self.controlnet is not None)
+        self._regions_alone("a T2I-Adapter", self.adapter is not None)
+        self._sync_regions()
         self._plans, self.plan = {}, None         # every recorded plan points into the previous conditioning's caches
         self.cfg_role = cfg_role
         self.do_cfg = guidance_scale > 1.0                                   # custom_pipelines.py:223
@@ -318,6 +363,13 @@ class DenoiseEngine:
         stacked, eager or graph.  The flag is part of the plan key; the bank plan and the seeded plan of one schedule coexist."""
         st, dev = self.st, self.device
         t_start = int(t_start)
+        self._regions_alone("cfg_role (the CFG split)", self.cfg_role is not None)
+        self._regions_alone("a ControlNet", self.controlnet is not None)
+        self._regions_alone("a T2I-Adapter", self.adapter is not None)
+        have, want = self._images_in_caches(), self.regions.n if self.regions is not None else 1
+        if have is not None and have != want:
+            raise L.ImhError(f"the conditioning's K / V caches hold {have} image prompt(s) per sample, the regions {want}: "
+                             f"set_ip_regions comes before set_conditioning")
         if not 0 <= t_start < int(num_inference_steps):
             raise ValueError(f"t_start {t_start} outside the schedule of {num_inference_steps} steps")
         from .attention_processor import IPAttnProcessor2_0
@@ -365,7 +417,8 @@ class DenoiseEngine:
             ad_key = (hashlib.sha1(torch.tensor(ad_gate, dtype=torch.float32).numpy().tobytes()).hexdigest(), self.ad["scale"])
         key = PlanKey(type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps),
                       float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(),
-                      controlnet=cn_key, inpaint=mode, adapter=ad_key, seeded=seeded)
+                      controlnet=cn_key, inpaint=mode, adapter=ad_key, seeded=seeded,
+                      regions=self.regions.digest() if self.regions is not None else None)
         self.t_start = t_start
         self.inpaint = mode
         self.general = general
@@ -421,7 +474,7 @@ class DenoiseEngine:
         _move(("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
                "xcd_candidates", "xcd_cells", "t_start", "inpaint", "general", "stochastic", "seeded"), self, e)
         # shared, read-only during denoising: the ControlNet's hint, caches and table, the adapter's features and gate table
-        _move(("controlnet", "cn", "cn_scale_tab", "adapter", "ad", "ad_gate_tab"), self, e)
+        _move(("controlnet", "cn", "cn_scale_tab", "adapter", "ad", "ad_gate_tab", "regions"), self, e)
         st = StepState()
         src = self.st
         st.aug_emb, st.kv = src.aug_emb, src.kv                      # shared, read-only during denoising
@@ -433,8 +486,22 @@ class DenoiseEngine:
         e.st = st
         return e
 
+    def _images_in_caches(self):
+        """image prompts per sample the K / V caches of the current conditioning were projected for (None: not known here)"""
+        if self._cond_in is None or self.st is None or not getattr(self.st, "kv", None):
+            return None
+        rows = self._cond_in[0].shape[0]
+        return next((int(kv.k2.shape[0]) // rows for kv in self.st.kv.values() if kv.k2 is not None), None)
+
+    def _sync_regions(self):
+        """the UNet's processors carry this engine's regions (or none) whenever it projects K / V or records: engines that share a UNet
+        may differ in them"""
+        from .ip_adapter import set_ip_regions
+        set_ip_regions(self.unet, self.regions)
+
     def _record(self):
         st = self.st
+        self._sync_regions()
         if st.latents is None or tuple(st.latents.shape) != (self.S, 4, self.H, self.W):
             st.latents = torch.zeros(self.S, 4, self.H, self.W, dtype=torch.float32, device=self.device)
         split = self.do_cfg and self.cfg_role is not None

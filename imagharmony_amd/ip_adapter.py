@@ -44,6 +44,20 @@ def set_scale(unet, scale):
             p.scale = scale
 
 
+def set_ip_regions(unet, regions):
+    """regional image prompts (regions.IPRegions: N masks over the picture, N weights) on every IP / ControlNet cross-attention
+    processor of `unet`, or None to take them off: the encoder states then end in N * num_tokens image tokens [r0 | r1 | ...].  Every
+    processor slices that many tokens off (the skip=True ones too, as they always slice num_tokens); the ones with an image-prompt
+    branch apply image i where mask i says."""
+    from .regions import IPRegions
+    if regions is not None and not isinstance(regions, IPRegions):
+        raise TypeError(f"set_ip_regions takes an imagharmony_amd.regions.IPRegions or None, not {type(regions).__name__}")
+    for p in unet.attn_processors.values():
+        if isinstance(p, (IPAttnProcessor2_0, CNAttnProcessor2_0)):
+            p.num_images = regions.n if regions is not None else 1
+            p.regions = regions
+
+
 # --------------------------------------------------------------------------------------------
 # Adapter classes (API surface of ip_adapter/ip_adapter.py:69-478 for the SDXL variants)
 # --------------------------------------------------------------------------------------------
@@ -265,6 +279,37 @@ class IPAdapterXL(IPAdapter):
                                           extra_prompt_embeds=extra_prompt_embeds)
         return self._run(ipe, uipe, prompt, negative_prompt, num_samples, seed, num_inference_steps, prompt_embeds, kwargs)
 
+
+    def generate_regions(self, regions, prompt=None, negative_prompt=None, scale=1.0, num_samples=4, seed=None,
+                         num_inference_steps=30, prompt_embeds=None, **kwargs):
+        """Several image prompts for one picture, each where its mask says ("this reference for the left half, that one for the
+        right"): diffusers' ``ip_adapter_masks`` with several images per adapter.  regions: a list of dicts with
+        ``pil_image`` or ``clip_image_embeds`` ([1, D]), ``mask`` (PIL, or a tensor [height, width]; white = here), ``weight`` (default
+        1.0) and optionally ``extra_text`` or ``extra_prompt_embeds`` -- each region goes through get_image_embeds, with its own
+        HarmonyAttention correction.  The image tokens are concatenated [text | r0 | r1 | ...], the unconditional ones the same way, and
+        reach the pipe with ``ip_region_masks= / ip_region_weights=``; height / width (kwargs) are the pipe's defaults unless given.
+        ``binarize=False`` (kwargs) keeps soft masks.  The text-to-image, image-to-image and inpainting pipes take regions; the
+        ControlNet and adapter pipes refuse them.  Afterwards the pipe is as it was: a plain ``generate`` sees one image prompt."""
+        regions = list(regions)
+        if not regions or not all(isinstance(r, dict) and r.get("mask") is not None for r in regions):
+            raise ValueError("generate_regions takes a list of dicts, each with `mask` and `pil_image` or `clip_image_embeds`")
+        self.set_scale(scale)
+        prompt, negative_prompt = _prompts(prompt, negative_prompt, 1)
+        ipes, uipes = [], []
+        for r in regions:
+            extra = r.get("extra_prompt_embeds")
+            if extra is None and r.get("extra_text") is not None:
+                extra = self.pipe.encode_prompt(r["extra_text"], num_images_per_prompt=num_samples, do_classifier_free_guidance=True,
+                                                negative_prompt=negative_prompt)[0]
+            ipe, uipe = self.get_image_embeds(pil_image=r.get("pil_image"), clip_image_embeds=r.get("clip_image_embeds"),
+                                              extra_prompt_embeds=extra)
+            if ipe.shape[0] != 1:
+                raise ValueError(f"a region carries one image, got a batch of {ipe.shape[0]}")
+            ipes.append(ipe)
+            uipes.append(uipe)
+        kwargs = dict(kwargs, ip_region_masks=[r["mask"] for r in regions], ip_region_weights=[float(r.get("weight", 1.0)) for r in regions])
+        return self._run(torch.cat(ipes, 1), torch.cat(uipes, 1), prompt, negative_prompt, num_samples, seed, num_inference_steps,
+                         prompt_embeds, kwargs)
 
     @torch.no_grad()
     def generate_pns(self, seeds, pil_image=None, prompt=None, negative_prompt=None, extra_text=None, scale=1.0,

@@ -20,6 +20,7 @@ OP_GEMM, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_EW, OP_ATTN_SMALL, OP_GEMM_DUAL
 OP_STEP_SEEDED, OP_RANDN_SEEDED = 10, 11      # the seeded step noise (imh.h): additive plan kinds
 OP_CLIP_PREPROCESS = 13                       # imh_clip_preprocess (imh.h: kind 12 stays refused)
 OP_CONTROL_ADD = 15                           # imh_control_add: the ControlNet's gated residual add (+ GroupNorm partials of the sum); 12 and 14 stay refused
+OP_XATTN_REGIONS = 17                         # imh_cross_attention_regions (include/imh_regions.h): N masked image prompts; 12, 14 and 16 stay refused
 CLIP_DT_F32 = 2                               # imh_clip_preprocess's fp32 rows (no other entry takes it)
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
@@ -76,6 +77,14 @@ class XAttnArgs(C.Structure):
                 ("ldx", _i32), ("ldw", _i32), ("ldk", _i32), ("ldvt", _i32), ("ldk2", _i32), ("ldvt2", _i32), ("ldo", _i32),
                 ("scale", _f32), ("scale2", _f32), ("scale2_tab", _vp), ("step", _vp), ("dtype", _i32),
                 ("pf_ptr", _vp), ("pf_bytes", C.c_uint32)]
+
+
+class XAttnRegionsArgs(C.Structure):
+    """imh_xattn_regions_args (include/imh_regions.h): XAttnArgs' fields, then the regions' own"""
+    _fields_ = XAttnArgs._fields_ + [("n_img", _i32), ("mask", _vp), ("ldm", _i32), ("weights", _vp)]
+
+
+REGIONS_MAX_IMAGES = 8
 
 
 class SmallAttnArgs(C.Structure):
@@ -194,6 +203,11 @@ ADAPTER_SYMBOLS = [
     ("imh_adapter_op", C.c_int, [C.POINTER(AdapterArgs), _vp]),
 ]
 
+# ... and the one of include/imh_regions.h (regional image prompts)
+REGIONS_SYMBOLS = [
+    ("imh_cross_attention_regions", C.c_int, [C.POINTER(XAttnRegionsArgs), _vp]),
+]
+
 _lib = None
 
 
@@ -210,7 +224,7 @@ def load():
         raise ImhError(f"{LIB_PATH} is missing: build the HIP extension first "
                        f"(python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS:
+    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS + REGIONS_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

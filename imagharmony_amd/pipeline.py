@@ -237,7 +237,25 @@ class StableDiffusionXLCustomPipeline:
         __call__ has come before, in that __call__."""
         self._refuse(c.output_type, c.eta, c.kwargs)
         self.step_seed_table(c.step_noise, c.generator, None)
+        masks, weights = c.kwargs.get("ip_region_masks"), c.kwargs.get("ip_region_weights")
+        if masks is None and weights is not None:
+            raise ValueError("ip_region_weights= comes with ip_region_masks=")
+        if masks is not None and (getattr(self, "controlnet", None) is not None or getattr(self, "adapter", None) is not None):
+            raise NotImplementedError("regional image prompts (ip_region_masks=) under a ControlNet or a T2I-Adapter are not built")
         c.begin(self)
+        if masks is None:
+            return self._denoise(c)
+        # regional image prompts: prompt_embeds carry text + N * num_tokens tokens; the masks are prepared at the call's height x width
+        from .regions import IPRegions
+        regions = masks if isinstance(masks, IPRegions) else IPRegions.from_masks(masks, c.height, c.width, weights,
+                                                                                  binarize=c.kwargs.get("binarize", True))
+        try:
+            self.engine.set_ip_regions(regions)
+            return self._denoise(c)
+        finally:
+            self.engine.set_ip_regions(None)        # a later plain call sees num_images == 1 and no regions
+
+    def _denoise(self, c: _Call):
         if c.prompt_embeds is None:
             c.prompt_embeds, c.negative_prompt_embeds, c.pooled_prompt_embeds, c.negative_pooled_prompt_embeds = \
                 self.encode_prompt(c.prompt, c.num_images_per_prompt, c.guidance_scale > 1.0, c.negative_prompt)

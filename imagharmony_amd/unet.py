@@ -343,9 +343,10 @@ class BasicTransformerBlock(nn.Module):
         return FOLD_LAYERNORM and isinstance(self.attn1.processor, (AttnProcessor2_0, CNAttnProcessor2_0)) \
             and isinstance(self.attn2.processor, (IPAttnProcessor2_0, CNAttnProcessor2_0)) and L_ % 64 == 0
 
-    def emit(self, ctx, h, B, L_, kv, st, stats=None, want_stats=False):
+    def emit(self, ctx, h, B, L_, kv, st, stats=None, want_stats=False, grid=None):
         """h: the residual stream [B*L, C]; stats: the row statistics of h from the GEMM that wrote it, or None (both consumed)
-        -> (h3, the statistics of h3 for the next block's norm1 where want_stats and this block runs folded, else None)."""
+        -> (h3, the statistics of h3 for the next block's norm1 where want_stats and this block runs folded, else None).
+        grid = (h, w) of the L tokens: handed to a cross-attention processor that carries regional image prompts (regions.py)."""
         p1, p2 = self.attn1.processor, self.attn2.processor
         if isinstance(p1, CNAttnProcessor2_0):
             p1 = _SELF_ATTN
@@ -353,13 +354,14 @@ class BasicTransformerBlock(nn.Module):
             raise L.ImhError("a non-HIP attention processor is installed; the fused forward needs "
                              "imagharmony_amd.attention_processor processors")
         ip2 = isinstance(p2, IPAttnProcessor2_0)
+        rk = dict(grid=grid) if ip2 and getattr(p2, "regions", None) is not None else {}      # (without regions: the call as it always was)
         if self.fused(L_):
             # LayerNorm never materialises: every consumer GEMM reads the residual stream itself, and takes the rows' statistics
             # from the epilogue of the GEMM that wrote it
             h1, s1 = p1.emit(ctx, self.attn1, h, B, L_, residual=h, ln=self.norm1, ln_stats=stats, want_stats=True)
             _free_rows(ctx, h, stats)
             h2, s2 = p2.emit(ctx, self.attn2, h1, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab, ln=self.norm2,
-                             ln_stats=s1, want_stats=True)
+                             ln_stats=s1, want_stats=True, **rk)
             _free_rows(ctx, h1, s1)
             h3, s3 = self.ff.emit(ctx, h2, residual=h2, ln=self.norm3, ln_stats=s2, want_stats=want_stats)
             _free_rows(ctx, h2, s2)
@@ -370,7 +372,7 @@ class BasicTransformerBlock(nn.Module):
         h1 = p1.emit(ctx, self.attn1, n, B, L_, residual=h)
         ctx.free(n); ctx.free(h)
         n = _ln(ctx, self.norm2, h1, "norm2")
-        h2 = p2.emit(ctx, self.attn2, n, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab) \
+        h2 = p2.emit(ctx, self.attn2, n, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab, **rk) \
             if ip2 else p2.emit(ctx, self.attn2, n, B, L_, residual=h1, kv=kv)
         ctx.free(n); ctx.free(h1)
         n = _ln(ctx, self.norm3, h2, "norm3")
@@ -404,7 +406,7 @@ class Transformer2DModel(nn.Module):
         ctx.free(n)
         for i, (blk, kv) in enumerate(zip(blocks, kvs)):
             more = ho and i + 1 < len(blocks) and blocks[i + 1].fused(L_)
-            h, stats = blk.emit(ctx, h, B, L_, kv, st, stats=stats, want_stats=more)
+            h, stats = blk.emit(ctx, h, B, L_, kv, st, stats=stats, want_stats=more, grid=(Hh, Ww))
         out = Feat.of(ctx.gemm(h, _w(self.proj_out, ctx), bias=_b(self.proj_out, ctx), residual=x2, descr="t2d.proj_out",
                                gn_out=L_ if GN_STATS_HANDOVER else None))
         ctx.free(h)
