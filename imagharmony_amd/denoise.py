@@ -149,6 +149,13 @@ class DenoiseEngine:
         self._plans = {k: v for k, v in self._plans.items() if not doomed(k)}
         self.plan, self._sched_key = None, None
 
+    def _check_weights_epoch(self):
+        """the K / V caches, aug_emb, the time-embedding rows and the recorded plans derive from the UNet's weights, and PlanKey has no
+        field for them: a LoRA merge (lora.LoRAState.apply) after set_conditioning is refused instead of computing from stale copies"""
+        ctx = self._cond_ctx             # (it owns the caches, so it carries the epoch they were computed at; forks share it)
+        if ctx is not None and getattr(ctx, "weights_epoch", 0) != getattr(self.unet, "lora_epoch", 0):
+            raise RuntimeError("weights changed since set_conditioning (a LoRA was loaded, re-weighted or unloaded): call set_conditioning again")
+
     @staticmethod
     def _image_fits(image, S, height, width):
         """a stored control image serves S samples at height x width: one image or one per sample, at that size"""
@@ -315,6 +322,7 @@ class DenoiseEngine:
         ctx = Ctx(self.device, self.dtype)      # fresh context: the K/V caches must outlive pooled buffers
         st = self.unet.prepare_conditioning(ctx, ehs, text, ids)
         self._cond_ctx = ctx
+        ctx.weights_epoch = getattr(self.unet, "lora_epoch", 0)       # unet.lora_epoch as these caches saw it (_check_weights_epoch)
         self.S, self.H, self.W = S, height // 8, width // 8
         self.T_total = ehs.shape[1]
         old = self.st
@@ -363,6 +371,7 @@ class DenoiseEngine:
         stacked, eager or graph.  The flag is part of the plan key; the bank plan and the seeded plan of one schedule coexist."""
         st, dev = self.st, self.device
         t_start = int(t_start)
+        self._check_weights_epoch()
         self._regions_alone("cfg_role (the CFG split)", self.cfg_role is not None)
         self._regions_alone("a ControlNet", self.controlnet is not None)
         self._regions_alone("a T2I-Adapter", self.adapter is not None)
@@ -688,6 +697,7 @@ class DenoiseEngine:
                                       "(a seeded schedule with step_seeds= needs none)")
         if self.t_start or self.inpaint:
             raise NotImplementedError("denoise_cfg_split runs whole text-to-image schedules (t_start = 0, no inpainting)")
+        self._check_weights_epoch()
         if self.plan is None:
             self._record()
         st = self.st
@@ -771,6 +781,7 @@ class DenoiseEngine:
         nothing is drawn; generator= / step_noise= are refused there, and step_seeds= anywhere else."""
         if self.cfg_role is not None and self.do_cfg:
             raise L.ImhError("this engine holds one half of the CFG pair (cfg_role): use denoise_cfg_split")
+        self._check_weights_epoch()
         if self.inpaint and latents is not None:
             raise L.ImhError("an inpainting schedule starts from prepare_inpaint: denoise(None)")
         if self.plan is None:

@@ -142,6 +142,16 @@ class AdapterArgs(C.Structure):
 ADAPTER_UNSHUFFLE, ADAPTER_RELU, ADAPTER_AVGPOOL2 = range(3)      # imh_adapter_op's modes (eager only: no plan kind)
 
 
+class LoraItem(C.Structure):
+    """imh_lora_item (include/imh_lora.h): one adapted weight of the grouped merge; the table is an array of these, on the host and on the device"""
+    _fields_ = [("base", _vp), ("dst", _vp), ("U", _vp), ("D", _vp), ("g", _vp), ("N", _i32), ("K", _i32), ("R", _i32),
+                ("ld_base", _i32), ("ld_dst", _i32), ("ldu", _i32), ("ldd", _i32), ("pad", _i32)]
+
+
+class LoraMergeArgs(C.Structure):
+    _fields_ = [("items_host", _vp), ("items_dev", _vp), ("tile_start_dev", _vp), ("n_items", _i32), ("total_tiles", _i32), ("dtype", _i32)]
+
+
 class F32Args(C.Structure):
     _fields_ = [("X", _vp), ("W", _vp), ("Y", _vp), ("bias", _vp), ("residual", _vp), ("gamma", _vp), ("beta", _vp), ("ws", _vp),
                 ("M", _i32), ("N", _i32), ("K", _i32), ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32),
@@ -208,6 +218,12 @@ REGIONS_SYMBOLS = [
     ("imh_cross_attention_regions", C.c_int, [C.POINTER(XAttnRegionsArgs), _vp]),
 ]
 
+# ... and the two of include/imh_lora.h (the grouped low-rank merge: eager only, no plan kind)
+LORA_SYMBOLS = [
+    ("imh_lora_merge_tiles", C.c_int, [C.c_int, C.c_int]),
+    ("imh_lora_merge", C.c_int, [C.POINTER(LoraMergeArgs), _vp]),
+]
+
 _lib = None
 
 
@@ -224,7 +240,7 @@ def load():
         raise ImhError(f"{LIB_PATH} is missing: build the HIP extension first "
                        f"(python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS + REGIONS_SYMBOLS:
+    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS + REGIONS_SYMBOLS + LORA_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

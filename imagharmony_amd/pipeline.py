@@ -12,6 +12,7 @@ import torch
 
 from .attention_processor import IPAttnProcessor
 from .denoise import DenoiseEngine
+from .lora import LoRAPipelineMixin
 from .schedulers import DDIMScheduler, get_timesteps
 
 
@@ -166,7 +167,8 @@ class _EditCall(_Call):
                      latent_mask(self.mask, h, w) if self.inpaint else None, strength_max, masked_moments)
 
 
-class StableDiffusionXLCustomPipeline:
+class StableDiffusionXLCustomPipeline(LoRAPipelineMixin):
+    """(LoRAPipelineMixin: diffusers' load_lora_weights / set_adapters / fuse_lora ..., delegated to the UNet -- lora.py)"""
     vae_scale_factor = 8
 
     def __init__(self, unet, scheduler=None, device="cuda:0", dtype=torch.bfloat16, vae_decode: Optional[Callable] = None,

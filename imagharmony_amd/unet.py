@@ -28,6 +28,7 @@ import torch.nn as nn
 from . import lib as L
 from .attention_processor import AttnProcessor2_0, CNAttnProcessor2_0, IPAttnProcessor2_0, _b, _vkey, _w, fold_ln
 from .ctx import Ctx, GnSpec
+from .lora import LoRAMixin
 
 
 # BasicTransformerBlock.norm1/2/3 folded into the consumer GEMMs (exact algebra, tested): the consumer takes the
@@ -815,7 +816,9 @@ class UNetEncoderModel(nn.Module):
         return ctx, st
 
 
-class UNet2DConditionModel(UNetEncoderModel):
+class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
+    """(LoRAMixin: load_lora_weights / set_adapters / ... merge adapters into the weights, lora.py; a UNet without one is what it was)"""
+
     def __init__(self, cfg: UNetConfig = None):
         super().__init__()
         cfg = cfg or UNetConfig()
