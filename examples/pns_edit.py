@@ -7,10 +7,13 @@ whole path (PIL in -> CLIP-shaped embeddings -> HarmonyAttention + ImageProjMode
                                 [--seeds 0 1 2 3] [--steps 30] [--preview-steps 10] [--size 1024]
                                 [--scheduler euler-a --step-noise seed]
                                 [--init-image in.png --strength 0.6] [--clip-backend hip --judge-preprocess hip]
+                                [--preview-vae taesdxl.safetensors | --preview-vae random]
 
 With --init-image the candidates are image-to-image EDITS of that image (IPAdapterXL.generate_pns(image=, strength=)): every seed fixes its
 posterior and add-noise draws, the previews are decoded and scored by the CLIP judge when a tower is attached (--clip-backend), and
---judge-preprocess hip takes the decoded previews to the HIP tower's patch rows in one launch.
+--judge-preprocess hip takes the decoded previews to the HIP tower's patch rows in one launch.  --preview-vae lets the judge see the
+previews through AutoencoderTiny (diffusers' TAESDXL decoder, 35 small launches per decode) instead of the full VAE; the winner's image
+still comes from the full VAE.
 
 Launch under torch.distributed.run with N ranks to shard the seeds over N GPUs (one process per GPU, RCCL).
 """
@@ -63,6 +66,9 @@ def main():
     ap.add_argument("--strength", type=float, default=0.6, help="with --init-image: how far the edit departs from the image (0 .. 1)")
     ap.add_argument("--judge-preprocess", choices=("torch", "hip"), default="torch",
                     help="with --init-image and a CLIP tower: how the judge gets from decoded previews to the tower's input (hip needs --clip-backend hip)")
+    ap.add_argument("--preview-vae", nargs="?", const="random", default=None, metavar="PATH",
+                    help="with --init-image and a CLIP tower: decode the judge's previews with AutoencoderTiny -- PATH = a diffusers taesdxl "
+                         "safetensors file; no value or `random` = seeded random weights")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -120,9 +126,14 @@ def main():
         from PIL import Image
         ip.image_encoder = enc                                            # the judge's tower (None: the latent-statistic scorer)
         init = Image.open(a.init_image).convert("RGB").resize((a.size, a.size))
+        preview_vae = None
+        if a.preview_vae is not None:
+            from imagharmony_amd import AutoencoderTiny
+            preview_vae = AutoencoderTiny().init_random_(7).to(dev, dtype) if a.preview_vae == "random" else \
+                AutoencoderTiny.from_safetensors(a.preview_vae, device=dev, dtype=dtype)
         r = ip.generate_pns(a.seeds, clip_image_embeds=clip_embeds, prompt_embeds=prompt, extra_prompt_embeds=extra, scale=a.scale,
                             preview_steps=a.preview_steps, num_inference_steps=a.steps, guidance_scale=a.guidance, image=init,
-                            strength=a.strength, step_noise=a.step_noise, judge_preprocess=a.judge_preprocess)
+                            strength=a.strength, step_noise=a.step_noise, judge_preprocess=a.judge_preprocess, preview_vae=preview_vae)
         if int(os.environ.get("RANK", "0")) == 0:
             r["images"][0].save(a.out)
             print(f"seeds {a.seeds} -> scores {[round(float(s), 4) for s in r['scores']]}; best seed {r['best_seed']}; "

@@ -22,6 +22,8 @@ _PIPELINES = ("StableDiffusionXLCustomPipeline", "StableDiffusionXLImg2ImgCustom
 _CONTROLNET = ("ControlNetModel",)
 # the SDXL T2I-Adapter (t2i_adapter.py): the once-per-image net whose four features the UNet's down path adds
 _T2I_ADAPTER = ("T2IAdapter",)
+# diffusers' AutoencoderTiny decoder (tiny_vae.py): the preview VAE of generate_pns(preview_vae=), or a pipeline's vae=
+_TINY_VAE = ("AutoencoderTiny", "TinyVAEConfig")
 # regional image prompts (regions.py): N masks over the picture and N weights for IPAdapterXL.generate_regions / ip_region_masks=
 _REGIONS = ("IPRegions",)
 # the schedulers of the device-resident loop (schedulers.py): the two linear ones and the multistep / ancestral ones
@@ -51,6 +53,9 @@ def __getattr__(name):
     if name in _T2I_ADAPTER:
         from . import t2i_adapter
         return getattr(t2i_adapter, name)
+    if name in _TINY_VAE:
+        from . import tiny_vae
+        return getattr(tiny_vae, name)
     if name in _REGIONS:
         from . import regions
         return getattr(regions, name)

@@ -1235,6 +1235,34 @@ class Ctx:
         self._adapter_op(a, descr)
         return out
 
+    # ------------------------------------------------------------------ AutoencoderTiny's conv (imh_tinyvae_conv: eager, one launch per conv)
+    def tinyvae_conv(self, x, w, bias=None, residual=None, relu=False, up2=False, head=False, tail=False, descr="tinyvae_conv"):
+        """one 3 x 3 conv of the tiny VAE decoder (include/imh_tinyvae.h).  Body: x NHWC [B, H, W, 64], w packed [64, 576] -> NHWC
+        [B, Ho, Wo, 64] = act(conv(up(x)) + bias + residual); head: x fp32 NCHW [B, 4, H, W], w [64, 36] -> NHWC (tanh clamp, conv, bias,
+        ReLU); tail: w [3, 576] -> fp32 NCHW [B, 3, H, W] = 2 (conv + bias) - 1.  The library validates; a refusal raises ImhError."""
+        if self.record:
+            raise L.ImhError(f"{descr}: imh_tinyvae_conv is no plan kind: the tiny decoder runs eagerly")
+        self._chk(x, descr + ".x", torch.float32 if head else None)
+        self._chk(w, descr + ".w"); self._chk(bias, descr + ".bias"); self._chk(residual, descr + ".residual")
+        cin, cout = (4 if head else 64), (3 if tail else 64)
+        ok = x.dim() == 4 and x.is_contiguous() and x.numel() > 0 and (x.shape[1] if head else x.shape[3]) == cin
+        if not ok or tuple(w.shape) != (cout, 9 * cin) or not w.is_contiguous():
+            raise L.ImhError(f"{descr}: x {tuple(x.shape)} / w {tuple(w.shape)}: expected dense "
+                             f"{'NCHW [B, 4, H, W]' if head else 'NHWC [B, H, W, 64]'} and a packed [{cout}, {9 * cin}] weight")
+        if bias is not None and (tuple(bias.shape) != (cout,) or not bias.is_contiguous()):
+            raise L.ImhError(f"{descr}: bias {tuple(bias.shape)}: expected [{cout}]")
+        B, H, W = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) if head else (int(v) for v in x.shape[:3])
+        Ho, Wo = (2 * H, 2 * W) if up2 else (H, W)
+        if residual is not None and (tuple(residual.shape) != (B, Ho, Wo, 64) or not residual.is_contiguous()):
+            raise L.ImhError(f"{descr}: residual {tuple(residual.shape)}: expected dense [{B}, {Ho}, {Wo}, 64]")
+        out = self.new(B, 3, Ho, Wo, dtype=torch.float32) if tail else self.new(B, Ho, Wo, 64)
+        a = L.TinyVaeArgs()
+        a.x, a.w, a.bias, a.residual, a.y = x.data_ptr(), w.data_ptr(), self._p(bias), self._p(residual), out.data_ptr()
+        a.B, a.H, a.W, a.dtype = B, H, W, self.dt
+        a.flags = (L.TINYVAE_RELU if relu else 0) | (L.TINYVAE_UP2 if up2 else 0) | (L.TINYVAE_HEAD if head else 0) | (L.TINYVAE_TAIL if tail else 0)
+        L.check(self.lib.imh_tinyvae_conv(C.byref(a), self.stream()), descr)
+        return out
+
     def gather_rows(self, table, idx, add=None, out=None, descr="gather_rows"):
         """out[r] = table[idx[r]] (+ add[r % P]) (IMH_EW_GATHER_ROWS): table [rows, C] and add [P, C] row-major in the compute dtype, idx
         int32 [n] on the device.  The caller has validated the indices on the host (the CLIP text towers' ids and EOS rows are host-known)."""

@@ -317,7 +317,7 @@ class IPAdapterXL(IPAdapter):
                      clip_image_embeds=None, prompt_embeds=None, extra_prompt_embeds=None, height=None, width=None,
                      output_type="pil", step_noise="global", image=None, mask_image=None, strength=None, judge_preprocess="torch",
                      control_image=None, controlnet_conditioning_scale=1.0, adapter_image=None, adapter_conditioning_scale=1.0,
-                     adapter_conditioning_factor=1.0, **schedule_kw):
+                     adapter_conditioning_factor=1.0, preview_vae=None, **schedule_kw):
         """Preference-guided noise selection (README.md:27, assets/1.png) around ``generate``: every candidate seed gets
         a ``preview_steps`` denoise, a judge scores the previews, the best NOISE gets the full ``num_inference_steps``
         denoise.  Candidates are sharded over the ranks of an initialised torch.distributed group (one process per
@@ -351,6 +351,9 @@ class IPAdapterXL(IPAdapter):
         per stage): one control image serves every candidate, its features are computed once per call.  An adapter makes no draws, so the
         winner's latents are the bits of the pipe's own call with ``image=adapter_image``, the scale and the factor, and that seed's
         generator.  On a pipe without an adapter ``adapter_image`` is refused (ValueError).
+        ``preview_vae`` (default None: ``pipe.vae``): the VAE whose ``decode`` the default CLIP judge sees the previews through -- an
+        ``AutoencoderTiny`` decodes a preview in 35 small launches; its fp32 NCHW image is what either ``judge_preprocess`` takes.  The
+        winner's image still comes from ``pipe.vae``; a custom ``scorer`` never sees it.
         Returns dict(images, best_seed, scores, latents)."""
         from . import pns
         from .pipeline import (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline, _ControlNetPipe,
@@ -418,7 +421,7 @@ class IPAdapterXL(IPAdapter):
         else:
             stages = pns.two_stage_fns(eng, pipe.scheduler, preview_steps, num_inference_steps, step_noise=step_noise, **schedule_kw)
         if scorer is None:
-            scorer = self._default_scorer(pipe.vae, fused, judge_preprocess)
+            scorer = self._default_scorer(pipe.vae if preview_vae is None else preview_vae, fused, judge_preprocess)
         state = {"n": None}
 
         def stacked(stage):
@@ -495,6 +498,8 @@ class IPAdapterXL(IPAdapter):
             raise ValueError(f"strength must be in [0.0, 1.0], got {strength}")
         if output_type != "latent" and pipe.vae is None and pipe.vae_decode is None:
             raise NotImplementedError("output_type=%r needs a VAE on the pipeline; pass output_type='latent'" % (output_type,))
+        if getattr(pipe.vae, "tiny", False):
+            pipe.vae.encode()                                    # AutoencoderTiny: its encoder's NotImplementedError
         if pipe.vae is None or not getattr(pipe.vae, "with_encoder", False):
             raise NotImplementedError("an edit needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
         for steps in (preview_steps, num_inference_steps):

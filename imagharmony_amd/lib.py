@@ -152,6 +152,15 @@ class LoraMergeArgs(C.Structure):
     _fields_ = [("items_host", _vp), ("items_dev", _vp), ("tile_start_dev", _vp), ("n_items", _i32), ("total_tiles", _i32), ("dtype", _i32)]
 
 
+class TinyVaeArgs(C.Structure):
+    """imh_tinyvae_args (include/imh_tinyvae.h): one 3 x 3 conv of the AutoencoderTiny decoder"""
+    _fields_ = [("x", _vp), ("w", _vp), ("bias", _vp), ("residual", _vp), ("y", _vp), ("B", _i32), ("H", _i32), ("W", _i32),
+                ("flags", _i32), ("dtype", _i32)]
+
+
+TINYVAE_RELU, TINYVAE_UP2, TINYVAE_HEAD, TINYVAE_TAIL = 1, 2, 4, 8      # imh_tinyvae_conv's flags (eager only: no plan kind)
+
+
 class F32Args(C.Structure):
     _fields_ = [("X", _vp), ("W", _vp), ("Y", _vp), ("bias", _vp), ("residual", _vp), ("gamma", _vp), ("beta", _vp), ("ws", _vp),
                 ("M", _i32), ("N", _i32), ("K", _i32), ("ldx", _i32), ("ldw", _i32), ("ldy", _i32), ("ldr", _i32),
@@ -224,6 +233,11 @@ LORA_SYMBOLS = [
     ("imh_lora_merge", C.c_int, [C.POINTER(LoraMergeArgs), _vp]),
 ]
 
+# ... and the one of include/imh_tinyvae.h (the AutoencoderTiny decoder's conv: eager only, no plan kind)
+TINYVAE_SYMBOLS = [
+    ("imh_tinyvae_conv", C.c_int, [C.POINTER(TinyVaeArgs), _vp]),
+]
+
 _lib = None
 
 
@@ -240,7 +254,7 @@ def load():
         raise ImhError(f"{LIB_PATH} is missing: build the HIP extension first "
                        f"(python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS + REGIONS_SYMBOLS + LORA_SYMBOLS:
+    for name, res, args in SYMBOLS + ADAPTER_SYMBOLS + REGIONS_SYMBOLS + LORA_SYMBOLS + TINYVAE_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

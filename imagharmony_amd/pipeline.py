@@ -142,6 +142,8 @@ class _EditCall(_Call):
             if (self.height or H, self.width or W) != (H, W):
                 raise NotImplementedError(f"height / width {self.height} x {self.width} differ from the image's {H} x {W}: resize the image first")
             self.mask = preprocess_mask(self.mask_image, H, W)               # mask_processor.preprocess
+        if getattr(pipe.vae, "tiny", False):
+            pipe.vae.encode()                                                # AutoencoderTiny: its encoder's NotImplementedError
         if pipe.vae is None or not getattr(pipe.vae, "with_encoder", False):
             raise NotImplementedError(f"{self.edit} needs a VAE with its encoder: vae=AutoencoderKL(config, with_encoder=True)")
         self.height, self.width = H, W
