@@ -7,6 +7,7 @@ A plain helper module; no fixtures, no pytest settings."""
 import torch
 import torch.nn.functional as F
 
+import exact_operands as exo
 from guarded import Arena
 from imagharmony_amd import lib as L
 from imagharmony_amd.ctx import Ctx, GnSpec, GnStats
@@ -120,9 +121,11 @@ def _ln_norm(K):
 
 
 class GemmCell:
-    """inputs and the float64 statement of one (feature, shape, dtype); call(ctx, cfg) places everything in ctx.arena and issues the request"""
+    """inputs and the float64 statement of one (feature, shape, dtype); call(ctx, cfg) places everything in ctx.arena and issues the request.
+    exact=True (the features of exact_operands.GEMM_FEATURES): the operands come from the binary grids of tests/exact_operands.py, the statement
+    and the placement stay as they are, and check() asks for the statement's one correctly rounded value, element for element"""
 
-    def __init__(self, feat, shape, dtype):
+    def __init__(self, feat, shape, dtype, exact=False):
         from conftest import ref_row_stats
         from test_gpu_ops import geglu_ref
         self.feat, self.shape, self.dtype = feat, shape, dtype
@@ -137,6 +140,13 @@ class GemmCell:
         self.res = (rnd(M, n_out, dtype=dtype, seed=4) * 1.5 + 0.5).contiguous() if f in ("residual", "residual_inplace", "bias_residual", "stats_out") else None
         self.rpb = (M + 2) // 3 if f == "rowadd" else 0
         self.rowadd = rnd(3, N + 64, dtype=dtype, seed=5) if f == "rowadd" else None
+        self.exact = exact
+        if exact:
+            assert f in exo.GEMM_FEATURES, f"{f} has no exact form"
+            o = exo.gemm_operands(f, shape, dtype)
+            assert all((getattr(self, n) is None) == (o[n] is None) for n in ("bias", "rowadd")) and (self.res is None) == (o["residual"] is None)
+            self.x, self.w, self.bias, self.res, self.rowadd = (None if t is None else t.to(DEV) for t in (o["x"], o["w"], o["bias"], o["residual"], o["rowadd"]))
+            self.assert_premise()
         self.hw = 256 if f in ("gn_out", "silu_gn_out") else 0
         self.ln = None
         if f in LN_FEATS:
@@ -184,6 +194,11 @@ class GemmCell:
         self.col0 = N // 2 if f == "yt" else 0          # 320 of 640: a multiple of 160
         self.ref = ref
         self.n_out = self.col0 or n_out
+
+    def assert_premise(self):
+        """exact cells: the launch's partial sums are exact in fp32 (again after a test replaced an operand)"""
+        ra = None if self.rowadd is None else self.rowadd[:, 32:32 + self.shape[1]]
+        exo.assert_exact_in_fp32(self.shape[2], self.x, self.w, self.bias, ra, self.res)
 
     def extras(self):
         return self.bias is not None or self.res is not None or self.rowadd is not None or self.feat in ("x2", "yt")
@@ -241,6 +256,11 @@ class GemmCell:
         from test_gpu_ops import assert_close, vt_unpermute
         f = self.feat
         ref = self.ref
+        if self.exact:
+            odt = torch.float32 if f == "out_f32" else self.dtype
+            assert out.dtype == odt
+            exo.assert_equal(vt_unpermute(out.contiguous()) if f == "vt_perm" else out, exo.expected(ref, odt), what)
+            return
         if f == "yt":
             assert_close(out, ref[:, :self.col0], self.dtype, what + " [Q|K]", k=self.k)
             assert_close(vt_unpermute(yt.contiguous()), ref[:, self.col0:].t(), self.dtype, what + " V^T", k=self.k)
@@ -309,7 +329,10 @@ def ref_gn_table(x, gamma, beta):
 
 
 class ConvCell:
-    def __init__(self, feat, shape, dtype, two_source=None):
+    """exact=True (the features of exact_operands.CONV_FEATURES): grid operands, the same statement and placement, equality in check().
+    gn_affine (exact only): conv3x3(gn=(table, False)) with a hand-made [B, Cin, 2] table whose fma(x, scale, shift) is exact in T"""
+
+    def __init__(self, feat, shape, dtype, two_source=None, exact=False):
         if feat == "x2" and shape[3] < 128:          # the feature's own rule: two sources of at least 64 channels each
             shape = shape[:3] + (128,) + shape[4:]
         self.feat, self.shape, self.dtype = feat, shape, dtype
@@ -319,6 +342,8 @@ class ConvCell:
         self.pad = 1 if f == "pad1" else 0
         self.up = 1 if f == "up1" else (2 if f == "up2" else 0)
         self.gn = f in ("gn_table", "gn_spec")
+        self.exact, self.table = exact, None
+        assert exact or f != "gn_affine"
         self.c1 = (Cin - 64 if two_source is None else two_source) if f == "x2" or two_source else Cin
         self.x = (rnd(B, H, W, Cin, dtype=dtype, seed=1) * (1.3 if self.gn else 1.0) + (0.4 if self.gn else 0.0)).contiguous()
         self.w4 = rnd(Cout, Cin, 3, 3, dtype=dtype, seed=2, scale=(9 * Cin) ** -0.5)
@@ -336,14 +361,35 @@ class ConvCell:
         if f == "rowadd":
             self.rowadd = rnd(B, Cout + 64, dtype=dtype, seed=4)
             ref = ref + self.rowadd[:, 32:32 + Cout].double()[:, None, None, :]
+        if exact:          # the same statement over the grid operands; xin: what the MFMAs read (x, or the staged halo of gn_affine)
+            assert f in exo.CONV_FEATURES and two_source is None, f"{f} has no exact form"
+            o = exo.conv_operands(f, shape, dtype)
+            self.x, self.w4, self.bias = o["x"].to(DEV), o["w4"].to(DEV), o["bias"].to(DEV)
+            self.res, self.rowadd = (None if o[n] is None else o[n].to(DEV) for n in ("residual", "rowadd"))
+            self.xin = self.x
+            if f == "gn_affine":
+                self.table = o["table"].to(DEV)
+                self.xin = exo.affine(self.x, self.table, dtype)
+            ref = conv_ref64(self.xin, self.w4, self.bias, self.stride, 1 if self.up else 0, self.pad)
+            if self.res is not None:
+                ref = ref + self.res.double()
+            if self.rowadd is not None:
+                ref = ref + self.rowadd[:, 32:32 + Cout].double()[:, None, None, :]
         self.ref = ref
         self.K = 9 * Cin
         self.M = ref.shape[0] * ref.shape[1] * ref.shape[2]
+        if exact:
+            self.assert_premise()
+
+    def assert_premise(self):
+        """exact cells: the launch's partial sums are exact in fp32 (again after a test replaced an operand, and xin with it)"""
+        ra = None if self.rowadd is None else self.rowadd[:, 32:32 + self.shape[4]]
+        exo.assert_exact_in_fp32(self.K, self.xin, self.w4, self.bias, ra, self.res)
 
     def variant_ok(self, cfg):
         if self.up == 2:
             return (cfg[0], cfg[1]) in Ctx._PHASE and self.shape[4] % cfg[1] == 0 and cfg[2] == 1
-        if (self.gn or self.c1 != self.shape[3]) and cfg[0] not in Ctx._HALO:      # (conv_fuses_gn: the front end lives in the LDS-halo kernels)
+        if (self.gn or self.table is not None or self.c1 != self.shape[3]) and cfg[0] not in Ctx._HALO:      # (conv_fuses_gn: the front end lives in the LDS-halo kernels)
             return False
         return Ctx._variant_ok(cfg[0], cfg[2], 0, 1, self.stride, False, self.M, self.shape[4], pad=self.pad)
 
@@ -384,6 +430,8 @@ class ConvCell:
                     kw["gn"] = (a.place(ref_gn_table(self.x, self.gamma, self.beta)), True)
                 else:
                     kw["gn"] = (ctx.gn_table(parts if two else parts[0], gamma, beta, G, 1e-5, H * W), True)
+            if self.table is not None:
+                kw["gn"] = (a.place(self.table), False)
             a.seal()
             r = ctx.conv3x3(xa, w, x2=xb, **kw)
         return (r[0], r[1]) if isinstance(r, tuple) else (r, None)
@@ -392,6 +440,9 @@ class ConvCell:
         from test_gpu_gnstats import _check_partials, _ref_partials
         from test_gpu_ops import assert_close
         assert tuple(out.shape) == tuple(self.ref.shape), (out.shape, self.ref.shape)
+        if self.exact:
+            exo.assert_equal(out, exo.expected(self.ref, self.dtype), what)
+            return
         assert_close(out, self.ref, self.dtype, what, k=self.k)
         if self.feat == "gn_groups" and side is not None:
             B, Ho, Wo, Cout = self.ref.shape

@@ -99,6 +99,39 @@ def _f32_gemm_conv_cases(ctx, tol):
         assert (y.double() - (ref.permute(0, 2, 3, 1) + res.double())).abs().max() < tol * 5e-5, (B, H, W, Cin, Cout, up, tol)
 
 
+def test_f32_gemm_and_conv_equal_float64_on_grid_operands():
+    """csrc/f32.hip on the binary grids of tests/exact_operands.py: every partial sum is exact in fp32, and the operands are representable in
+    bf16, so the hi / lo split of the default arithmetic mode has lo = 0 -- BOTH modes (imh_debug_set(10, 1): fp32 MFMA; 0: three bf16 MFMAs
+    per product) must return the float64 statement exactly.  f32_gemm with bias and residual on ragged M and N, N = 3 and a strided W;
+    f32_conv3x3 with up, with stride 2 + pad 1, and plain"""
+    import exact_operands as exo
+    from imagharmony_amd.ctx import Ctx
+    ctx = Ctx(DEV, torch.bfloat16)
+    for mode in (1, 0):
+        ctx.lib.imh_debug_set(10, mode)
+        try:
+            for shape in exo.F32_GEMM_SHAPES:
+                x, w, b, r = (t.to(DEV) for t in exo.f32_gemm_operands(shape))
+                exo.assert_exact_in_fp32(shape[2], x, w, b, r)
+                y = ctx.f32_gemm(x, w, bias=b, residual=r)
+                exo.assert_equal(y, exo.expected(exo.gemm_statement(x, w, b, residual=r), torch.float32), f"f32_gemm {shape} mode {mode}")
+            # strided weight operand: a column slice of V^T [C, B L], one batch at a time
+            x, _, b, r = (t.to(DEV) for t in exo.f32_gemm_operands((130, 32, 128)))
+            vt = exo.grid((32, 3 * 128), exo.ACT_N, 5, torch.float32).to(DEV)
+            exo.assert_exact_in_fp32(128, x, vt[:, 128:256], b, r)
+            y = ctx.f32_gemm(x, vt[:, 128:256], bias=b, residual=r, N=32, K=128, ldw=384)
+            exo.assert_equal(y, exo.expected(exo.gemm_statement(x, vt[:, 128:256], b, residual=r), torch.float32), f"f32_gemm strided W mode {mode}")
+            for case in exo.F32_CONV_CASES:
+                B, H, W, Cin, Cout, up, stride, pad = case
+                x, w4, b, r = (t.to(DEV) for t in exo.f32_conv_operands(case))
+                exo.assert_exact_in_fp32(9 * Cin, x, w4, b, r)
+                y = ctx.f32_conv3x3(x, w4.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous(), bias=b, residual=r.view(-1, Cout), up=up, stride=stride, pad=pad)
+                ref = exo.conv_statement(x, w4, b, stride, up, pad) + r.double()
+                exo.assert_equal(y, exo.expected(ref, torch.float32), f"f32_conv3x3 {case} mode {mode}")
+        finally:
+            ctx.lib.imh_debug_set(10, 0)
+
+
 def _f32_rest(ctx):
     import torch.nn.functional as F
     for (B, HW, Cc, silu, off) in [(2, 5000, 128, True, 0.0), (1, 1024, 512, False, 300.0), (3, 70, 32, True, -40.0)]:
