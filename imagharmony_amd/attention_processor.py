@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import lib as L
 from .ctx import Ctx
+from .derived import derived
 
 HEAD_DIM = 64
 # the wave-specialised projection pair of self-attention (imh_gemm_dual variant 24128).  Off by default: measured 45.7 us per
@@ -57,22 +58,11 @@ def _b(attn_lin, ctx):
     return b.detach().contiguous()
 
 
-def _vkey(*tensors):
-    """cache key of derived (packed / folded) weights: storage address AND in-place version counter of every source tensor,
-    so load_state_dict / LoRA fuse / weight.copy_ after the first forward rebuild the derived copy instead of leaving a
-    stale one behind (the address alone does not change on an in-place update)"""
-    return tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors)
-
-
 def _packed_qk(attn, ctx):
     """[Wq; Wk] stacked so Q and K of a self-attention layer come out of ONE GEMM; cached on the module."""
-    key = (_vkey(attn.to_q.weight, attn.to_k.weight), ctx.dtype, str(ctx.device))
-    cached = getattr(attn, "_imh_qk", None)
-    if cached is None or cached[0] != key:
-        w = torch.cat([attn.to_q.weight.detach(), attn.to_k.weight.detach()], 0).to(device=ctx.device, dtype=ctx.dtype)
-        cached = (key, w.contiguous())
-        attn._imh_qk = cached
-    return cached[1]
+    wq, wk = attn.to_q.weight, attn.to_k.weight
+    return derived(attn, "_imh_qk", (wq, wk), lambda: torch.cat([wq.detach(), wk.detach()], 0).to(device=ctx.device, dtype=ctx.dtype).contiguous(),
+                   where=(ctx.dtype, str(ctx.device)))
 
 
 def fold_ln(w, norm, ctx):
@@ -85,12 +75,13 @@ def fold_ln(w, norm, ctx):
     return wg, wg.float().sum(1).contiguous(), (wf @ b).contiguous()
 
 
-def _cached(obj, name, key, make):
-    c = getattr(obj, name, None)
-    if c is None or c[0] != key:
-        c = (key, make())
-        setattr(obj, name, c)
-    return c[1]
+def _folded(attn, slot, groups, norm, ctx):
+    """per group of ``attn``'s projections -- (("to_q", "to_k"), ("to_v",)): [Wq; Wk] and Wv -- the fold_ln triple of their stacked weights
+    under LayerNorm ``norm``; cached on the module"""
+    ws = [[getattr(attn, n).weight for n in g] for g in groups]
+    return derived(attn, slot, [t for w in ws for t in w] + [norm.weight, norm.bias],
+                   lambda: tuple(fold_ln(w[0] if len(w) == 1 else torch.cat([t.detach() for t in w], 0), norm, ctx) for w in ws),
+                   where=(ctx.dtype, str(ctx.device)))
 
 
 def _check_attn(attn, hidden_states, attention_mask):
@@ -158,17 +149,13 @@ class AttnProcessor2_0(nn.Module):
             g1, g2 = dict(x=x, w=wqk), dict(x=wv, w=x, flags=L.GF_VT_PERM)
         else:
             norm = ln
-            key = (_vkey(attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, norm.weight, norm.bias), ctx.dtype, str(ctx.device))
-            fq, fv = _cached(attn, "_imh_ln_qkv", key, lambda: (
-                fold_ln(torch.cat([attn.to_q.weight.detach(), attn.to_k.weight.detach()], 0), norm, ctx),
-                fold_ln(attn.to_v.weight, norm, ctx)))
+            fq, fv = _folded(attn, "_imh_ln_qkv", (("to_q", "to_k"), ("to_v",)), norm, ctx)
             g1 = dict(x=x, w=fq[0], flags=L.GF_LN_ROW, ln=(fq[1], fq[2], norm.eps, ln_stats))
             g2 = dict(x=fv[0], w=x, flags=L.GF_VT_PERM | L.GF_LN_COL, ln=(fv[1], fv[2], norm.eps, ln_stats))
         if ln is not None and ln_stats is not None and QKV_ONE and (B * L_) % 256 == 0 and C_ % 160 == 0 and C_ in QKV_ONE_WIDTHS:
             # [Q|K|V] = LN(x) [Wq;Wk;Wv]^T as ONE wave-specialised launch of 256 x 160 tiles (M = 2048, N = 3840: 192 tiles, one
             # round); the V third leaves the kernel transposed through LDS, in the V^T layout the attention's PV operand reads
-            f3 = _cached(attn, "_imh_ln_qkv3", key, lambda: fold_ln(
-                torch.cat([attn.to_q.weight.detach(), attn.to_k.weight.detach(), attn.to_v.weight.detach()], 0), norm, ctx))
+            f3, = _folded(attn, "_imh_ln_qkv3", (("to_q", "to_k", "to_v"),), norm, ctx)
             vt = ctx.new(C_, B * L_)
             cfg3 = ctx.tuning.get((B * L_, 3 * C_, C_, 0, 1))         # (a table entry must be a wave-specialised bn = 160 variant or 23256 x 128)
             ok3 = cfg3 is not None and cfg3[2] == 1 and (B * L_) % 256 == 0 and (
@@ -282,8 +269,7 @@ class IPAttnProcessor2_0(nn.Module):
             wq, lnq = _w(attn.to_q, ctx), None
         else:       # x is the un-normalised stream; LayerNorm `ln` folded into to_q inside the fused kernel
             norm = ln
-            key = (_vkey(attn.to_q.weight, norm.weight, norm.bias), ctx.dtype, str(ctx.device))
-            fq = _cached(attn, "_imh_ln_q", key, lambda: fold_ln(attn.to_q.weight, norm, ctx))
+            fq, = _folded(attn, "_imh_ln_q", (("to_q",),), norm, ctx)
             wq, lnq = fq[0], (fq[1], fq[2], norm.eps, ln_stats)
         ao = ctx.new(B * L_, C_)
         # to_q + text attention (+ image-prompt attention + text + scale * ip) in ONE launch (csrc/xattn.hip)

@@ -11,20 +11,16 @@ surface ``SDXLPromptEncoder`` uses: ``enc(input_ids, output_hidden_states=True)`
 (quick-)GELU -> fc2 + residual, the final LayerNorm over all rows, a second row gather for the EOS pooling and, with projection, the
 bias-free text_projection GEMM.  The launch sequence is recorded once per batch size into a plan, captured into a hipGraph and replayed
 on later calls; the token ids and the EOS rows live in plan-owned int32 buffers that are refilled (validated on the host) before each
-replay.  The only thing left to transformers on the inference path is the tokenizer.
+replay.  The only thing left to transformers on the inference path is the tokenizer.  The layer stack, the packed QKV copies, the plan
+cache and the checkpoint readers are clip_tower.py's, shared with the vision tower.
 """
-import json
-import os
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
-from . import lib as L
-from .clip_vision import _Encoder, _vkey
+from .clip_tower import ACT, Tower, _Encoder, config_from_any, emit_layers, layernorm, load_directory, pack_qkv, plan_record
 from .ctx import Ctx
-
-_ACT = {"gelu": L.GF_ACT_GELU, "quick_gelu": L.GF_ACT_QGELU}
 
 
 @dataclass
@@ -54,23 +50,7 @@ class CLIPTextEncoderConfig:
     @classmethod
     def from_any(cls, cfg):
         """from a dict (config.json, possibly a full CLIP config with a ``text_config`` section) or any object with these attributes"""
-        if isinstance(cfg, cls):
-            return cls(**{f.name: getattr(cfg, f.name) for f in fields(cls)})
-        if isinstance(cfg, dict):
-            proj = cfg.get("projection_dim")
-            if "text_config" in cfg and "hidden_size" not in cfg:
-                cfg = dict(cfg["text_config"])
-                if proj is not None:
-                    cfg["projection_dim"] = proj
-            get = cfg.get
-        else:
-            get = lambda k, d=None: getattr(cfg, k, d)      # noqa: E731
-        kw = {}
-        for f in fields(cls):
-            v = get(f.name, None)
-            if v is not None:
-                kw[f.name] = type(f.default)(v)
-        return cls(**kw)
+        return config_from_any(cls, cfg, "text_config")
 
 
 def eos_positions(input_ids, eos_token_id):
@@ -133,7 +113,7 @@ class CLIPTextEncoderOutput:
         return getattr(self, i) if isinstance(i, str) else self.to_tuple()[i]
 
 
-class CLIPTextEncoder(nn.Module):
+class CLIPTextEncoder(Tower):
     def __init__(self, config=None, with_projection=False, **kw):
         super().__init__()
         self.config = CLIPTextEncoderConfig.from_any(config) if config is not None else CLIPTextEncoderConfig(**kw)
@@ -147,8 +127,6 @@ class CLIPTextEncoder(nn.Module):
         else:                           # CLIPTextModel (transformers 5.x): the tower's parts at the top level
             tm = _TextModel(cfg)
             self.embeddings, self.encoder, self.final_layer_norm = tm.embeddings, tm.encoder, tm.final_layer_norm
-        self._derived = None            # (key, dict): packed [Wq; Wk; Wv] / biases per layer
-        self._plans = {}                # batch size -> recorded plan
         self.requires_grad_(False)
 
     @property
@@ -172,23 +150,10 @@ class CLIPTextEncoder(nn.Module):
         """``config.json`` + ``model.safetensors`` or ``pytorch_model.bin`` of a saved ``CLIPTextModel`` / ``CLIPTextModelWithProjection``
         directory, written by transformers 4.x or 5.x (normalise_keys).  with_projection=None: as the checkpoint (it has a
         ``text_projection.weight`` or not)."""
-        with open(os.path.join(path, "config.json")) as f:
-            cfg = CLIPTextEncoderConfig.from_any(json.load(f))
-        st = os.path.join(path, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st, device="cpu")
-        elif os.path.exists(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
-        else:
-            raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin")
-        if with_projection is None:
-            with_projection = "text_projection.weight" in sd
-        enc = cls(cfg, with_projection=with_projection)
-        enc.load_state_dict(normalise_keys(sd, with_projection), strict=True)
-        if device is not None or dtype is not None:
-            enc.to(device=device, dtype=dtype)
-        return enc
+        def make(cfg, sd):
+            proj = "text_projection.weight" in sd if with_projection is None else with_projection
+            return cls(CLIPTextEncoderConfig.from_any(cfg), with_projection=proj), normalise_keys(sd, proj)
+        return load_directory(path, make, device, dtype)
 
     @property
     def dtype(self):
@@ -199,29 +164,15 @@ class CLIPTextEncoder(nn.Module):
         return self.tower.embeddings.token_embedding.weight.device
 
     # ------------------------------------------------------------------ derived caches
-    def derived(self, key=None):
-        """per layer ``wqkv`` [3 hidden, hidden] = [Wq; Wk; Wv] and ``bqkv``, rebuilt when any parameter changes (loaded, moved, cast or
-        modified in place)"""
-        key = key if key is not None else self._weights_key()
-        if self._derived is None or self._derived[0] != key:
-            with torch.no_grad():
-                d = dict(wqkv=[], bqkv=[])
-                for ly in self.tower.encoder.layers:
-                    a = ly.self_attn
-                    d["wqkv"].append(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).detach().contiguous())
-                    d["bqkv"].append(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).detach().contiguous())
-            self._derived = (key, d)
-            self._plans = {}
-        return self._derived[1]
-
-    def _weights_key(self):
-        return _vkey(*self.parameters())
+    def _pack(self):
+        """per layer ``wqkv`` [3 hidden, hidden] = [Wq; Wk; Wv] and ``bqkv`` (Tower.derived)"""
+        return pack_qkv(self.tower.encoder.layers)
 
     # ------------------------------------------------------------------ forward
     def _refuse(self, input_ids, attention_mask, position_ids, output_attentions):
         """-> the ids on the host (int64 [B, L]); every refusal comes before a Ctx exists"""
         cfg = self.config
-        if cfg.hidden_act not in _ACT:
+        if cfg.hidden_act not in ACT:
             raise NotImplementedError(f"CLIPTextEncoder: hidden_act={cfg.hidden_act!r} is not implemented ('gelu' or 'quick_gelu')")
         hd = cfg.hidden_size // cfg.num_attention_heads
         if hd % 8 or hd > 128:
@@ -246,47 +197,25 @@ class CLIPTextEncoder(nn.Module):
             raise ValueError(f"CLIPTextEncoder: token ids span [{lo}, {hi}], the vocabulary is [0, {cfg.vocab_size})")
         return ids
 
-    def _record(self, B, Ls):
-        """record one forward at batch size B, sequence length Ls -> dict(ctx, ids / eos (int32 index buffers), hidden (list of
-        [B*Ls, hidden]), last, pooled, embeds)"""
+    def _record(self, B, Ls, ctx=None):
+        """record one forward at batch size B, sequence length Ls (into ``ctx``: a recording context of the caller's, e.g. a dry one) ->
+        dict(ctx, ids / eos (int32 index buffers), hidden (list of [B*Ls, hidden]), last, pooled, embeds, Ls)"""
         cfg, tm, d = self.config, self.tower, self.derived()
-        hid, heads = cfg.hidden_size, cfg.num_attention_heads
-        hd = hid // heads
-        act = _ACT[cfg.hidden_act]
-        ctx = Ctx(self.device, self.dtype, record=True)
-        M = B * Ls
-        ids = ctx.zeros(M, dtype=torch.int32)          # token ids, row b * Ls + l; refilled before every replay
+        heads = cfg.num_attention_heads
+        ctx = ctx or Ctx(self.device, self.dtype, record=True)
+        ids = ctx.zeros(B * Ls, dtype=torch.int32)     # token ids, row b * Ls + l; refilled before every replay
         eos = ctx.zeros(B, dtype=torch.int32)          # b * Ls + eos position of row b; likewise
         x = ctx.gather_rows(tm.embeddings.token_embedding.weight.detach(), ids,
                             add=tm.embeddings.position_embedding.weight.detach()[:Ls], descr="clip_text.embed")
-        ln = lambda norm, t, descr: ctx.layernorm(t, norm.weight.detach(), norm.bias.detach(), norm.eps, descr=descr)      # noqa: E731
-        hidden = [x]
-        for i, ly in enumerate(tm.encoder.layers):
-            ctx.tag = 1 + i
-            t = ln(ly.layer_norm1, x, "clip_text.ln1")
-            qkv = ctx.gemm(t, d["wqkv"][i], bias=d["bqkv"][i], descr="clip_text.qkv")
-            ctx.free(t)
-            o = ctx.attention_enc(qkv[:, :hid], qkv[:, hid:2 * hid], qkv[:, 2 * hid:], B, heads, Ls, hd, causal=True, descr="clip_text.attn")
-            ctx.free(qkv)
-            a = ly.self_attn.out_proj
-            x1 = ctx.gemm(o, a.weight.detach(), bias=a.bias.detach(), residual=x, descr="clip_text.out_proj")
-            ctx.free(o)
-            t = ln(ly.layer_norm2, x1, "clip_text.ln2")
-            f = ctx.gemm(t, ly.mlp.fc1.weight.detach(), bias=ly.mlp.fc1.bias.detach(), flags=act, descr="clip_text.fc1")
-            ctx.free(t)
-            x = ctx.gemm(f, ly.mlp.fc2.weight.detach(), bias=ly.mlp.fc2.bias.detach(), residual=x1, descr="clip_text.fc2")
-            ctx.free(f)
-            ctx.free(x1)
-            hidden.append(x)                           # every layer's output stays live: hidden_states
+        hidden = emit_layers(ctx, tm.encoder.layers, d["wqkv"], d["bqkv"], x, B, heads, Ls, cfg.hidden_size // heads, ACT[cfg.hidden_act],
+                             causal=True, pre="clip_text.")
         ctx.tag = 99
-        last = ln(tm.final_layer_norm, x, "clip_text.final_layer_norm")
+        last = layernorm(ctx, tm.final_layer_norm, hidden[-1], "clip_text.final_layer_norm")
         pooled = ctx.gather_rows(last, eos, descr="clip_text.eos_pool")
         embeds = None
         if self.with_projection:
             embeds = ctx.gemm(pooled, self.text_projection.weight.detach(), descr="clip_text.text_projection")
-        if os.environ.get("IMH_GRAPHED", "1") != "0":
-            ctx.capture()
-        return dict(ctx=ctx, ids=ids, eos=eos, hidden=hidden, last=last, pooled=pooled, embeds=embeds, L=Ls, key=self._weights_key())
+        return plan_record(ctx, ids=ids, eos=eos, hidden=hidden, last=last, pooled=pooled, embeds=embeds, Ls=Ls)
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, output_attentions=False, output_hidden_states=False, **_):
@@ -296,11 +225,7 @@ class CLIPTextEncoder(nn.Module):
         hid = cfg.hidden_size
         rows = torch.arange(B, dtype=torch.int64) * Ls + eos_positions(ids, cfg.eos_token_id)      # < B * Ls by construction
         with torch.inference_mode(False):       # the plan's buffers outlive this call: normal tensors, also under inference_mode callers
-            key = self._weights_key()
-            self.derived(key)
-            plan = self._plans.get(B)
-            if plan is None or plan["key"] != key or plan["L"] != Ls:
-                plan = self._plans[B] = self._record(B, Ls)
+            plan = self._plan(B, Ls=Ls)
             plan["ids"].copy_(ids.reshape(-1).to(torch.int32))
             plan["eos"].copy_(rows.to(torch.int32))
             plan["ctx"].replay()

@@ -9,17 +9,17 @@ surface the adapters and the judge use: ``enc(pixel_values[, output_hidden_state
 ``forward`` issues launches of libimh_hip.so only: the patch embedding as a GEMM over the 14 x 14 x 3 patches (the im2col is a
 torch view / reshape, K = 588 zero-padded to a multiple of 64), LayerNorm launches, one [Wq; Wk; Wv] GEMM per layer,
 ``imh_attention_enc`` straight on the packed QKV buffer, and the bias / erf-GELU / residual epilogues of ``imh_gemm``.  The launch
-sequence is recorded once per batch size into a plan, captured into a hipGraph and replayed on later calls.
+sequence is recorded once per batch size into a plan, captured into a hipGraph and replayed on later calls.  The layer stack, the packed
+QKV copies, the plan cache and the checkpoint readers are clip_tower.py's, shared with the text towers.
 """
-import json
-import os
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
 from . import lib as L
+from .clip_tower import Tower, _Encoder, config_from_any, emit_layers, layernorm, load_directory, pack_qkv, plan_record
 from .ctx import Ctx
 
 
@@ -49,23 +49,7 @@ class CLIPVisionEncoderConfig:
     @classmethod
     def from_any(cls, cfg):
         """from a dict (config.json, possibly a full CLIP config with a ``vision_config`` section) or any object with these attributes"""
-        if isinstance(cfg, cls):
-            return cls(**{f.name: getattr(cfg, f.name) for f in fields(cls)})
-        if isinstance(cfg, dict):
-            proj = cfg.get("projection_dim")
-            if "vision_config" in cfg and "hidden_size" not in cfg:
-                cfg = dict(cfg["vision_config"])
-                if proj is not None:
-                    cfg["projection_dim"] = proj
-            get = cfg.get
-        else:
-            get = lambda k, d=None: getattr(cfg, k, d)      # noqa: E731
-        kw = {}
-        for f in fields(cls):
-            v = get(f.name, None)
-            if v is not None:
-                kw[f.name] = type(f.default)(v)
-        return cls(**kw)
+        return config_from_any(cls, cfg, "vision_config")
 
 
 class _Embeddings(nn.Module):
@@ -77,35 +61,6 @@ class _Embeddings(nn.Module):
         self.position_embedding = nn.Embedding(n, cfg.hidden_size)
 
 
-class _Attention(nn.Module):
-    def __init__(self, cfg):
-        super().__init__()
-        h = cfg.hidden_size
-        self.k_proj, self.v_proj, self.q_proj, self.out_proj = nn.Linear(h, h), nn.Linear(h, h), nn.Linear(h, h), nn.Linear(h, h)
-
-
-class _MLP(nn.Module):
-    def __init__(self, cfg):
-        super().__init__()
-        self.fc1 = nn.Linear(cfg.hidden_size, cfg.intermediate_size)
-        self.fc2 = nn.Linear(cfg.intermediate_size, cfg.hidden_size)
-
-
-class _Layer(nn.Module):
-    def __init__(self, cfg):
-        super().__init__()
-        self.self_attn = _Attention(cfg)
-        self.layer_norm1 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
-        self.mlp = _MLP(cfg)
-        self.layer_norm2 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
-
-
-class _Encoder(nn.Module):
-    def __init__(self, cfg):
-        super().__init__()
-        self.layers = nn.ModuleList([_Layer(cfg) for _ in range(cfg.num_hidden_layers)])
-
-
 class _VisionModel(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -115,11 +70,7 @@ class _VisionModel(nn.Module):
         self.post_layernorm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
 
-def _vkey(*ts):
-    return tuple((t.data_ptr(), t._version, t.dtype, str(t.device)) for t in ts)
-
-
-class CLIPVisionEncoder(nn.Module):
+class CLIPVisionEncoder(Tower):
     def __init__(self, config=None, **kw):
         super().__init__()
         self.config = CLIPVisionEncoderConfig.from_any(config) if config is not None else CLIPVisionEncoderConfig(**kw)
@@ -128,8 +79,6 @@ class CLIPVisionEncoder(nn.Module):
             raise ValueError("hidden_size must divide by num_attention_heads and image_size by patch_size")
         self.vision_model = _VisionModel(cfg)
         self.visual_projection = nn.Linear(cfg.hidden_size, cfg.projection_dim, bias=False)
-        self._derived = None        # (key, dict): packed [Wq; Wk; Wv] / biases per layer, padded patch weight, class + position row
-        self._plans = {}            # batch size -> recorded plan
         self.requires_grad_(False)
 
     # ------------------------------------------------------------------ construction
@@ -145,21 +94,9 @@ class CLIPVisionEncoder(nn.Module):
     @classmethod
     def from_pretrained(cls, path, device=None, dtype=None):
         """``config.json`` + ``model.safetensors`` or ``pytorch_model.bin`` of a saved ``CLIPVisionModelWithProjection`` directory"""
-        with open(os.path.join(path, "config.json")) as f:
-            enc = cls(CLIPVisionEncoderConfig.from_any(json.load(f)))
-        st = os.path.join(path, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st, device="cpu")
-        elif os.path.exists(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
-        else:
-            raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin")
-        sd = {k: v for k, v in sd.items() if not k.endswith("embeddings.position_ids")}      # a buffer older checkpoints persist
-        enc.load_state_dict(sd, strict=True)
-        if device is not None or dtype is not None:
-            enc.to(device=device, dtype=dtype)
-        return enc
+        def make(cfg, sd):      # embeddings.position_ids: a buffer older checkpoints persist
+            return cls(CLIPVisionEncoderConfig.from_any(cfg)), {k: v for k, v in sd.items() if not k.endswith("embeddings.position_ids")}
+        return load_directory(path, make, device, dtype)
 
     @property
     def dtype(self):
@@ -176,32 +113,17 @@ class CLIPVisionEncoder(nn.Module):
     # ------------------------------------------------------------------ derived caches
     PATCH_K_ALIGN = 64      # imh_gemm contracts in steps of 64: 3 * 14 * 14 = 588 -> 640
 
-    def derived(self, key=None):
-        """packed / padded copies of the weights, rebuilt when any parameter changes (loaded, moved, cast or modified in place): per layer
-        ``wqkv`` [3 hidden, hidden] = [Wq; Wk; Wv] and ``bqkv``; ``patch_w`` [hidden, K'] (K = 3 p p zero-padded to a multiple of 64);
-        ``cls_pos`` = class embedding + position row 0"""
-        vm = self.vision_model
-        key = key if key is not None else self._weights_key()
-        if self._derived is None or self._derived[0] != key:
-            with torch.no_grad():
-                pw = vm.embeddings.patch_embedding.weight.detach()
-                k = pw[0].numel()
-                kp = (k + self.PATCH_K_ALIGN - 1) // self.PATCH_K_ALIGN * self.PATCH_K_ALIGN
-                patch_w = pw.new_zeros(pw.shape[0], kp)
-                patch_w[:, :k] = pw.reshape(pw.shape[0], k)
-                d = dict(patch_w=patch_w, patch_k=k,
-                         cls_pos=(vm.embeddings.class_embedding.detach() + vm.embeddings.position_embedding.weight.detach()[0]).contiguous(),
-                         wqkv=[], bqkv=[])
-                for ly in vm.encoder.layers:
-                    a = ly.self_attn
-                    d["wqkv"].append(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).detach().contiguous())
-                    d["bqkv"].append(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).detach().contiguous())
-            self._derived = (key, d)
-            self._plans = {}
-        return self._derived[1]
-
-    def _weights_key(self):
-        return _vkey(*self.parameters())
+    def _pack(self):
+        """packed / padded copies of the weights (Tower.derived): per layer ``wqkv`` [3 hidden, hidden] = [Wq; Wk; Wv] and ``bqkv``;
+        ``patch_w`` [hidden, K'] (K = 3 p p zero-padded to a multiple of 64); ``cls_pos`` = class embedding + position row 0"""
+        emb = self.vision_model.embeddings
+        pw = emb.patch_embedding.weight.detach()
+        k = pw[0].numel()
+        kp = (k + self.PATCH_K_ALIGN - 1) // self.PATCH_K_ALIGN * self.PATCH_K_ALIGN
+        patch_w = pw.new_zeros(pw.shape[0], kp)
+        patch_w[:, :k] = pw.reshape(pw.shape[0], k)
+        return dict(patch_w=patch_w, patch_k=k, cls_pos=(emb.class_embedding.detach() + emb.position_embedding.weight.detach()[0]).contiguous(),
+                    **pack_qkv(self.vision_model.encoder.layers))
 
     # ------------------------------------------------------------------ forward
     def _refuse(self, pixel_values, interpolate_pos_encoding, output_attentions):
@@ -217,47 +139,36 @@ class CLIPVisionEncoder(nn.Module):
             raise NotImplementedError(f"CLIPVisionEncoder: pixel_values {tuple(pixel_values.shape)} must be [B, 3, {cfg.image_size}, "
                                       f"{cfg.image_size}] (config.image_size; no position interpolation)")
 
-    def _record(self, B):
-        """record one forward at batch size B -> dict(ctx, patches (input buffer), hidden (list of [B*n, hidden]), embeds)"""
+    def _record(self, B, ctx=None):
+        """record one forward at batch size B (into ``ctx``: a recording context of the caller's, e.g. a dry one) -> dict(ctx, patches
+        (input buffer), hidden (list of [B*n, hidden]), embeds)"""
         cfg, vm, d = self.config, self.vision_model, self.derived()
         hid, heads, n, npatch = cfg.hidden_size, cfg.num_attention_heads, self.num_positions, self.num_positions - 1
-        hd = hid // heads
-        ctx = Ctx(self.device, self.dtype, record=True)
-        M = B * n
+        ctx = ctx or Ctx(self.device, self.dtype, record=True)
         patches = ctx.zeros(B * npatch, d["patch_w"].shape[1])         # im2col rows; the K padding stays zero
-        emb = ctx.new(M, hid)
+        emb = ctx.new(B * n, hid)
         pos = vm.embeddings.position_embedding.weight.detach()
         emb.view(B, n, hid)[:, 0] = d["cls_pos"]                       # class token + position 0: the same for every image and call
         for b in range(B):                                             # patch rows of image b + their position rows, in the epilogue
             ctx.gemm(patches[b * npatch:(b + 1) * npatch], d["patch_w"], out=emb[b * n + 1:(b + 1) * n], residual=pos[1:],
                      descr="clip.patch_embed")
-        ln = lambda norm, x, descr: ctx.layernorm(x, norm.weight.detach(), norm.bias.detach(), norm.eps, descr=descr)      # noqa: E731
-        x = ln(vm.pre_layrnorm, emb, "clip.pre_layrnorm")
-        hidden = [x]
-        for i, ly in enumerate(vm.encoder.layers):
-            ctx.tag = 1 + i
-            t = ln(ly.layer_norm1, x, "clip.ln1")
-            qkv = ctx.gemm(t, d["wqkv"][i], bias=d["bqkv"][i], descr="clip.qkv")
-            ctx.free(t)
-            o = ctx.attention_enc(qkv[:, :hid], qkv[:, hid:2 * hid], qkv[:, 2 * hid:], B, heads, n, hd, descr="clip.attn")
-            ctx.free(qkv)
-            a = ly.self_attn.out_proj
-            x1 = ctx.gemm(o, a.weight.detach(), bias=a.bias.detach(), residual=x, descr="clip.out_proj")
-            ctx.free(o)
-            t = ln(ly.layer_norm2, x1, "clip.ln2")
-            f = ctx.gemm(t, ly.mlp.fc1.weight.detach(), bias=ly.mlp.fc1.bias.detach(), flags=L.GF_ACT_GELU, descr="clip.fc1")
-            ctx.free(t)
-            x = ctx.gemm(f, ly.mlp.fc2.weight.detach(), bias=ly.mlp.fc2.bias.detach(), residual=x1, descr="clip.fc2")
-            ctx.free(f)
-            ctx.free(x1)
-            hidden.append(x)                                           # every layer's output stays live: hidden_states
+        x = layernorm(ctx, vm.pre_layrnorm, emb, "clip.pre_layrnorm")
+        hidden = emit_layers(ctx, vm.encoder.layers, d["wqkv"], d["bqkv"], x, B, heads, n, hid // heads, L.GF_ACT_GELU, causal=False, pre="clip.")
         ctx.tag = 99
         # post_layernorm is per row: normalise every row, project the class rows (row stride n * hidden)
-        pl = ln(vm.post_layernorm, x, "clip.post_layernorm")
+        pl = layernorm(ctx, vm.post_layernorm, hidden[-1], "clip.post_layernorm")
         embeds = ctx.gemm(pl.view(B, n * hid)[:, :hid], self.visual_projection.weight.detach(), descr="clip.visual_projection")
-        if os.environ.get("IMH_GRAPHED", "1") != "0":
-            ctx.capture()
-        return dict(ctx=ctx, patches=patches, hidden=hidden, embeds=embeds, key=self._weights_key())
+        return plan_record(ctx, patches=patches, hidden=hidden, embeds=embeds)
+
+    def _replay(self, plan, B, output_hidden_states):
+        """replay a plan whose ``patches`` are filled -> the output object (clones: the next call overwrites the plan's buffers)"""
+        n, hid = self.num_positions, self.config.hidden_size
+        plan["ctx"].replay()
+        out = SimpleNamespace(image_embeds=plan["embeds"].clone(), last_hidden_state=plan["hidden"][-1].view(B, n, hid).clone(),
+                              hidden_states=None, attentions=None)
+        if output_hidden_states:
+            out.hidden_states = tuple(h.view(B, n, hid).clone() for h in plan["hidden"])
+        return out
 
     @torch.no_grad()
     def forward(self, pixel_values, output_hidden_states=False, interpolate_pos_encoding=False, output_attentions=False, **_):
@@ -267,23 +178,12 @@ class CLIPVisionEncoder(nn.Module):
                              f"{self.device} / {self.dtype}")
         cfg = self.config
         B, p, g = pixel_values.shape[0], cfg.patch_size, cfg.image_size // cfg.patch_size
-        n, hid = self.num_positions, cfg.hidden_size
         with torch.inference_mode(False):       # the plan's buffers outlive this call: normal tensors, also under inference_mode callers
-            key = self._weights_key()
-            d = self.derived(key)
-            plan = self._plans.get(B)
-            if plan is None or plan["key"] != key:
-                plan = self._plans[B] = self._record(B)
+            plan = self._plan(B)
             # im2col as a view: [B, 3, g, p, g, p] -> [B, g, g, 3, p, p] = one row of 3 p p per patch, Conv2d's weight order
             rows = pixel_values.detach().reshape(B, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, 3 * p * p)
-            plan["patches"][:, :d["patch_k"]].copy_(rows)
-            plan["ctx"].replay()
-            out = SimpleNamespace(image_embeds=plan["embeds"].clone(),
-                                  last_hidden_state=plan["hidden"][-1].view(B, n, hid).clone(),
-                                  hidden_states=None, attentions=None)
-            if output_hidden_states:
-                out.hidden_states = tuple(h.view(B, n, hid).clone() for h in plan["hidden"])
-        return out
+            plan["patches"][:, :3 * p * p].copy_(rows)
+            return self._replay(plan, B, output_hidden_states)
 
     @torch.no_grad()
     def embed_decoded(self, images, output_hidden_states=False):
@@ -299,22 +199,12 @@ class CLIPVisionEncoder(nn.Module):
             raise NotImplementedError(f"CLIPVisionEncoder.embed_decoded: images {tuple(images.shape)} must be [S, 3, H, W]")
         if images.device != self.device or images.dtype != torch.float32:
             raise L.ImhError(f"CLIPVisionEncoder.embed_decoded: images on {images.device} / {images.dtype}, expected {self.device} / torch.float32")
-        B, n, hid = images.shape[0], self.num_positions, cfg.hidden_size
+        B = images.shape[0]
         with torch.inference_mode(False):
-            key = self._weights_key()
-            self.derived(key)
-            plan = self._plans.get(B)
-            if plan is None or plan["key"] != key:
-                plan = self._plans[B] = self._record(B)
+            plan = self._plan(B)
             eager = self.__dict__.get("_eager")          # one eager context for the encoder's life, not one per preview group
             if eager is None or eager.device != self.device or eager.dtype != self.dtype:
                 eager = self.__dict__["_eager"] = Ctx(self.device, self.dtype)
             eager.clip_preprocess(images.detach().contiguous(), plan["patches"], cfg.image_size, cfg.patch_size, CLIP_MEAN, CLIP_STD,
                                   descr="clip.preprocess")
-            plan["ctx"].replay()
-            out = SimpleNamespace(image_embeds=plan["embeds"].clone(),
-                                  last_hidden_state=plan["hidden"][-1].view(B, n, hid).clone(),
-                                  hidden_states=None, attentions=None)
-            if output_hidden_states:
-                out.hidden_states = tuple(h.view(B, n, hid).clone() for h in plan["hidden"])
-        return out
+            return self._replay(plan, B, output_hidden_states)

@@ -12,7 +12,7 @@ starts from the snapshot and rounds once), U / D the ``up`` / ``down`` factors o
 rank, in fp32, and g[j] = adapter_weight * alpha / rank of the adapter that owns column j (0 when it is inactive).
 
 The kernel stores into the weights behind torch's back, so apply() bumps ``_version`` of every touched parameter -- every packed,
-folded, interleaved or stacked copy of a weight is keyed by attention_processor._vkey = (data_ptr, _version) and rebuilds itself -- and
+folded, interleaved or stacked copy of a weight is keyed by derived.vkey = (data_ptr, _version) and rebuilds itself (derived.py) -- and
 increments ``unet.lora_epoch``, which DenoiseEngine compares with the value it saw at set_conditioning (its K / V caches, aug_emb,
 time-embedding rows and recorded plans derive from the weights).
 

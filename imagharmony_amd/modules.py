@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from . import lib as L
 from .ctx import Ctx
+from .derived import vkey
 
 
 def _ctx_for(t):
@@ -47,7 +48,7 @@ class Graphed:
         if not xs or any((not torch.is_tensor(x)) or x.device.type != "cuda" for x in xs) or os.environ.get("IMH_GRAPHED", "1") == "0":
             return self.module(*xs)
         key = tuple((tuple(x.shape), x.dtype, x.device.index) for x in xs) + \
-            tuple((t.data_ptr(), t._version) for t in list(self.module.parameters()) + list(self.module.buffers()))
+            vkey(*self.module.parameters(), *self.module.buffers())
         ent = self._cache.get(key)
         if ent is None:
             dev = xs[0].device

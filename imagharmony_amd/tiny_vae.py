@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import _vkey
+from .derived import derived
 
 
 class TinyVAEConfig:
@@ -44,14 +44,11 @@ class _Conv(nn.Conv2d):
 
     def packed(self, ctx):
         """-> ([Cout, 9 Cin] with K index = (ky * 3 + kx) * Cin + c, bias [Cout] or None) in the context's dtype"""
-        key = (_vkey(self.weight, self.bias), ctx.dtype, str(ctx.device))
-        c = getattr(self, "_imh_packed", None)
-        if c is None or c[0] != key:
+        def build():
             w = self.weight.detach().permute(0, 2, 3, 1).reshape(self.weight.shape[0], -1)
             b = None if self.bias is None else self.bias.detach().to(device=ctx.device, dtype=ctx.dtype).contiguous()
-            c = (key, w.to(device=ctx.device, dtype=ctx.dtype).contiguous(), b)
-            self._imh_packed = c
-        return c[1], c[2]
+            return w.to(device=ctx.device, dtype=ctx.dtype).contiguous(), b
+        return derived(self, "_imh_packed", (self.weight, self.bias), build, where=(ctx.dtype, str(ctx.device)))
 
 
 class _Block(nn.Module):

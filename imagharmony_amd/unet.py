@@ -26,8 +26,9 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import AttnProcessor2_0, CNAttnProcessor2_0, IPAttnProcessor2_0, _b, _vkey, _w, fold_ln
+from .attention_processor import AttnProcessor2_0, CNAttnProcessor2_0, IPAttnProcessor2_0, _b, _w, fold_ln
 from .ctx import Ctx, GnSpec
+from .derived import derived
 from .lora import LoRAMixin
 
 
@@ -141,21 +142,16 @@ class Conv2d(nn.Module):
 
     def packed(self, ctx):
         """[Cout, Cin, k, k] -> [Cout, k*k*Cin] (K index = (ky*k+kx)*Cin + c), cached."""
-        key = (_vkey(self.weight), ctx.dtype, str(ctx.device))
-        c = getattr(self, "_imh_packed", None)
-        if c is None or c[0] != key:
+        def build():
             w = self.weight.detach().permute(0, 2, 3, 1).reshape(self.weight.shape[0], -1)
-            c = (key, w.to(device=ctx.device, dtype=ctx.dtype).contiguous())
-            self._imh_packed = c
-        return c[1]
+            return w.to(device=ctx.device, dtype=ctx.dtype).contiguous()
+        return derived(self, "_imh_packed", (self.weight,), build, where=(ctx.dtype, str(ctx.device)))
 
     def packed_padded(self, ctx, pad_out=True):
         """-> (packed [Cout', k*k * Cin'], bias [Cout']) with Cin' (and Cout' unless pad_out is False) zero-padded to a multiple of 64, so
         a conv over a few channels runs on the implicit-GEMM kernel: the padded output channels are exact zeros, silu(0) = 0, so a chain
         of such convs stays what the unpadded convs give.  Cached."""
-        key = (_vkey(self.weight, self.bias), ctx.dtype, str(ctx.device), pad_out)
-        c = getattr(self, "_imh_padded", None)
-        if c is None or c[0] != key:
+        def build():
             w = self.weight.detach()
             co, ci = w.shape[:2]
             cop, cip = ((co + 63) // 64 * 64 if pad_out else co), (ci + 63) // 64 * 64
@@ -163,21 +159,15 @@ class Conv2d(nn.Module):
             wp[:co, :ci] = w
             bp = torch.zeros(cop, dtype=w.dtype, device=w.device)
             bp[:co] = self.bias.detach()
-            c = (key, wp.permute(0, 2, 3, 1).reshape(cop, -1).to(device=ctx.device, dtype=ctx.dtype).contiguous(),
-                 bp.to(device=ctx.device, dtype=ctx.dtype))
-            self._imh_padded = c
-        return c[1], c[2]
+            return wp.permute(0, 2, 3, 1).reshape(cop, -1).to(device=ctx.device, dtype=ctx.dtype).contiguous(), bp.to(device=ctx.device, dtype=ctx.dtype)
+        return derived(self, "_imh_padded", (self.weight, self.bias), build, where=(ctx.dtype, str(ctx.device)), extra=(pad_out,))
 
     def packed_phase(self, ctx):
         """the 3 x 3 weight of an upsampler conv in the phase form of Ctx.conv3x3(up=2): [4 * Cout, 4 * Cin], pre-summed in fp32 from
         the stored weight and rounded once to the model dtype (ctx.phase_pack), cached."""
         from .ctx import phase_pack
-        key = (_vkey(self.weight), ctx.dtype, str(ctx.device))
-        c = getattr(self, "_imh_packed_phase", None)
-        if c is None or c[0] != key:
-            c = (key, phase_pack(self.weight).to(device=ctx.device, dtype=ctx.dtype).contiguous())
-            self._imh_packed_phase = c
-        return c[1]
+        return derived(self, "_imh_packed_phase", (self.weight,), lambda: phase_pack(self.weight).to(device=ctx.device, dtype=ctx.dtype).contiguous(),
+                       where=(ctx.dtype, str(ctx.device)))
 
 
 class Norm(nn.Module):
@@ -241,29 +231,22 @@ class GEGLU(nn.Module):
 
     def packed(self, ctx):
         """rows interleaved in (value, value, gate, gate) quads (geglu_interleave; GF_GEGLU epilogue)."""
-        key = (_vkey(self.proj.weight, self.proj.bias), ctx.dtype, str(ctx.device))
-        c = getattr(self, "_imh_packed", None)
-        if c is None or c[0] != key:
+        def build():
             w, b = self.proj.weight.detach(), self.proj.bias.detach()
             wi, bi = geglu_interleave(w), geglu_interleave(b)
-            c = (key, wi.to(device=ctx.device, dtype=ctx.dtype).contiguous(),
-                 bi.to(device=ctx.device, dtype=ctx.dtype).contiguous())
-            self._imh_packed = c
-        return c[1], c[2]
+            return wi.to(device=ctx.device, dtype=ctx.dtype).contiguous(), bi.to(device=ctx.device, dtype=ctx.dtype).contiguous()
+        return derived(self, "_imh_packed", (self.proj.weight, self.proj.bias), build, where=(ctx.dtype, str(ctx.device)))
 
     def packed_ln(self, ctx, norm):
         """GEGLU projection with LayerNorm folded in (see attention_processor.fold_ln), rows interleaved in quads (geglu_interleave)."""
-        key = (_vkey(self.proj.weight, self.proj.bias, norm.weight, norm.bias), ctx.dtype, str(ctx.device))
-        c = getattr(self, "_imh_packed_ln", None)
-        if c is None or c[0] != key:
+        def build():
             wg, s, cc = fold_ln(self.proj.weight, norm, ctx)
             il = geglu_interleave
             # the Linear's bias rides in the fold's constant term, c = W beta + b (fp32): one epilogue operand (and twenty live
             # registers per lane of the 256 x 160 kernel's epilogue) less than a separate bias vector
             b = self.proj.bias.detach().to(device=ctx.device, dtype=torch.float32)
-            c = (key, il(wg), None, il(s), il(cc + b))
-            self._imh_packed_ln = c
-        return c[1], c[2], c[3], c[4]
+            return il(wg), None, il(s), il(cc + b)
+        return derived(self, "_imh_packed_ln", (self.proj.weight, self.proj.bias, norm.weight, norm.bias), build, where=(ctx.dtype, str(ctx.device)))
 
 
 class FeedForward(nn.Module):
@@ -638,14 +621,12 @@ class UNetEncoderModel(nn.Module):
 
     # ---- packed / stacked weights ----
     def _temb_stack(self, ctx):
-        key = (_vkey(*[t for r in self.resnets() for t in (r.time_emb_proj.weight, r.time_emb_proj.bias)]), ctx.dtype, str(ctx.device))
-        c = getattr(self, "_imh_temb", None)
-        if c is None or c[0] != key:
-            w = torch.cat([r.time_emb_proj.weight.detach() for r in self.resnets()], 0)
-            b = torch.cat([r.time_emb_proj.bias.detach() for r in self.resnets()], 0)
-            c = (key, w.to(device=ctx.device, dtype=ctx.dtype).contiguous(), b.to(device=ctx.device, dtype=ctx.dtype))
-            self._imh_temb = c
-        return c[1], c[2]
+        lins = [r.time_emb_proj for r in self.resnets()]
+
+        def build():
+            w, b = torch.cat([p.weight.detach() for p in lins], 0), torch.cat([p.bias.detach() for p in lins], 0)
+            return w.to(device=ctx.device, dtype=ctx.dtype).contiguous(), b.to(device=ctx.device, dtype=ctx.dtype)
+        return derived(self, "_imh_temb", [t for p in lins for t in (p.weight, p.bias)], build, where=(ctx.dtype, str(ctx.device)))
 
     def _temb_chain(self, ctx, tsin, aug):
         """time_embedding(t) + aug_emb -> SiLU -> the 17 stacked time_emb_proj Linears: [rows, 320] -> [rows, sum Cout]"""

@@ -31,8 +31,9 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .attention_processor import _b, _vkey, _w
+from .attention_processor import _b, _w
 from .ctx import Ctx
+from .derived import derived
 from .unet import Conv2d, Linear, Norm
 
 
@@ -173,32 +174,19 @@ class AutoencoderKLOutput:
 
 def _pad_1x1(conv, cpad, dtype, device):
     """a 1 x 1 conv as a [cpad, cpad] matrix and a [cpad] bias, zero-padded, cached per cpad"""
-    key = (_vkey(conv.weight, conv.bias), dtype, str(device))
-    c = getattr(conv, f"_imh_padded{cpad}", None)
-    if c is None or c[0] != key:
+    def build():
         w = conv.weight.detach().view(conv.weight.shape[0], -1)
         wp = torch.zeros(cpad, cpad, dtype=w.dtype, device=w.device)
         wp[:w.shape[0], :w.shape[1]] = w
         bp = torch.zeros(cpad, dtype=w.dtype, device=w.device)
         bp[:w.shape[0]] = conv.bias.detach()
-        c = (key, wp.to(device=device, dtype=dtype).contiguous(), bp.to(device=device, dtype=dtype))
-        setattr(conv, f"_imh_padded{cpad}", c)
-    return c[1], c[2]
-
-
-def _f32_cached(mod, name, build, *src):
-    """fp32 copy of a module's (packed / padded) parameter on the device, rebuilt when the source changes (in place or re-assigned)"""
-    key = (_vkey(*src), str(src[0].device))
-    c = getattr(mod, name, None)
-    if c is None or c[0] != key:
-        c = (key, build())
-        setattr(mod, name, c)
-    return c[1]
+        return wp.to(device=device, dtype=dtype).contiguous(), bp.to(device=device, dtype=dtype)
+    return derived(conv, f"_imh_padded{cpad}", (conv.weight, conv.bias), build, where=(dtype, str(device)), extra=(cpad,))
 
 
 def _f32_w(mod, cin_pad=0):
     """a Linear's [N, K], or a conv's [Cout, Cin, k, k] -> packed [Cout, k*k * Cin'] (K index = (ky*k+kx)*Cin' + c) with Cin zero-padded
-    to cin_pad, in fp32"""
+    to cin_pad, in fp32 where the weight lives; cached"""
     def build():
         w = mod.weight.detach().float()
         if w.dim() == 4:
@@ -208,12 +196,13 @@ def _f32_w(mod, cin_pad=0):
                 w = wp
             w = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
         return w.contiguous()
-    return _f32_cached(mod, "_imh_f32_w", build, mod.weight)
+    return derived(mod, "_imh_f32_w", (mod.weight,), build, where=(str(mod.weight.device),), extra=(cin_pad,))
 
 
 def _f32_vec(mod, attr="bias"):
+    """``mod.<attr>`` in fp32 where it lives; cached"""
     t = getattr(mod, attr)
-    return _f32_cached(mod, "_imh_f32_" + attr, lambda: t.detach().float().contiguous(), t)
+    return derived(mod, "_imh_f32_" + attr, (t,), lambda: t.detach().float().contiguous(), where=(str(t.device),))
 
 
 # ---- the two back ends: everything that differs between the compute modes; the walks below are written once against them ----

@@ -381,7 +381,7 @@ def test_derived_weight_caches_follow_in_place_updates():
     """packed / LayerNorm-folded weight copies are cached on the modules; their keys carry the in-place version counter of
     every source tensor (weight, bias, norm.weight, norm.bias), so load_state_dict / weight.copy_ after a first forward
     rebuild them -- the storage address alone does not change on an in-place update"""
-    from imagharmony_amd.attention_processor import _packed_qk, _cached, _vkey, fold_ln
+    from imagharmony_amd.attention_processor import _folded, _packed_qk
     from imagharmony_amd.ctx import Ctx
     from imagharmony_amd.unet import Attention, Conv2d, GEGLU, Norm
     ctx = Ctx("cpu", torch.bfloat16, record=True, dry=True)
@@ -396,8 +396,8 @@ def test_derived_weight_caches_follow_in_place_updates():
     w0, b0, s0, c0 = [t.clone() if t is not None else None for t in ge.packed_ln(ctx, norm)]
     assert b0 is None                    # the Linear's bias rides in the fold's constant term c = W beta + b
     cw0 = conv.packed(ctx).clone()
-    key = lambda: (_vkey(attn.to_q.weight, norm.weight, norm.bias), ctx.dtype, str(ctx.device))
-    f0 = [t.clone() for t in _cached(attn, "_imh_ln_q", key(), lambda: fold_ln(attn.to_q.weight, norm, ctx))]
+    folded_q = lambda: _folded(attn, "_imh_ln_q", (("to_q",),), norm, ctx)[0]       # noqa: E731
+    f0 = [t.clone() for t in folded_q()]
     with torch.no_grad():                 # in-place updates: same data_ptr, new version
         attn.to_q.weight.mul_(2.0)
         norm.bias.add_(1.0)
@@ -406,7 +406,7 @@ def test_derived_weight_caches_follow_in_place_updates():
     w1, b1, s1, c1 = ge.packed_ln(ctx, norm)
     assert torch.equal(w1, w0) and not torch.equal(c1, c0)                               # beta moved: c = W beta follows
     assert torch.equal(conv.packed(ctx), (cw0.float() * 0.5).to(torch.bfloat16))
-    f1 = _cached(attn, "_imh_ln_q", key(), lambda: fold_ln(attn.to_q.weight, norm, ctx))
+    f1 = folded_q()
     assert not torch.equal(f1[0], f0[0]) and not torch.equal(f1[2], f0[2])
     sd = {k: v.clone() for k, v in attn.state_dict().items()}
     qk1 = _packed_qk(attn, ctx).clone()
