@@ -148,15 +148,31 @@ static int do_gemm(const imh_gemm_args* a, hipStream_t s) {
     return gemm_launch(p, a->dtype, a->conv, bm, bn, s);
 }
 
+// the fields imh_attn_args, imh_xattn_args and imh_xattn_regions_args share under the same names; Q / ldq: the fused forms compute their queries
+// in the launch.  split and defer_log2 are the launchers' to set (imh_kernels.h)
+template <class A>
+static void fill_attn(AttnParams& p, const A* a, const void* Q, int ldq) {
+    p.Q = Q; p.K = a->K; p.Vt = a->Vt; p.K2 = a->K2; p.Vt2 = a->Vt2; p.O = a->O;
+    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.Lk_pad = a->Lk_pad; p.Lk2 = a->Lk2; p.Lk2_pad = a->Lk2_pad;
+    p.ldq = ldq; p.ldk = a->ldk; p.ldvt = a->ldvt; p.ldk2 = a->ldk2; p.ldvt2 = a->ldvt2; p.ldo = a->ldo;
+    p.scale = a->scale; p.scale2 = a->scale2; p.scale2_tab = a->scale2_tab; p.step = a->step;
+    p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes; p.split = 0; p.defer_log2 = 0.f;
+}
+
+// ... and the fused to_q of imh_xattn_args and imh_xattn_regions_args: the statistics count only under a folded LayerNorm
+template <class A>
+static void fill_xattn(XAttnParams& x, const A* a) {
+    fill_attn(x.a, a, nullptr, 0);
+    x.X = a->X; x.Wq = a->Wq; x.ln_s = a->ln_s; x.ln_c = a->ln_c; x.ln_eps = a->ln_eps;
+    x.ln_stats = a->ln_s ? a->ln_stats : nullptr; x.ln_slots = a->ln_slots;
+    x.C = a->C; x.ldx = a->ldx; x.ldw = a->ldw; x.split = 0;
+}
+
 static int do_attn(const imh_attn_args* a, hipStream_t s) {
     if (!a || !a->Q || !a->K || !a->Vt || !a->O) { set_error("attention: null pointer argument"); return IMH_ERR_ARG; }
     if ((a->K2 == nullptr) != (a->Vt2 == nullptr)) { set_error("attention: K2 and Vt2 must come together"); return IMH_ERR_ARG; }
     AttnParams p;
-    p.Q = a->Q; p.K = a->K; p.Vt = a->Vt; p.K2 = a->K2; p.Vt2 = a->Vt2; p.O = a->O;
-    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.Lk_pad = a->Lk_pad; p.Lk2 = a->Lk2; p.Lk2_pad = a->Lk2_pad;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldvt = a->ldvt; p.ldk2 = a->ldk2; p.ldvt2 = a->ldvt2; p.ldo = a->ldo;
-    p.scale = a->scale; p.scale2 = a->scale2; p.scale2_tab = a->scale2_tab; p.step = a->step;
-    p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes; p.split = 0; p.defer_log2 = 0.f;
+    fill_attn(p, a, a->Q, a->ldq);
     return attention_launch(p, a->dtype, s);
 }
 
@@ -168,16 +184,8 @@ static int do_xattn(const imh_xattn_args* a, hipStream_t s) {
     }
     if (a->C != a->H * 64) { set_error("cross_attention: C=%d must be H*64 (H=%d)", a->C, a->H); return IMH_ERR_SHAPE; }
     XAttnParams x;
-    AttnParams& p = x.a;
-    p.Q = nullptr; p.K = a->K; p.Vt = a->Vt; p.K2 = a->K2; p.Vt2 = a->Vt2; p.O = a->O;
-    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.Lk_pad = a->Lk_pad; p.Lk2 = a->Lk2; p.Lk2_pad = a->Lk2_pad;
-    p.ldq = 0; p.ldk = a->ldk; p.ldvt = a->ldvt; p.ldk2 = a->ldk2; p.ldvt2 = a->ldvt2; p.ldo = a->ldo;
-    p.scale = a->scale; p.scale2 = a->scale2; p.scale2_tab = a->scale2_tab; p.step = a->step;
-    p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes;
-    x.X = a->X; x.Wq = a->Wq; x.ln_s = a->ln_s; x.ln_c = a->ln_c; x.ln_eps = a->ln_eps;
-    x.ln_stats = a->ln_s ? a->ln_stats : nullptr; x.ln_slots = a->ln_slots;
+    fill_xattn(x, a);
     if (x.ln_stats && (a->ln_slots <= 0 || a->C % a->ln_slots)) { set_error("cross_attention: ln_slots=%d must divide C=%d", a->ln_slots, a->C); return IMH_ERR_ARG; }
-    x.C = a->C; x.ldx = a->ldx; x.ldw = a->ldw; x.split = 0;
     return xattn_launch(x, a->dtype, s);
 }
 
@@ -192,18 +200,9 @@ static int do_xattn_regions(const imh_xattn_regions_args* a, hipStream_t s) {
     if ((a->scale2_tab == nullptr) != (a->step == nullptr)) { set_error("%s: scale2_tab and step come together", who); return IMH_ERR_ARG; }
     if (a->C != a->H * 64) { set_error("%s: C=%d must be H*64 (H=%d)", who, a->C, a->H); return IMH_ERR_SHAPE; }
     XRegionParams r;
-    XAttnParams& x = r.x;
-    AttnParams& p = x.a;
-    p.Q = nullptr; p.K = a->K; p.Vt = a->Vt; p.K2 = a->K2; p.Vt2 = a->Vt2; p.O = a->O;
-    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.Lk_pad = a->Lk_pad; p.Lk2 = a->Lk2; p.Lk2_pad = a->Lk2_pad;
-    p.ldq = 0; p.ldk = a->ldk; p.ldvt = a->ldvt; p.ldk2 = a->ldk2; p.ldvt2 = a->ldvt2; p.ldo = a->ldo;
-    p.scale = a->scale; p.scale2 = a->scale2; p.scale2_tab = a->scale2_tab; p.step = a->step;
-    p.pf_ptr = a->pf_ptr; p.pf_bytes = a->pf_bytes; p.split = 0; p.defer_log2 = 0.f;
-    x.X = a->X; x.Wq = a->Wq; x.ln_s = a->ln_s; x.ln_c = a->ln_c; x.ln_eps = a->ln_eps;
-    x.ln_stats = a->ln_s ? a->ln_stats : nullptr; x.ln_slots = a->ln_slots;
+    fill_xattn(r.x, a);
     if (a->ln_s && !a->ln_stats) { set_error("%s: the folded LayerNorm takes the token rows' statistics from ln_stats", who); return IMH_ERR_ARG; }
-    if (x.ln_stats && (a->ln_slots <= 0 || a->C % a->ln_slots)) { set_error("%s: ln_slots=%d must divide C=%d", who, a->ln_slots, a->C); return IMH_ERR_ARG; }
-    x.C = a->C; x.ldx = a->ldx; x.ldw = a->ldw; x.split = 0;
+    if (r.x.ln_stats && (a->ln_slots <= 0 || a->C % a->ln_slots)) { set_error("%s: ln_slots=%d must divide C=%d", who, a->ln_slots, a->C); return IMH_ERR_ARG; }
     r.mask = a->mask; r.weights = a->weights; r.n_img = a->n_img; r.ldm = a->ldm;
     return xattn_regions_launch(r, a->dtype, s);
 }
@@ -237,14 +236,28 @@ static NormParams to_norm(const imh_norm_args* a) {
     return p;
 }
 
-static int do_ew(int op, const imh_ew_args* a, hipStream_t s) {
-    if (!a || !a->y) { set_error("elementwise: null pointer argument"); return IMH_ERR_ARG; }
+static EwParams to_ew(const imh_ew_args* a) {
     EwParams p;
     p.a = a->a; p.b = a->b; p.y = a->y; p.w = a->w; p.bias = a->bias; p.tab = a->tab; p.step = a->step; p.n = a->n;
     p.i0 = a->i0; p.i1 = a->i1; p.i2 = a->i2; p.i3 = a->i3; p.i4 = a->i4; p.i5 = a->i5;
     p.f0 = a->f0; p.f1 = a->f1; p.f2 = a->f2; p.f3 = a->f3;
     p.x2 = a->x2; p.noise = a->noise; p.mask = a->mask; p.blend_tab = a->blend_tab;
-    return ew_launch(op, p, a->dtype, s);
+    return p;
+}
+
+static int do_groupnorm(const imh_norm_args* a, hipStream_t s) {
+    if (!a) { set_error("groupnorm: null pointer argument"); return IMH_ERR_ARG; }
+    return groupnorm_launch(to_norm(a), a->dtype, s);
+}
+
+static int do_layernorm(const imh_norm_args* a, hipStream_t s) {
+    if (!a || !a->x || !a->y) { set_error("layernorm: null pointer argument"); return IMH_ERR_ARG; }
+    return layernorm_launch(to_norm(a), a->dtype, s);
+}
+
+static int do_ew(int op, const imh_ew_args* a, hipStream_t s) {
+    if (!a || !a->y) { set_error("elementwise: null pointer argument"); return IMH_ERR_ARG; }
+    return ew_launch(op, to_ew(a), a->dtype, s);
 }
 
 // imh_step_seeded: IMH_EW_CFG_MSTEP's launch with the noise generated from the seed rows (elementwise.hip cfg_mstep_kernel<.., SEEDED>)
@@ -253,14 +266,9 @@ static int do_step_seeded(const imh_seeded_args* a, hipStream_t s) {
     if (!a->seeds) { set_error("imh_step_seeded: null seeds (one uint32 row (k0, k1, lane, 0) per sample)"); return IMH_ERR_ARG; }
     if (a->ew.bias) { set_error("imh_step_seeded: bias (the noise bank of IMH_EW_CFG_MSTEP) must be NULL: the noise comes from seeds"); return IMH_ERR_ARG; }
     if ((uintptr_t)a->seeds & 3) { set_error("imh_step_seeded: seeds must be 4-byte aligned"); return IMH_ERR_ARG; }
-    const imh_ew_args* e = &a->ew;
-    EwParams p;
-    p.a = e->a; p.b = e->b; p.y = e->y; p.w = e->w; p.bias = nullptr; p.tab = e->tab; p.step = e->step; p.n = e->n;
-    p.i0 = e->i0; p.i1 = e->i1; p.i2 = e->i2; p.i3 = e->i3; p.i4 = e->i4; p.i5 = e->i5;
-    p.f0 = e->f0; p.f1 = e->f1; p.f2 = e->f2; p.f3 = e->f3;
-    p.x2 = e->x2; p.noise = e->noise; p.mask = e->mask; p.blend_tab = e->blend_tab;
+    EwParams p = to_ew(&a->ew);                  // (bias, the noise bank, is null: checked above)
     p.seeds = a->seeds; p.noise_stream = a->stream;
-    return ew_launch(IMH_EW_CFG_MSTEP, p, e->dtype, s);
+    return ew_launch(IMH_EW_CFG_MSTEP, p, a->ew.dtype, s);
 }
 
 static int to_randn(const imh_randn_args* a, const char* who, RandnParams* p) {
@@ -395,55 +403,45 @@ struct imh_plan {
     hipGraphExec_t exec = nullptr;
 };
 
+// the plan kinds: what imh_plan_add copies for each and what runs it.  A kind that is not here (12, 14 and 16 among them) is refused
+struct op_entry {
+    int kind;
+    size_t size;
+    int (*run)(const imh_op&, hipStream_t);
+};
+static const op_entry g_ops[] = {
+    {IMH_OP_GEMM, sizeof(imh_gemm_args), [](const imh_op& o, hipStream_t s) { return do_gemm(&o.u.gemm, s); }},
+    {IMH_OP_ATTN, sizeof(imh_attn_args), [](const imh_op& o, hipStream_t s) { return do_attn(&o.u.attn, s); }},
+    {IMH_OP_GROUPNORM, sizeof(imh_norm_args), [](const imh_op& o, hipStream_t s) { return do_groupnorm(&o.u.norm, s); }},
+    {IMH_OP_LAYERNORM, sizeof(imh_norm_args), [](const imh_op& o, hipStream_t s) { return do_layernorm(&o.u.norm, s); }},
+    {IMH_OP_EW, sizeof(imh_ew_args), [](const imh_op& o, hipStream_t s) { return do_ew(o.ew_op, &o.u.ew, s); }},
+    {IMH_OP_ATTN_SMALL, sizeof(imh_small_attn_args), [](const imh_op& o, hipStream_t s) { return do_attn_small(&o.u.sattn, s); }},
+    {IMH_OP_GEMM_DUAL, 2 * sizeof(imh_gemm_args), [](const imh_op& o, hipStream_t s) { return do_gemm_dual(&o.u.gemm2[0], &o.u.gemm2[1], s); }},
+    {IMH_OP_XATTN, sizeof(imh_xattn_args), [](const imh_op& o, hipStream_t s) { return do_xattn(&o.u.xattn, s); }},
+    {IMH_OP_ATTN_ENC, sizeof(imh_enc_attn_args), [](const imh_op& o, hipStream_t s) { return do_attn_enc(&o.u.eattn, s); }},
+    {IMH_OP_ATTN_ENC_CAUSAL, sizeof(imh_enc_attn_args), [](const imh_op& o, hipStream_t s) { return do_attn_enc(&o.u.eattn, s, 1); }},
+    {IMH_OP_STEP_SEEDED, sizeof(imh_seeded_args), [](const imh_op& o, hipStream_t s) { return do_step_seeded(&o.u.seeded, s); }},
+    {IMH_OP_RANDN_SEEDED, sizeof(imh_randn_args), [](const imh_op& o, hipStream_t s) { return do_randn_seeded(&o.u.randn, s); }},
+    {IMH_OP_CLIP_PREPROCESS, sizeof(imh_clip_preprocess_args), [](const imh_op& o, hipStream_t s) { return do_clip_preprocess(&o.u.clip, s); }},
+    {IMH_OP_CONTROL_ADD, sizeof(imh_control_add_args), [](const imh_op& o, hipStream_t s) { return do_control_add(&o.u.cadd, s); }},
+    {IMH_OP_XATTN_REGIONS, sizeof(imh_xattn_regions_args), [](const imh_op& o, hipStream_t s) { return do_xattn_regions(&o.u.xregions, s); }},
+};
+
+static const op_entry* find_op(int kind) {
+    for (const op_entry& e : g_ops)
+        if (e.kind == kind) return &e;
+    return nullptr;
+}
+
 static int run_op(const imh_op& o, hipStream_t s) {
-    switch (o.kind) {
-        case IMH_OP_GEMM: return do_gemm(&o.u.gemm, s);
-        case IMH_OP_ATTN: return do_attn(&o.u.attn, s);
-        case IMH_OP_GROUPNORM: return groupnorm_launch(to_norm(&o.u.norm), o.u.norm.dtype, s);
-        case IMH_OP_LAYERNORM: {
-            if (!o.u.norm.x || !o.u.norm.y) { set_error("layernorm: null pointer argument"); return IMH_ERR_ARG; }
-            return layernorm_launch(to_norm(&o.u.norm), o.u.norm.dtype, s);
-        }
-        case IMH_OP_EW: return do_ew(o.ew_op, &o.u.ew, s);
-        case IMH_OP_ATTN_SMALL: return do_attn_small(&o.u.sattn, s);
-        case IMH_OP_GEMM_DUAL: return do_gemm_dual(&o.u.gemm2[0], &o.u.gemm2[1], s);
-        case IMH_OP_XATTN: return do_xattn(&o.u.xattn, s);
-        case IMH_OP_ATTN_ENC: return do_attn_enc(&o.u.eattn, s);
-        case IMH_OP_ATTN_ENC_CAUSAL: return do_attn_enc(&o.u.eattn, s, 1);
-        case IMH_OP_STEP_SEEDED: return do_step_seeded(&o.u.seeded, s);
-        case IMH_OP_RANDN_SEEDED: return do_randn_seeded(&o.u.randn, s);
-        case IMH_OP_CLIP_PREPROCESS: return do_clip_preprocess(&o.u.clip, s);
-        case IMH_OP_CONTROL_ADD: return do_control_add(&o.u.cadd, s);
-        case IMH_OP_XATTN_REGIONS: return do_xattn_regions(&o.u.xregions, s);
-    }
-    set_error("plan: unknown op kind %d", o.kind);
-    return IMH_ERR_ARG;
+    const op_entry* e = find_op(o.kind);
+    if (!e) { set_error("plan: unknown op kind %d", o.kind); return IMH_ERR_ARG; }
+    return e->run(o, s);
 }
 
 static void drop_graph(imh_plan* p) {
     if (p->exec) { hipGraphExecDestroy(p->exec); p->exec = nullptr; }
     if (p->graph) { hipGraphDestroy(p->graph); p->graph = nullptr; }
-}
-
-static size_t args_size(int kind) {
-    switch (kind) {
-        case IMH_OP_GEMM: return sizeof(imh_gemm_args);
-        case IMH_OP_ATTN: return sizeof(imh_attn_args);
-        case IMH_OP_GROUPNORM:
-        case IMH_OP_LAYERNORM: return sizeof(imh_norm_args);
-        case IMH_OP_EW: return sizeof(imh_ew_args);
-        case IMH_OP_ATTN_SMALL: return sizeof(imh_small_attn_args);
-        case IMH_OP_GEMM_DUAL: return 2 * sizeof(imh_gemm_args);
-        case IMH_OP_XATTN: return sizeof(imh_xattn_args);
-        case IMH_OP_ATTN_ENC:
-        case IMH_OP_ATTN_ENC_CAUSAL: return sizeof(imh_enc_attn_args);
-        case IMH_OP_STEP_SEEDED: return sizeof(imh_seeded_args);
-        case IMH_OP_RANDN_SEEDED: return sizeof(imh_randn_args);
-        case IMH_OP_CLIP_PREPROCESS: return sizeof(imh_clip_preprocess_args);
-        case IMH_OP_CONTROL_ADD: return sizeof(imh_control_add_args);
-        case IMH_OP_XATTN_REGIONS: return sizeof(imh_xattn_regions_args);
-    }
-    return 0;
 }
 
 extern "C" {
@@ -520,17 +518,11 @@ int imh_attention_small(const imh_small_attn_args* a, void* stream) { return do_
 int imh_attention_enc(const imh_enc_attn_args* a, void* stream) { return do_attn_enc(a, (hipStream_t)stream); }
 int imh_attention_enc_causal(const imh_enc_attn_args* a, void* stream) { return do_attn_enc(a, (hipStream_t)stream, 1); }
 
-int imh_groupnorm(const imh_norm_args* a, void* stream) {
-    if (!a) { set_error("groupnorm: null pointer argument"); return IMH_ERR_ARG; }
-    return groupnorm_launch(to_norm(a), a->dtype, (hipStream_t)stream);
-}
+int imh_groupnorm(const imh_norm_args* a, void* stream) { return do_groupnorm(a, (hipStream_t)stream); }
 size_t imh_groupnorm_workspace_bytes(int B, int HW, int C, int groups) { return groupnorm_workspace_bytes(B, HW, C, groups); }
 int imh_groupnorm_stats_blocks(int HW, int C) { return groupnorm_stats_blocks(HW, C); }
 int imh_groupnorm_stats_sub(int C, int groups) { return groups > 0 && C % groups == 0 ? groupnorm_stats_sub(C, groups) : 0; }
-int imh_layernorm(const imh_norm_args* a, void* stream) {
-    if (!a || !a->x || !a->y) { set_error("layernorm: null pointer argument"); return IMH_ERR_ARG; }
-    return layernorm_launch(to_norm(a), a->dtype, (hipStream_t)stream);
-}
+int imh_layernorm(const imh_norm_args* a, void* stream) { return do_layernorm(a, (hipStream_t)stream); }
 
 int imh_elementwise(int op, const imh_ew_args* a, void* stream) { return do_ew(op, a, (hipStream_t)stream); }
 
@@ -567,12 +559,12 @@ void imh_plan_destroy(imh_plan* p) {
 }
 int imh_plan_add(imh_plan* p, int kind, const void* args, int ew_op, int tag) {
     if (!p || !args) { set_error("plan_add: null argument"); return IMH_ERR_ARG; }
-    const size_t sz = args_size(kind);
-    if (!sz) { set_error("plan_add: unknown kind %d", kind); return IMH_ERR_ARG; }
+    const op_entry* e = find_op(kind);
+    if (!e) { set_error("plan_add: unknown kind %d", kind); return IMH_ERR_ARG; }
     imh_op o;
     memset(&o, 0, sizeof(o));
     o.kind = kind; o.ew_op = ew_op; o.tag = tag;
-    memcpy(&o.u, args, sz);
+    memcpy(&o.u, args, e->size);
     p->ops.push_back(o);
     drop_graph(p);
     return (int)p->ops.size() - 1;
@@ -580,7 +572,7 @@ int imh_plan_add(imh_plan* p, int kind, const void* args, int ew_op, int tag) {
 int imh_plan_size(const imh_plan* p) { return p ? (int)p->ops.size() : 0; }
 int imh_plan_update(imh_plan* p, int index, const void* args) {
     if (!p || !args || index < 0 || index >= (int)p->ops.size()) { set_error("plan_update: bad index"); return IMH_ERR_ARG; }
-    memcpy(&p->ops[index].u, args, args_size(p->ops[index].kind));
+    memcpy(&p->ops[index].u, args, find_op(p->ops[index].kind)->size);          // (imh_plan_add let no other kind in)
     drop_graph(p);
     return IMH_OK;
 }

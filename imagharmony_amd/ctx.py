@@ -190,7 +190,9 @@ class Ctx:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ emit
-    def _emit(self, kind, args, ew_op=0, descr="", flops=0.0, nbytes=0.0, keep=(), shape=None, epi=None):
+    def _emit(self, kind, args, ew_op=0, descr="", flops=0.0, nbytes=0.0, keep=(), shape=None, epi=None, free=()):
+        """the one way a launch leaves Python: recorded into the plan, or handed to the eager entry point L.OPS names for its kind.
+        free: pool buffers that only this launch reads (the statistics of _ln_stats) -- returned once it is emitted"""
         if self.record:
             if kind == L.OP_GEMM and not self.dry:
                 # a launch the library refuses is refused HERE, not when the plan first runs (imh_plan_add copies the arguments unseen)
@@ -199,39 +201,14 @@ class Ctx:
             if rc < 0:
                 L.check(rc, "imh_plan_add")
             self.keep.extend(k for k in keep if k is not None)
-            self.tags.append((self.tag, kind, descr, flops, nbytes, shape, epi))
-            self._ops.append((kind, args, self._cold(keep) if kind in (L.OP_GEMM, L.OP_XATTN, L.OP_XATTN_REGIONS) else []))
-            return
-        s = self.stream()
-        if kind == L.OP_GEMM:
-            rc = self.lib.imh_gemm(C.byref(args), s)
-        elif kind == L.OP_ATTN:
-            rc = self.lib.imh_attention(C.byref(args), s)
-        elif kind == L.OP_GROUPNORM:
-            rc = self.lib.imh_groupnorm(C.byref(args), s)
-        elif kind == L.OP_LAYERNORM:
-            rc = self.lib.imh_layernorm(C.byref(args), s)
-        elif kind == L.OP_ATTN_SMALL:
-            rc = self.lib.imh_attention_small(C.byref(args), s)
-        elif kind == L.OP_XATTN:
-            rc = self.lib.imh_cross_attention(C.byref(args), s)
-        elif kind == L.OP_XATTN_REGIONS:
-            rc = self.lib.imh_cross_attention_regions(C.byref(args), s)
-        elif kind == L.OP_ATTN_ENC:
-            rc = self.lib.imh_attention_enc(C.byref(args), s)
-        elif kind == L.OP_ATTN_ENC_CAUSAL:
-            rc = self.lib.imh_attention_enc_causal(C.byref(args), s)
-        elif kind == L.OP_STEP_SEEDED:
-            rc = self.lib.imh_step_seeded(C.byref(args), s)
-        elif kind == L.OP_RANDN_SEEDED:
-            rc = self.lib.imh_randn_seeded(C.byref(args), s)
-        elif kind == L.OP_CLIP_PREPROCESS:
-            rc = self.lib.imh_clip_preprocess(C.byref(args), s)
-        elif kind == L.OP_CONTROL_ADD:
-            rc = self.lib.imh_control_add(C.byref(args), s)
+            # (a two-problem launch is tagged as the GEMMs it computes; its _ops row keeps the plan kind, which finalize_prefetch reads)
+            self.tags.append((self.tag, L.OP_GEMM if kind == L.OP_GEMM_DUAL else kind, descr, flops, nbytes, shape, epi))
+            self._ops.append((kind, args, self._cold(keep) if kind in (L.OP_GEMM, L.OP_GEMM_DUAL, L.OP_XATTN, L.OP_XATTN_REGIONS) else []))
         else:
-            rc = self.lib.imh_elementwise(ew_op, C.byref(args), s)
-        L.check(rc, descr or f"op kind {kind}")
+            _, entry, call = L.OPS[kind]
+            L.check(call(getattr(self.lib, entry), args, ew_op, self.stream()), descr or f"op kind {kind}")
+        for t in free:
+            self.free(t)
 
     @staticmethod
     def _p(t):
@@ -347,14 +324,12 @@ class Ctx:
             n_out = int(yt[1])
         if out is None:
             out = self.new(M, n_out, dtype=torch.float32 if flags & L.GF_OUT_F32 else None)
-        ln_stats = ln[3] if ln is not None and len(ln) > 3 else None
-        own_stats = False
-        if ln is not None and ln_stats is None and flags & (L.GF_LN_ROW | L.GF_LN_COL):
-            if _args_only:
+        ln_stats, own = None, ()
+        if ln is not None:
+            fold = flags & (L.GF_LN_ROW | L.GF_LN_COL)
+            ln_stats, own = self._ln_stats(ln, (lambda: (x[:M, :K] if flags & L.GF_LN_ROW else w[:N, :K])) if fold and not _args_only else None, descr)
+            if fold and ln_stats is None:
                 raise L.ImhError(f"{descr}: a folded-LayerNorm problem of gemm_dual needs its row statistics (gemm_dual supplies them)")
-            tok = x if flags & L.GF_LN_ROW else w
-            ln_stats = self.row_stats(tok[:M if flags & L.GF_LN_ROW else N, :K], descr=descr + ".ln_row_stats")
-            own_stats = True
         if stats_out and flags & L.GF_OUT_F32:
             raise L.ImhError(f"{descr}: stats_out describes rows stored in the compute dtype; an fp32 output (GF_OUT_F32) has no such statistics")
         if stats_out and gn_out is not None:
@@ -369,57 +344,34 @@ class Ctx:
             bm, bn, sp = (128, 128, 1) if M * N >= 8192 * 640 else (64, 64, 1)
         if _args_only:
             sp = 1
-        a = L.GemmArgs()
-        a.X, a.W, a.Y = x.data_ptr(), w.data_ptr(), out.data_ptr()
-        if x2 is not None:
-            a.X2, a.Cin1 = x2.data_ptr(), x.shape[1]
+        a = self._gemm_args(x, w, out, (M, N, K), (ldx if ldx is not None else x.stride(0), ldw if ldw is not None else w.stride(0),
+                                                   ldy if ldy is not None else out.stride(0)), (bm, bn, sp), flags=flags,
+                            bias=bias, rowadd=rowadd, residual=residual, ldra=ldra, rows_per_batch=rows_per_batch, x2=x2,
+                            ldr=(ldr if ldr is not None else residual.stride(0)) if residual is not None else 0)
         if yt is not None:
             self._chk(yt[0], descr + ".yt")
             if yt[0].dim() != 2 or yt[0].stride(1) != 1 or yt[0].shape[0] != N - int(yt[1]) or yt[0].shape[1] < M:
                 raise L.ImhError(f"{descr}: yt {tuple(yt[0].shape)} does not fit [{N - int(yt[1])}, >= {M}]")
             a.Yt, a.yt_col0, a.ldyt = yt[0].data_ptr(), int(yt[1]), yt[0].stride(0)
-        a.bias, a.rowadd, a.residual = self._p(bias), self._p(rowadd), self._p(residual)
-        keep_ln = ()
-        if ln is not None:           # (s, c fp32, eps[, stats]); the caller sets GF_LN_ROW / GF_LN_COL in flags
-            a.ln_s, a.ln_c, a.ln_eps = ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2])
-            keep_ln = (ln[0], ln[1])
-            if ln_stats is not None:
-                a.ln_stats, a.ln_slots = ln_stats[0].data_ptr(), int(ln_stats[1])
-                keep_ln += (ln_stats[0],)
-        a.M, a.N, a.K = M, N, K
-        a.ldx = ldx if ldx is not None else x.stride(0)
-        a.ldw = ldw if ldw is not None else w.stride(0)
-        a.ldy = ldy if ldy is not None else out.stride(0)
-        a.ldr = (ldr if ldr is not None else residual.stride(0)) if residual is not None else 0
-        a.ldra = ldra
-        a.rows_per_batch = rows_per_batch
-        a.splits, a.flags, a.dtype, a.conv, a.bm, a.bn = sp, flags, self.dt, 0, bm, bn
-        a.xcd = self._xcd_for(N, flags, 0)
-        if sp > 1:
-            a.partial = self.workspace(self.lib.imh_gemm_workspace_bytes(M, N, sp)).data_ptr()
+        keep_ln = self._ln_fold(a, ln, ln_stats)           # (s, c fp32, eps[, stats]); the caller sets GF_LN_ROW / GF_LN_COL in flags
+        es = x.element_size()
+        keep = (x, w, out, bias, rowadd, residual, x2) + keep_ln
+        if _args_only:
+            return a, out, 2.0 * M * N * K, es * (M * K + N * K + M * n_out), keep
         st = None
-        if stats_out and not _args_only:
+        if stats_out:
             wd = self.lib.imh_gemm_stats_slot_width(bm, bn)
             # (a folded-LayerNorm launch of a wave-specialised variant ends in the lean epilogue, which emits none: gemm_launch refuses)
             if wd > 0 and N % wd == 0 and sp == 1 and not flags & (L.GF_GEGLU | L.GF_VT_PERM | L.GF_OUT_F32) \
                     and not (bm > 128 and flags & (L.GF_LN_ROW | L.GF_LN_COL)):
                 st = (self.new(M, N // wd, 2, dtype=torch.float32), N // wd)
                 a.ln_stats_out, a.ln_slots_out = st[0].data_ptr(), st[1]
-        gn = self._gn_epilogue(a, gn_out) if gn_out is not None and not _args_only else None
-        es = x.element_size()
-        if _args_only:
-            return a, out, 2.0 * M * N * K, es * (M * K + N * K + M * n_out), (x, w, out, bias, rowadd, residual, x2) + keep_ln
+        gn = self._gn_epilogue(a, gn_out) if gn_out is not None else None
         self._emit(L.OP_GEMM, a, descr=descr, flops=2.0 * M * N * K, nbytes=es * (M * K + N * K + M * n_out),
-                   keep=(x, w, out, bias, rowadd, residual, x2) + keep_ln + ((st[0],) if st else ()) + ((gn.t,) if gn else ())
-                   + ((yt[0],) if yt is not None else ()),
-                   shape=(M, N, K, 0, None),
-                   epi=dict(flags=flags, bias=bias is not None, residual=residual is not None, rowadd=rowadd is not None,
-                            rows_per_batch=rows_per_batch, cfg=(bm, bn, sp), ln_pre=ln_stats is not None,
-                            ln_slots=int(ln_stats[1]) if ln_stats is not None else 0, stats_out=st is not None,
-                            gn_out=(gn.nblk, gn_out) if gn else None, x2=x.shape[1] if x2 is not None else 0,
-                            yt=int(yt[1]) if yt is not None else 0))
-        if own_stats:
-            self.free(ln_stats[0])
+                   keep=keep + ((st[0],) if st else ()) + ((gn.t,) if gn else ()) + ((yt[0],) if yt is not None else ()),
+                   shape=(M, N, K, 0, None), free=own,
+                   epi=self._gemm_epi(a, gn, gn_out, ln_pre=ln_stats is not None, ln_slots=int(ln_stats[1]) if ln_stats is not None else 0,
+                                      stats_out=st is not None, yt=int(yt[1]) if yt is not None else 0))
         if stats_out:
             if st is None:
                 st = self.row_stats(out.view(M, n_out) if out.dim() != 2 else out, descr=descr + ".row_stats")
@@ -427,6 +379,56 @@ class Ctx:
         if gn_out is not None:
             return out, gn
         return out
+
+    def _gemm_args(self, x, w, out, mnk, ld, cfg, flags=0, geom=None, bias=None, rowadd=None, residual=None, ldr=0, ldra=0, rows_per_batch=0,
+                   x2=None):
+        """the L.GemmArgs of every GEMM and implicit-GEMM launch: operands, mnk = (M, N, K), ld = (ldx, ldw, ldy), cfg = (bm, bn, splits)
+        with the split-K workspace, the XCD request; geom = (H, W, Cin, Ho, Wo, stride, up, pad) makes it a conv3x3.  x2: the second
+        token / channel source, read after the x.shape[-1] columns of x"""
+        a = L.GemmArgs()
+        a.X, a.W, a.Y = x.data_ptr(), w.data_ptr(), out.data_ptr()
+        a.bias, a.rowadd, a.residual = self._p(bias), self._p(rowadd), self._p(residual)
+        if x2 is not None:
+            a.X2, a.Cin1 = x2.data_ptr(), x.shape[-1]
+        a.M, a.N, a.K = mnk
+        a.ldx, a.ldw, a.ldy = ld
+        a.ldr, a.ldra, a.rows_per_batch = ldr, ldra, rows_per_batch
+        a.bm, a.bn, a.splits = cfg
+        a.flags, a.dtype, a.conv = flags, self.dt, int(geom is not None)
+        a.xcd = self._xcd_for(a.N, flags, a.conv)
+        if geom is not None:
+            a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.stride, a.up, a.pad = geom
+        if a.splits > 1:
+            a.partial = self.workspace(self.lib.imh_gemm_workspace_bytes(a.M, a.N, a.splits)).data_ptr()
+        return a
+
+    @staticmethod
+    def _gemm_epi(a, gn, gn_hw, **more):
+        """the epilogue / config dict of a GEMM or conv3x3 launch as ctx.tags keeps it; gn = the GnStats its epilogue writes (or None) over
+        gn_hw rows per sample"""
+        return dict(flags=a.flags, bias=bool(a.bias), residual=bool(a.residual), rowadd=bool(a.rowadd), rows_per_batch=a.rows_per_batch,
+                    cfg=(a.bm, a.bn, a.splits), gn_out=(gn.nblk, gn_hw) if gn else None, x2=a.Cin1 if a.X2 else 0, **more)
+
+    def _ln_stats(self, ln, rows, descr):
+        """the statistics of a folded LayerNorm ln = (s, c, eps[, stats]), for every launch that folds one: those the caller hands over,
+        else those of a row-statistics launch over the token rows rows() -- its buffer goes back to the pool once the consumer is emitted
+        (_emit(free=...)).  rows=None: no launch.  -> ((tensor, slots) or None, buffers to free)"""
+        if len(ln) > 3 and ln[3] is not None:
+            return ln[3], ()
+        if rows is None:
+            return None, ()
+        st = self.row_stats(rows(), descr=descr + ".ln_row_stats")
+        return st, (st[0],)
+
+    def _ln_fold(self, a, ln, stats):
+        """ln = (s, c, eps[, ...]) and its statistics into the ln_* fields GemmArgs and the fused cross-attentions share -> tensors to keep"""
+        if ln is None:
+            return ()
+        a.ln_s, a.ln_c, a.ln_eps = ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2])
+        if stats is None:
+            return ln[0], ln[1]
+        a.ln_stats, a.ln_slots = stats[0].data_ptr(), int(stats[1])
+        return ln[0], ln[1], stats[0]
 
     # (bm, bn, tile rows) that carry the transposed store (gemm_launch: every wave-specialised variant at bn = 160, and 23256 x 128)
     _YT = ((23256, 160, 256), (24128, 160, 128), (2464, 160, 64), (1464, 160, 64), (23256, 128, 256), (22128, 160, 128))
@@ -449,19 +451,22 @@ class Ctx:
         raise L.ImhError(f"{descr}: Yt (the transposed V^T store, yt=) needs a wave-specialised bn = 160 variant or 23256 x 128 with whole tiles and col0 a "
                          f"multiple of bn (variant {tuple(c)}, M={M}, N={N}, col0={col0})")
 
-    def _gn_epilogue(self, a, hw):
+    def _gn_epilogue(self, a, hw, phases=1):
         """GroupNorm partials from the launch's epilogue (imh_gemm_args.gn_out) if its variant and shape have one: fills the
-        fields of a and returns the GnStats of the output ([B, blocks, N / 10, 2] fp32), else None"""
+        fields of a and returns the GnStats of the output ([B, blocks, N / 10, 2] fp32), else None.  hw: rows of a per sample.
+        phases = 4: the phase form of conv3x3(up=2), whose N is four phases of N / 4 output channels -- one partial per (sample, `rows`
+        consecutive low-res pixels, phase, 10 channels): block ph * (hw / rows) + low-res row block"""
         rows = self.lib.imh_gemm_gn_block_rows(a.bm, a.bn)
         halo = a.bm in self._HALO
-        if (rows <= 0 or a.splits != 1 or a.N % 10 or hw % rows or a.M % hw
-                or a.N % (a.bn if halo else 80) or a.flags & ~(L.GF_ACT_SILU | L.GF_ACT_GELU | L.GF_ACT_QGELU)
+        N = a.N // phases
+        if (rows <= 0 or a.splits != 1 or N % 10 or hw % rows or a.M % hw
+                or N % (a.bn if halo else 80) or a.flags & ~(L.GF_ACT_SILU | L.GF_ACT_GELU | L.GF_ACT_QGELU)
                 or (halo and (a.Ho % (rows // 4) or a.Wo % 16))):
             return None
-        nblk = hw // rows
-        t = self.new(a.M // hw, nblk, a.N // 10, 2, dtype=torch.float32)
+        nblk = phases * (hw // rows)
+        t = self.new(a.M // hw, nblk, N // 10, 2, dtype=torch.float32)
         a.gn_out, a.gn_nblk, a.gn_hw = t.data_ptr(), nblk, hw
-        return GnStats(t, nblk, 10, rows * 10, a.N)
+        return GnStats(t, nblk, 10, rows * 10, N)
 
     def row_stats(self, x, descr="row_stats"):
         """LayerNorm statistics of token rows x [rows, C] in the hand-over format (one slot per row): the stand-alone
@@ -479,29 +484,20 @@ class Ctx:
         for g in (g1, g2):
             if g.get("x2") is not None or g.get("yt") is not None or g.get("gn_out") is not None or g.get("stats_out"):
                 raise L.ImhError(f"{descr}: x2 / yt / gn_out / stats_out are single-problem (Ctx.gemm) features")
-        own = None
+        own = ()
         l1, l2 = g1.get("ln"), g2.get("ln")
-        if l1 is not None and (len(l1) < 4 or l1[3] is None):
-            own = self.row_stats(g1["x"], descr=descr + ".ln_row_stats")
-            g1 = dict(g1, ln=tuple(l1[:3]) + (own,))
-            if l2 is not None and (len(l2) < 4 or l2[3] is None):
-                g2 = dict(g2, ln=tuple(l2[:3]) + (own,))
+        if l1 is not None:
+            st, own = self._ln_stats(l1, lambda: g1["x"], descr)
+            if own:
+                g1 = dict(g1, ln=tuple(l1[:3]) + (st,))
+                if l2 is not None and (len(l2) < 4 or l2[3] is None):
+                    g2 = dict(g2, ln=tuple(l2[:3]) + (st,))
         a1, o1, f1, b1, k1 = self.gemm(_args_only=True, cfg=(cfg[0], cfg[1], 1), **g1)
         a2, o2, f2, b2, k2 = self.gemm(_args_only=True, cfg=(cfg[0], cfg[1], 1), **g2)
-        pair = (L.GemmArgs * 2)(a1, a2)
-        if self.record:
-            rc = self.lib.imh_plan_add(self.plan, L.OP_GEMM_DUAL, C.cast(pair, C.c_void_p), 0, self.tag)
-            if rc < 0:
-                L.check(rc, "imh_plan_add")
-            self.keep.extend(t for t in k1 + k2 if t is not None)
-            self.tags.append((self.tag, L.OP_GEMM, descr, f1 + f2, b1 + b2, None,
-                              dict(dual=((a1.M, a1.N, a1.K, a1.flags), (a2.M, a2.N, a2.K, a2.flags)), cfg=tuple(cfg),
-                                   ln_pre=bool(a1.ln_stats), ln_slots=int(a1.ln_slots))))
-            self._ops.append((L.OP_GEMM_DUAL, pair, self._cold(k1[:2] + k2[:2])))
-        else:
-            L.check(self.lib.imh_gemm_dual(C.byref(pair[0]), C.byref(pair[1]), self.stream()), descr)
-        if own is not None:
-            self.free(own[0])
+        # (keep: the cold-weight candidates, _cold's first two, are those of k1[:2] + k2[:2])
+        self._emit(L.OP_GEMM_DUAL, (L.GemmArgs * 2)(a1, a2), descr=descr, flops=f1 + f2, nbytes=b1 + b2, keep=k1[:2] + k2[:2] + k1[2:] + k2[2:],
+                   free=own, epi=dict(dual=((a1.M, a1.N, a1.K, a1.flags), (a2.M, a2.N, a2.K, a2.flags)), cfg=tuple(cfg),
+                                      ln_pre=bool(a1.ln_stats), ln_slots=int(a1.ln_slots)))
         return o1, o2
 
     def conv_fuses_gn(self, M, N, K, stride=1, up=0, cfg=None):
@@ -544,35 +540,19 @@ class Ctx:
         if c is None:
             raise L.ImhError(f"{descr}: the phase form (up=2) does not run this launch (Cin {Cin} % 64, Cout {Cout} % tile width, variant "
                              f"{cfg}, imh_debug_set key 11); use up=1 (Ctx.conv_up_phase_cfg)")
-        bm, bn, sp = c
         Ho, Wo = 2 * H, 2 * W
         M, N, K = B * H * W, 4 * Cout, 4 * Cin
         if out is None:
             out = self.new(B, Ho, Wo, Cout)
-        a = L.GemmArgs()
-        a.X, a.W, a.Y, a.bias = x.data_ptr(), w_phase.data_ptr(), out.data_ptr(), self._p(bias)
-        a.M, a.N, a.K = M, N, K
-        a.ldx, a.ldw, a.ldy = Cin, K, Cout
-        a.rows_per_batch = H * W
-        a.splits, a.flags, a.dtype, a.conv, a.bm, a.bn = 1, 0, self.dt, 1, bm, bn
-        a.xcd = self._xcd_for(N, 0, 1)
-        a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.stride, a.up, a.pad = H, W, Cin, Ho, Wo, 1, 2, 0
-        gs = None
-        rows = self.lib.imh_gemm_gn_block_rows(bm, bn)
-        if gn_groups and rows > 0 and Cout % 80 == 0 and (H * W) % rows == 0:
-            # one partial per (sample, `rows` consecutive low-res pixels, phase, 10 channels): block ph * (H W / rows) + low-res row block
-            nblk = 4 * (H * W // rows)
-            t = self.new(B, nblk, Cout // 10, 2, dtype=torch.float32)
-            a.gn_out, a.gn_nblk, a.gn_hw = t.data_ptr(), nblk, H * W
-            gs = GnStats(t, nblk, 10, rows * 10, Cout)
+        a = self._gemm_args(x, w_phase, out, (M, N, K), (Cin, K, Cout), c, geom=(H, W, Cin, Ho, Wo, 1, 2, 0), bias=bias, rows_per_batch=H * W)
+        gs = self._gn_epilogue(a, H * W, phases=4) if gn_groups else None
         es = x.element_size()
         # (recorded as the conv it computes -- output pixels x Cout x 9 Cin, geometry up = 2, the conv's algorithmic FLOPs like every other
         # launch; the launch executes 4/9 of them, 2 M N K)
         self._emit(L.OP_GEMM, a, descr=descr, flops=2.0 * (B * Ho * Wo) * Cout * 9 * Cin, nbytes=es * (M * Cin + N * K + 4 * M * Cout),
                    keep=(x, w_phase, out, bias) + ((gs.t,) if gs else ()),
                    shape=(B * Ho * Wo, Cout, 9 * Cin, 1, (B, H, W, Cin, 1, 2)),
-                   epi=dict(flags=0, bias=bias is not None, residual=False, rowadd=False, rows_per_batch=Ho * Wo, cfg=(bm, bn, sp),
-                            gn_out=(gs.nblk, Ho * Wo) if gs else None, gn_in=None, x2=0))
+                   epi=dict(self._gemm_epi(a, gs, Ho * Wo, gn_in=None), rows_per_batch=Ho * Wo))
         return (out, gs) if gn_groups else out
 
     def conv3x3(self, x, w, bias=None, stride=1, up=0, residual=None, rowadd=None, ldra=0, out=None, cfg=None,
@@ -615,28 +595,13 @@ class Ctx:
         if (gn is not None or x2 is not None) and not self.conv_fuses_gn(M, N, K, stride, up, cfg=(bm, bn, sp)):
             raise L.ImhError(f"{descr}: the fused GroupNorm front end / two-source input need the LDS-halo conv3x3 (variant {bm} x {bn}, "
                              f"stride {stride}, up {up}); apply the GroupNorm / concat as passes for this launch (Ctx.conv_fuses_gn)")
-        a = L.GemmArgs()
-        a.X, a.W, a.Y = x.data_ptr(), w.data_ptr(), out.data_ptr()
-        a.bias, a.rowadd, a.residual = self._p(bias), self._p(rowadd), self._p(residual)
-        a.M, a.N, a.K = M, N, K
-        a.ldx, a.ldw, a.ldy = Cin, K, Cout
-        a.ldr = Cout if residual is not None else 0
-        a.ldra = ldra
-        a.rows_per_batch = Ho * Wo
-        a.splits, a.flags, a.dtype, a.conv, a.bm, a.bn = sp, 0, self.dt, 1, bm, bn
-        a.xcd = self._xcd_for(N, 0, 1)
-        a.H, a.Wd, a.Cin, a.Ho, a.Wo, a.stride, a.up, a.pad = H, W, Cin, Ho, Wo, stride, up, pad
-        if x2 is not None:
-            a.X2, a.Cin1 = x2.data_ptr(), C1
+        a = self._gemm_args(x, w, out, (M, N, K), (Cin, K, Cout), (bm, bn, sp), geom=(H, W, Cin, Ho, Wo, stride, up, pad), bias=bias, rowadd=rowadd,
+                            residual=residual, ldr=Cout if residual is not None else 0, ldra=ldra, rows_per_batch=Ho * Wo, x2=x2)
         gn_keep = ()
         if gn is not None and isinstance(gn[0], GnSpec):
             sp_, silu = gn
             sp_.check(B, Cin, descr)
-            s0 = sp_.srcs[0]
-            a.gn_part, a.gn_pnblk, a.gn_psub, a.gn_pnpart, a.gn_pC1 = s0.t.data_ptr(), s0.nblk, s0.sub, s0.npart, s0.C
-            if len(sp_.srcs) == 2:
-                s1 = sp_.srcs[1]
-                a.gn_part2, a.gn_pnblk2, a.gn_psub2, a.gn_pnpart2 = s1.t.data_ptr(), s1.nblk, s1.sub, s1.npart
+            self._gn_sources(a, sp_.srcs)
             a.gn_gamma, a.gn_beta, a.gn_groups, a.gn_eps, a.gn_silu = self._p(sp_.gamma), self._p(sp_.beta), sp_.groups, sp_.eps, int(bool(silu))
             gn_keep = sp_.tensors()
         elif gn is not None:
@@ -645,36 +610,68 @@ class Ctx:
                 raise L.ImhError(f"{descr}: GroupNorm table {tuple(tab.shape)} does not fit [{B}, {Cin}, 2] fp32")
             a.gn_tab, a.gn_silu = tab.data_ptr(), int(bool(silu))
             gn_keep = (tab,)
-        if sp > 1:
-            a.partial = self.workspace(self.lib.imh_gemm_workspace_bytes(M, N, sp)).data_ptr()
         gs = self._gn_epilogue(a, Ho * Wo) if gn_groups else None
         es = x.element_size()
         self._emit(L.OP_GEMM, a, descr=descr, flops=2.0 * M * N * K,
                    nbytes=es * (B * H * W * Cin + N * K + M * N),
                    keep=(x, w, out, bias, rowadd, residual, x2) + ((gs.t,) if gs else ()) + gn_keep,
                    shape=(M, N, K, 1, (B, H, W, Cin, stride, up) + ((pad,) if pad else ())),
-                   epi=dict(flags=0, bias=bias is not None, residual=residual is not None, rowadd=rowadd is not None,
-                            rows_per_batch=Ho * Wo, cfg=(bm, bn, sp), gn_out=(gs.nblk, Ho * Wo) if gs else None,
-                            gn_in=None if gn is None else int(bool(gn[1])), x2=C1 if x2 is not None else 0))
+                   epi=self._gemm_epi(a, gs, Ho * Wo, gn_in=None if gn is None else int(bool(gn[1]))))
         return (out, gs) if gn_groups else out
+
+    # the fields that take the first of one or two GnStats (partials, blocks, sub-run width, elements per partial, channels) in the argument
+    # structs that read GroupNorm partials; the second source's are these names + "2", and it has no channel count of its own
+    _GN_SRC = {L.GemmArgs: ("gn_part", "gn_pnblk", "gn_psub", "gn_pnpart", "gn_pC1"), L.NormArgs: ("partial", "nblk", "sub", "npart", "C1")}
+
+    @classmethod
+    def _gn_sources(cls, a, srcs):
+        """one or two GnStats (a channel concat [a | b]) into the source fields of a conv3x3 / gn_table / gn_table_apply launch"""
+        for sfx, g in zip(("", "2"), srcs):
+            for name, v in zip(cls._GN_SRC[type(a)][:4 if sfx else 5], (g.t.data_ptr(), g.nblk, g.sub, g.npart, g.C)):
+                setattr(a, name + sfx, v)
 
     # ------------------------------------------------------------------ attention
     def attention(self, q, k, vt, out, B, H, Lq, Lk, Lk_pad, ldq, ldk, ldvt, ldo, scale,
                   k2=None, vt2=None, Lk2=0, Lk2_pad=0, ldk2=0, ldvt2=0, scale2=0.0, scale2_tab=None, step=None,
                   descr="attention"):
-        a = L.AttnArgs()
-        a.Q, a.K, a.Vt, a.O = q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
-        a.K2, a.Vt2 = self._p(k2), self._p(vt2)
-        a.B, a.H, a.Lq, a.Lk, a.Lk_pad, a.Lk2, a.Lk2_pad = B, H, Lq, Lk, Lk_pad, Lk2, Lk2_pad
-        a.ldq, a.ldk, a.ldvt, a.ldk2, a.ldvt2, a.ldo = ldq, ldk, ldvt, ldk2, ldvt2, ldo
-        a.scale, a.scale2, a.dtype = scale, scale2, self.dt
-        a.scale2_tab, a.step = self._p(scale2_tab), self._p(step)
+        a = self._attn_args(L.AttnArgs(), out, B, H, Lq, (k, vt, Lk, Lk_pad, ldk, ldvt), (k2, vt2, Lk2, Lk2_pad, ldk2, ldvt2), ldo,
+                            (scale, scale2, scale2_tab, step))
+        a.Q, a.ldq = q.data_ptr(), ldq
         es = q.element_size()
         fl = 4.0 * B * H * Lq * (Lk + Lk2) * 64
         by = es * (2 * B * Lq * H * 64 + 2 * B * (Lk + Lk2) * H * 64)
         self._emit(L.OP_ATTN, a, descr=descr, flops=fl, nbytes=by, keep=(q, k, vt, out, k2, vt2, scale2_tab, step),
                    shape=(B, H, Lq, Lk, Lk_pad), epi=dict(Lk2=Lk2, Lk2_pad=Lk2_pad, tab=scale2_tab is not None))
         return out
+
+    def _attn_args(self, a, out, B, H, Lq, keys, keys2, ldo, scales):
+        """what AttnArgs, XAttnArgs and XAttnRegionsArgs share: keys = (k, vt, Lk, Lk_pad, ldk, ldvt), keys2 the same of the second key
+        set (tensors None / zeros without one), scales = (scale, scale2, scale2_tab, step)"""
+        (k, vt, a.Lk, a.Lk_pad, a.ldk, a.ldvt), (k2, vt2, a.Lk2, a.Lk2_pad, a.ldk2, a.ldvt2) = keys, keys2
+        a.K, a.Vt, a.K2, a.Vt2, a.O = k.data_ptr(), vt.data_ptr(), self._p(k2), self._p(vt2), out.data_ptr()
+        a.B, a.H, a.Lq, a.ldo, a.dtype = B, H, Lq, ldo, self.dt
+        a.scale, a.scale2, tab, step = scales
+        a.scale2_tab, a.step = self._p(tab), self._p(step)
+        return a
+
+    def _xattn_args(self, a, x, wq, out, B, H, Lq, keys, keys2, scales, ln, descr):
+        """XAttnArgs / XAttnRegionsArgs: _attn_args plus the fused to_q's x / wq / folded LayerNorm with the statistics the CALLER handed
+        over (the launch's own come from _ln_stats) -> (a, those statistics or None)"""
+        self._chk(x, descr + ".x"); self._chk(wq, descr + ".wq")
+        C_ = H * 64
+        if x.shape[-1] != C_ or tuple(wq.shape) != (C_, C_) or x.stride(-1) != 1 or wq.stride(-1) != 1:
+            raise L.ImhError(f"{descr}: x [.., {C_}] / wq [{C_}, {C_}] expected, got {tuple(x.shape)} / {tuple(wq.shape)}")
+        self._attn_args(a, out, B, H, Lq, keys, keys2, out.stride(0), scales)
+        a.X, a.Wq, a.C, a.ldx, a.ldw = x.data_ptr(), wq.data_ptr(), C_, x.stride(0), wq.stride(0)
+        st = self._ln_stats(ln, None, descr)[0] if ln is not None else None
+        self._ln_fold(a, ln, st)
+        return a, st
+
+    def _emit_xattn(self, kind, a, ln, st, own, keep, fl, by, descr, **epi):
+        """the tag row both fused cross-attentions share"""
+        self._emit(kind, a, descr=descr, flops=fl, nbytes=by, keep=keep + tuple((ln or ())[:2]) + ((st[0],) if st is not None else ()),
+                   shape=(a.B, a.H, a.Lq, a.Lk, a.Lk_pad), free=own,
+                   epi=dict(Lk2=a.Lk2, Lk2_pad=a.Lk2_pad, tab=bool(a.scale2_tab), ln=ln is not None, ln_slots=int(a.ln_slots) if ln is not None else 0, **epi))
 
     def cross_attention(self, x, wq, k, vt, out, B, H, Lq, Lk, Lk_pad, ldk, ldvt, scale, ln=None,
                         k2=None, vt2=None, Lk2=0, Lk2_pad=0, ldk2=0, ldvt2=0, scale2=0.0, scale2_tab=None, step=None,
@@ -683,38 +680,17 @@ class Ctx:
         (csrc/xattn.hip).  x [B*Lq, C]; wq [C, C]; k / k2 caches with head dims in vt_perm16 order (GF_VT_PERM);
         ln = (s, c, eps[, stats]): x is un-normalised and wq pre-scaled by gamma; stats as in gemm() (None -> a row-statistics
         launch over x supplies them)."""
-        self._chk(x, descr + ".x"); self._chk(wq, descr + ".wq")
-        C_ = H * 64
-        if x.shape[-1] != C_ or tuple(wq.shape) != (C_, C_) or x.stride(-1) != 1 or wq.stride(-1) != 1:
-            raise L.ImhError(f"{descr}: x [.., {C_}] / wq [{C_}, {C_}] expected, got {tuple(x.shape)} / {tuple(wq.shape)}")
-        a = L.XAttnArgs()
-        a.X, a.Wq, a.K, a.Vt, a.O = x.data_ptr(), wq.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
-        a.K2, a.Vt2 = self._p(k2), self._p(vt2)
-        keep_st = ()
-        own = False
-        if ln is not None:
-            a.ln_s, a.ln_c, a.ln_eps = ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2])
-            st_in = ln[3] if len(ln) > 3 and ln[3] is not None else None
-            own = st_in is None
-            if own:
-                st_in = self.row_stats(x.view(-1, C_), descr=descr + ".ln_row_stats")
-            a.ln_stats, a.ln_slots = st_in[0].data_ptr(), int(st_in[1])
-            keep_st = (st_in[0],)
-        a.B, a.H, a.Lq, a.C = B, H, Lq, C_
-        a.Lk, a.Lk_pad, a.Lk2, a.Lk2_pad = Lk, Lk_pad, Lk2, Lk2_pad
-        a.ldx, a.ldw, a.ldk, a.ldvt, a.ldk2, a.ldvt2, a.ldo = x.stride(0), wq.stride(0), ldk, ldvt, ldk2, ldvt2, out.stride(0)
-        a.scale, a.scale2, a.dtype = scale, scale2, self.dt
-        a.scale2_tab, a.step = self._p(scale2_tab), self._p(step)
+        a, st = self._xattn_args(L.XAttnArgs(), x, wq, out, B, H, Lq, (k, vt, Lk, Lk_pad, ldk, ldvt), (k2, vt2, Lk2, Lk2_pad, ldk2, ldvt2),
+                                 (scale, scale2, scale2_tab, step), ln, descr)
+        own = ()
+        if ln is not None and st is None:
+            st, own = self._ln_stats(ln, lambda: x.view(-1, a.C), descr)
+            self._ln_fold(a, ln, st)
         es = x.element_size()
-        M = B * Lq
+        M, C_ = B * Lq, a.C
         fl = 2.0 * M * C_ * C_ + 4.0 * B * H * Lq * (Lk + Lk2) * 64
         by = es * (2 * M * C_ + C_ * C_ + 2 * B * (Lk + Lk2) * C_)
-        self._emit(L.OP_XATTN, a, descr=descr, flops=fl, nbytes=by,
-                   keep=(x, wq, k, vt, out, k2, vt2, scale2_tab, step) + tuple((ln or ())[:2]) + keep_st,
-                   shape=(B, H, Lq, Lk, Lk_pad), epi=dict(Lk2=Lk2, Lk2_pad=Lk2_pad, tab=scale2_tab is not None, ln=ln is not None,
-                                                          ln_slots=int(a.ln_slots) if ln is not None else 0))
-        if own:
-            self.free(keep_st[0])
+        self._emit_xattn(L.OP_XATTN, a, ln, st, own, (x, wq, k, vt, out, k2, vt2, scale2_tab, step), fl, by, descr)
         return out
 
     @staticmethod
@@ -761,14 +737,13 @@ class Ctx:
         scale2.  k2 / vt2 hold image i of batch b at key (b * n_img + i) * Lk2_pad (the K / V projection of the image tokens as a batch of
         B * n_img); mask fp32 [n_img, >= Lq] (rows mask.stride(0) apart), weights fp32 [n_img] or None (all 1), both on the device.
         What the library refuses is refused here, where the launch is recorded."""
-        self._chk(x, descr + ".x"); self._chk(wq, descr + ".wq")
         self._chk(mask, descr + ".mask", torch.float32); self._chk(weights, descr + ".weights", torch.float32)
         self._chk(scale2_tab, descr + ".scale2_tab", torch.float32); self._chk(step, descr + ".step", torch.int32)
-        C_ = H * 64
-        if x.shape[-1] != C_ or tuple(wq.shape) != (C_, C_) or x.stride(-1) != 1 or wq.stride(-1) != 1:
-            raise L.ImhError(f"{descr}: x [.., {C_}] / wq [{C_}, {C_}] expected, got {tuple(x.shape)} / {tuple(wq.shape)}")
         if mask is None or k2 is None or vt2 is None:
             raise L.ImhError(f"{descr}: k2, vt2 and mask are required")
+        a, st = self._xattn_args(L.XAttnRegionsArgs(), x, wq, out, B, H, Lq, (k, vt, Lk, Lk_pad, ldk, ldvt), (k2, vt2, Lk2, Lk2_pad, ldk2, ldvt2),
+                                 (scale, scale2, scale2_tab, step), ln, descr)
+        C_ = a.C
         n_img = int(n_img)
         if mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] != n_img or mask.shape[1] < Lq:
             raise L.ImhError(f"{descr}: mask {tuple(mask.shape)} must be fp32 [n_img = {n_img}, >= Lq = {Lq}] with unit column stride")
@@ -777,43 +752,21 @@ class Ctx:
         keys2 = B * n_img * Lk2_pad
         if k2.dim() != 2 or vt2.dim() != 2 or k2.shape[0] < keys2 or vt2.shape[1] < keys2 or k2.shape[1] < C_ or vt2.shape[0] < C_:
             raise L.ImhError(f"{descr}: k2 {tuple(k2.shape)} / vt2 {tuple(vt2.shape)} do not hold B * n_img * Lk2_pad = {keys2} keys of {C_} dims")
-        a = L.XAttnRegionsArgs()
-        a.X, a.Wq, a.K, a.Vt, a.O = x.data_ptr(), wq.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
-        a.K2, a.Vt2 = k2.data_ptr(), vt2.data_ptr()
-        a.B, a.H, a.Lq, a.C = B, H, Lq, C_
-        a.Lk, a.Lk_pad, a.Lk2, a.Lk2_pad = Lk, Lk_pad, Lk2, Lk2_pad
-        a.ldx, a.ldw, a.ldk, a.ldvt, a.ldk2, a.ldvt2, a.ldo = x.stride(0), wq.stride(0), ldk, ldvt, ldk2, ldvt2, out.stride(0)
-        a.scale, a.scale2, a.dtype = scale, scale2, self.dt
-        a.scale2_tab, a.step = self._p(scale2_tab), self._p(step)
         a.n_img, a.mask, a.ldm, a.weights = n_img, mask.data_ptr(), mask.stride(0), self._p(weights)
-        keep_st = ()
-        own = False
-        if ln is not None:
-            a.ln_s, a.ln_c, a.ln_eps = ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2])
-            st_in = ln[3] if len(ln) > 3 and ln[3] is not None else None
-            own = st_in is None
-            if own:
-                a.ln_stats, a.ln_slots = 1, 1           # (row_stats' one slot per row, a placeholder pointer: the statistics launch comes after the rule check)
-            else:
-                a.ln_stats, a.ln_slots = st_in[0].data_ptr(), int(st_in[1])
+        need, own = ln is not None and st is None, ()
+        if need:
+            a.ln_stats, a.ln_slots = 1, 1           # (row_stats' one slot per row, a placeholder pointer: the statistics launch comes after the rule check)
         why = self.regions_refusal(a)
         if why:
             raise L.ImhError(f"{descr}: {why}")
-        if own:
-            st_in = self.row_stats(x.view(-1, C_), descr=descr + ".ln_row_stats")
-            a.ln_stats, a.ln_slots = st_in[0].data_ptr(), int(st_in[1])
-        if ln is not None:
-            keep_st = (st_in[0],)
+        if need:
+            st, own = self._ln_stats(ln, lambda: x.view(-1, C_), descr)
+            self._ln_fold(a, ln, st)
         es = x.element_size()
         M = B * Lq
         fl = 2.0 * M * C_ * C_ + 4.0 * B * H * Lq * (Lk + n_img * Lk2) * 64
         by = es * (2 * M * C_ + C_ * C_ + 2 * B * (Lk + n_img * Lk2) * C_) + 4.0 * n_img * Lq
-        self._emit(L.OP_XATTN_REGIONS, a, descr=descr, flops=fl, nbytes=by,
-                   keep=(x, wq, k, vt, out, k2, vt2, scale2_tab, step, mask, weights) + tuple((ln or ())[:2]) + keep_st,
-                   shape=(B, H, Lq, Lk, Lk_pad), epi=dict(Lk2=Lk2, Lk2_pad=Lk2_pad, tab=scale2_tab is not None, ln=ln is not None,
-                                                          ln_slots=int(a.ln_slots) if ln is not None else 0, n_img=n_img))
-        if own:
-            self.free(keep_st[0])
+        self._emit_xattn(L.OP_XATTN_REGIONS, a, ln, st, own, (x, wq, k, vt, out, k2, vt2, scale2_tab, step, mask, weights), fl, by, descr, n_img=n_img)
         return out
 
     # ------------------------------------------------------------------ fp32 (reference-precision) ops of the VAE decode tail (csrc/f32.hip)
@@ -943,57 +896,55 @@ class Ctx:
         return out
 
     # ------------------------------------------------------------------ norms
-    def _norm_args(self, B, HW, Cc, groups, eps, silu, mode):
+    def _norm_args(self, mode, B, HW, Cc, groups=1, eps=1.0, silu=0, rows=0, **tensors):
+        """the L.NormArgs of every GroupNorm pass and of layernorm; tensors: pointer fields by name (None stays null)"""
         a = L.NormArgs()
-        a.B, a.HW, a.C, a.groups, a.eps, a.silu, a.dtype, a.mode = B, HW, Cc, groups, eps, int(silu), self.dt, mode
+        a.B, a.HW, a.C, a.groups, a.rows, a.eps, a.silu, a.dtype, a.mode = B, HW, Cc, groups, rows, eps, int(silu), self.dt, mode
+        for name, t in tensors.items():
+            setattr(a, name, self._p(t))
         return a
+
+    @staticmethod
+    def _bhwc(x):
+        """(B, HW, C) of a flattened NHWC tensor [B, ..., C]"""
+        return x.shape[0], x.numel() // (x.shape[0] * x.shape[-1]), x.shape[-1]
 
     def gn_stats(self, x, sub=10, descr="gn_stats"):
         """stand-alone GroupNorm statistics of x [B, HW, C] (a pass over x) in the hand-over format -- for tensors whose writing
         launch has no statistics epilogue (conv_in, split-K / ring variants)"""
         self._chk(x, descr + ".x")
-        B, HW, Cc = x.shape[0], x.numel() // (x.shape[0] * x.shape[-1]), x.shape[-1]
+        B, HW, Cc = self._bhwc(x)
         if Cc % sub:
             raise L.ImhError(f"{descr}: sub-run width {sub} does not divide C={Cc}")
         nblk = self.lib.imh_groupnorm_stats_blocks(HW, Cc)
         t = self.new(B, nblk, Cc // sub, 2, dtype=torch.float32)
-        a = self._norm_args(B, HW, Cc, 1, 1.0, 0, L.GN_STATS)
-        a.x, a.partial, a.sub = x.data_ptr(), t.data_ptr(), sub
+        a = self._norm_args(L.GN_STATS, B, HW, Cc, x=x, partial=t)
+        a.sub = sub
         self._emit(L.OP_GROUPNORM, a, descr=descr, nbytes=float(x.numel() * x.element_size()), keep=(x, t))
         return GnStats(t, nblk, sub, 0, Cc)
 
     def gn_table(self, stats, gamma, beta, groups, eps, HW, descr="gn_table"):
         """(scale, shift) table [B, C, 2] fp32 of a GroupNorm from the partials of its input: stats = GnStats or a list of two
         (channel concat [a | b]: C = a.C + b.C)"""
-        srcs = list(stats) if isinstance(stats, (list, tuple)) else [stats]
-        if not 1 <= len(srcs) <= 2:
-            raise L.ImhError(f"{descr}: one or two statistics sources")
-        Cc = sum(g.C for g in srcs)
-        B = srcs[0].t.shape[0]
-        cpg = Cc // groups
-        for g in srcs:
-            if tuple(g.t.shape) != (B, g.nblk, g.C // g.sub, 2) or g.t.dtype != torch.float32 or cpg % g.sub or srcs[0].C % g.sub:
-                raise L.ImhError(f"{descr}: statistics {tuple(g.t.shape)} (sub {g.sub}) do not fit C={Cc}, groups={groups}")
+        spec = GnSpec(stats, gamma, beta, groups, eps)
+        B, Cc = (spec.srcs[0].t.shape[0] if spec.srcs else 0), spec.C
+        spec.check(B, Cc, descr)
         tab = self.new(B, Cc, 2, dtype=torch.float32)
-        a = self._norm_args(B, HW, Cc, groups, eps, 0, L.GN_TABLE)
-        a.gamma, a.beta, a.table = self._p(gamma), self._p(beta), tab.data_ptr()
-        a.partial, a.nblk, a.sub, a.npart, a.C1 = srcs[0].t.data_ptr(), srcs[0].nblk, srcs[0].sub, srcs[0].npart, srcs[0].C
-        if len(srcs) == 2:
-            a.partial2, a.nblk2, a.sub2, a.npart2 = srcs[1].t.data_ptr(), srcs[1].nblk, srcs[1].sub, srcs[1].npart
-        self._emit(L.OP_GROUPNORM, a, descr=descr, keep=(gamma, beta, tab) + tuple(g.t for g in srcs))
+        a = self._norm_args(L.GN_TABLE, B, HW, Cc, groups, eps, gamma=gamma, beta=beta, table=tab)
+        self._gn_sources(a, spec.srcs)
+        self._emit(L.OP_GROUPNORM, a, descr=descr, keep=(gamma, beta, tab) + tuple(g.t for g in spec.srcs))
         return tab
 
     def gn_apply(self, x, tab, silu, out=None, descr="gn_apply"):
         """y = silu?(x * scale + shift) as a pass (the consumers that cannot take the table themselves: Linear layers, the
         implicit-GEMM convs)"""
         self._chk(x, descr + ".x")
-        B, HW, Cc = x.shape[0], x.numel() // (x.shape[0] * x.shape[-1]), x.shape[-1]
+        B, HW, Cc = self._bhwc(x)
         if tuple(tab.shape) != (B, Cc, 2) or tab.dtype != torch.float32:
             raise L.ImhError(f"{descr}: table {tuple(tab.shape)} does not fit [{B}, {Cc}, 2]")
         if out is None:
             out = self.new(*x.shape)
-        a = self._norm_args(B, HW, Cc, 1, 1.0, silu, L.GN_APPLY)
-        a.x, a.y, a.table = x.data_ptr(), out.data_ptr(), tab.data_ptr()
+        a = self._norm_args(L.GN_APPLY, B, HW, Cc, silu=silu, x=x, y=out, table=tab)
         es = x.element_size()
         self._emit(L.OP_GROUPNORM, a, descr=descr, flops=4.0 * x.numel(), nbytes=2.0 * es * x.numel(), keep=(x, out, tab))
         return out
@@ -1003,17 +954,12 @@ class Ctx:
         builds its sample's table in LDS -- the form for consumers that cannot take the norm themselves (Transformer2DModel.norm in
         front of proj_in, conv_norm_out)"""
         self._chk(x, descr + ".x")
-        B, HW, Cc = x.shape[0], x.numel() // (x.shape[0] * x.shape[-1]), x.shape[-1]
+        B, HW, Cc = self._bhwc(x)
         spec.check(B, Cc, descr)
         if out is None:
             out = self.new(*x.shape)
-        a = self._norm_args(B, HW, Cc, spec.groups, spec.eps, silu, L.GN_TABLE_APPLY)
-        a.x, a.y, a.gamma, a.beta = x.data_ptr(), out.data_ptr(), self._p(spec.gamma), self._p(spec.beta)
-        s0 = spec.srcs[0]
-        a.partial, a.nblk, a.sub, a.npart, a.C1 = s0.t.data_ptr(), s0.nblk, s0.sub, s0.npart, s0.C
-        if len(spec.srcs) == 2:
-            s1 = spec.srcs[1]
-            a.partial2, a.nblk2, a.sub2, a.npart2 = s1.t.data_ptr(), s1.nblk, s1.sub, s1.npart
+        a = self._norm_args(L.GN_TABLE_APPLY, B, HW, Cc, spec.groups, spec.eps, silu, x=x, y=out, gamma=spec.gamma, beta=spec.beta)
+        self._gn_sources(a, spec.srcs)
         es = x.element_size()
         self._emit(L.OP_GROUPNORM, a, descr=descr, flops=4.0 * x.numel(), nbytes=2.0 * es * x.numel(), keep=(x, out) + spec.tensors())
         return out
@@ -1022,17 +968,16 @@ class Ctx:
         """x: [B, HW, C] (NHWC flattened).  stats = GnStats left by the producing launch's epilogue (gemm(gn_out=...) /
         conv3x3(gn_groups=...)) or by gn_stats(): table + apply, no statistics pass over x; None: statistics + table + apply."""
         self._chk(x, descr + ".x")
-        B, HW, Cc = x.shape[0], x.numel() // (x.shape[0] * x.shape[-1]), x.shape[-1]
+        B, HW, Cc = self._bhwc(x)
         if stats is not None:
             if not isinstance(stats, GnStats) or stats.C != Cc or stats.t.shape[0] != B:
                 raise L.ImhError(f"{descr}: statistics do not fit x {tuple(x.shape)}")
             return self.gn_table_apply(x, GnSpec(stats, gamma, beta, groups, eps), silu, out=out, descr=descr)
         if out is None:
             out = self.new(*x.shape)
-        a = self._norm_args(B, HW, Cc, groups, eps, silu, L.GN_ALL)
-        a.x, a.y, a.gamma, a.beta = x.data_ptr(), out.data_ptr(), self._p(gamma), self._p(beta)
         # scratch use is confined to this op's three kernels (stream order), so the shared workspace is safe
-        a.partial = self.workspace(self.lib.imh_groupnorm_workspace_bytes(B, HW, Cc, groups)).data_ptr()
+        a = self._norm_args(L.GN_ALL, B, HW, Cc, groups, eps, silu, x=x, y=out, gamma=gamma, beta=beta,
+                            partial=self.workspace(self.lib.imh_groupnorm_workspace_bytes(B, HW, Cc, groups)))
         es = x.element_size()
         self._emit(L.OP_GROUPNORM, a, descr=descr, flops=8.0 * x.numel(), nbytes=3.0 * es * x.numel(), keep=(x, out, gamma, beta))
         return out
@@ -1043,15 +988,20 @@ class Ctx:
         rows = x.numel() // Cc
         if out is None:
             out = self.new(*x.shape)
-        a = L.NormArgs()
-        a.x, a.y, a.gamma, a.beta = x.data_ptr(), out.data_ptr(), self._p(gamma), self._p(beta)
-        a.rows, a.C, a.eps, a.dtype = rows, Cc, eps, self.dt
+        a = self._norm_args(L.GN_ALL, 0, 0, Cc, 0, eps, rows=rows, x=x, y=out, gamma=gamma, beta=beta)      # (mode: unread by imh_layernorm)
         es = x.element_size()
         self._emit(L.OP_LAYERNORM, a, descr=descr, flops=8.0 * x.numel(), nbytes=2.0 * es * x.numel(),
                    keep=(x, out, gamma, beta), shape=(rows, Cc))
         return out
 
     # ------------------------------------------------------------------ elementwise
+    def _chk_dense_f32(self, descr, **named):
+        for nm, t in named.items():
+            if t is not None:
+                self._chk(t, f"{descr}.{nm}", torch.float32)
+                if not t.is_contiguous():
+                    raise L.ImhError(f"{descr}: {nm} must be contiguous")
+
     def ew(self, op, y, a=None, b=None, w=None, bias=None, tab=None, step=None, n=0, i=(0, 0, 0, 0, 0, 0),
            f=(0.0, 0.0, 0.0, 0.0), descr="ew", nbytes=0.0, x2=None, noise=None, mask=None, blend_tab=None, hist=None, bank=None,
            seeds=None, noise_stream=0):
@@ -1069,20 +1019,12 @@ class Ctx:
         if hist is not None or bank is not None:
             if op != L.EW_CFG_MSTEP or b is not None or bias is not None:
                 raise L.ImhError(f"{descr}: hist / bank belong to EW_CFG_MSTEP and take the place of b / bias")
-            for t, nm in ((hist, "hist"), (bank, "bank")):
-                if t is not None:
-                    self._chk(t, f"{descr}.{nm}", torch.float32)
-                    if not t.is_contiguous():
-                        raise L.ImhError(f"{descr}: {nm} must be contiguous")
+            self._chk_dense_f32(descr, hist=hist, bank=bank)
             b, bias = hist, bank
         e = L.EwArgs()
         e.a, e.b, e.y, e.w, e.bias = self._p(a), self._p(b), y.data_ptr(), self._p(w), self._p(bias)
         e.tab, e.step = self._p(tab), self._p(step)
-        for t, nm in ((x2, "x2"), (noise, "noise"), (mask, "mask"), (blend_tab, "blend_tab")):
-            if t is not None:
-                self._chk(t, f"{descr}.{nm}", torch.float32)
-                if not t.is_contiguous():
-                    raise L.ImhError(f"{descr}: {nm} must be contiguous")
+        self._chk_dense_f32(descr, x2=x2, noise=noise, mask=mask, blend_tab=blend_tab)
         e.x2, e.noise, e.mask, e.blend_tab = self._p(x2), self._p(noise), self._p(mask), self._p(blend_tab)
         e.n = n
         e.i0, e.i1, e.i2, e.i3, e.i4, e.i5 = i

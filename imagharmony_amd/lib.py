@@ -21,6 +21,7 @@ OP_STEP_SEEDED, OP_RANDN_SEEDED = 10, 11      # the seeded step noise (imh.h): a
 OP_CLIP_PREPROCESS = 13                       # imh_clip_preprocess (imh.h: kind 12 stays refused)
 OP_CONTROL_ADD = 15                           # imh_control_add: the ControlNet's gated residual add (+ GroupNorm partials of the sum); 12 and 14 stay refused
 OP_XATTN_REGIONS = 17                         # imh_cross_attention_regions (include/imh_regions.h): N masked image prompts; 12, 14 and 16 stay refused
+# (OPS, below the argument structs, gives every kind its struct and its eager entry point)
 CLIP_DT_F32 = 2                               # imh_clip_preprocess's fp32 rows (no other entry takes it)
 GN_ALL, GN_STATS, GN_TABLE, GN_APPLY, GN_TABLE_APPLY = 0, 1, 2, 3, 4
 (EW_TIMESTEP, EW_SILU, EW_CONCAT, EW_CONV_IN, EW_CFG_STEP, EW_CAST_F32, EW_ADD, EW_STEP_SET, EW_CFG_RESCALE, EW_SOFTMAX,
@@ -237,6 +238,40 @@ LORA_SYMBOLS = [
 TINYVAE_SYMBOLS = [
     ("imh_tinyvae_conv", C.c_int, [C.POINTER(TinyVaeArgs), _vp]),
 ]
+
+
+# how an eager entry point takes a launch: (entry, args, element-wise op code, stream) -> status
+def _launch(fn, a, op, s):
+    return fn(C.byref(a), s)
+
+
+def _launch_op(fn, a, op, s):                 # imh_elementwise: the op code comes first
+    return fn(op, C.byref(a), s)
+
+
+def _launch_pair(fn, a, op, s):               # imh_gemm_dual: a is (GemmArgs * 2), handed over as two pointers
+    return fn(C.byref(a[0]), C.byref(a[1]), s)
+
+
+# the op table: plan kind -> (argument struct, eager entry point, how that entry is called).  What records under a kind (imh_plan_add copies
+# sizeof(struct) bytes, twice that for the pair) is what its entry launches eagerly; Ctx._emit goes through here for both
+OPS = {
+    OP_GEMM: (GemmArgs, "imh_gemm", _launch),
+    OP_ATTN: (AttnArgs, "imh_attention", _launch),
+    OP_GROUPNORM: (NormArgs, "imh_groupnorm", _launch),
+    OP_LAYERNORM: (NormArgs, "imh_layernorm", _launch),
+    OP_EW: (EwArgs, "imh_elementwise", _launch_op),
+    OP_ATTN_SMALL: (SmallAttnArgs, "imh_attention_small", _launch),
+    OP_GEMM_DUAL: (GemmArgs, "imh_gemm_dual", _launch_pair),
+    OP_XATTN: (XAttnArgs, "imh_cross_attention", _launch),
+    OP_ATTN_ENC: (EncAttnArgs, "imh_attention_enc", _launch),
+    OP_ATTN_ENC_CAUSAL: (EncAttnArgs, "imh_attention_enc_causal", _launch),
+    OP_STEP_SEEDED: (SeededArgs, "imh_step_seeded", _launch),
+    OP_RANDN_SEEDED: (RandnArgs, "imh_randn_seeded", _launch),
+    OP_CLIP_PREPROCESS: (ClipPreprocessArgs, "imh_clip_preprocess", _launch),
+    OP_CONTROL_ADD: (ControlAddArgs, "imh_control_add", _launch),
+    OP_XATTN_REGIONS: (XAttnRegionsArgs, "imh_cross_attention_regions", _launch),
+}
 
 _lib = None
 

@@ -9,6 +9,7 @@
 """
 import copy
 import ctypes as C
+import importlib.util
 import json
 import os
 
@@ -247,7 +248,15 @@ def _describe(ctx):
     for o in ctx._ops:
         structs = list(o[1]) if isinstance(o[1], C.Array) else [o[1]]
         alias.append([None if not p else first.setdefault(p, len(first)) for s in structs for p in _pointers(s)])
-    return dict(tags=json.loads(json.dumps([list(t) for t in ctx.tags])), alias=alias)
+    return dict(tags=json.loads(json.dumps([list(t) for t in ctx.tags])), alias=alias, args=list(_forward_trace_tool().args_digest(ctx)))
+
+
+def _forward_trace_tool():
+    """tools/forward_trace.py, for its args_digest: the exact arguments of every recorded launch"""
+    spec = importlib.util.spec_from_file_location("forward_trace", os.path.join(os.path.dirname(os.path.dirname(__file__)), "tools", "forward_trace.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 TOWER = dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2, projection_dim=64)
@@ -294,6 +303,7 @@ def test_towers_record_what_they_recorded_before_they_shared_a_stack(tower_trace
         assert g == w, f"launch {i}: {g} != {w}"
     for i, (g, w) in enumerate(zip(got["alias"], want["alias"])):
         assert g == w, f"launch {i} ({want['tags'][i][2]}): buffers {g} != {w}"
+    assert got["args"] == want["args"], "the same launches over the same buffers, but a scalar argument, a byte offset or a prefetch differs"
     # the records still answer what the GPU tests and the timing tools read
     keys = ("ctx", "ids", "eos", "hidden", "last", "pooled", "embeds") if name.startswith("text") else ("ctx", "patches", "hidden", "embeds")
     assert all(k in plan for k in keys) and len(plan["hidden"]) == 3

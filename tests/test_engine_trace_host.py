@@ -75,3 +75,21 @@ def test_a_second_conditioning_before_any_schedule_carries_what_there_is():
         TOOL.condition(eng)
         assert eng.st.coef_tab is tab and eng.st.temb_table is None and eng._sched_key is not None
     TOOL.dry(run)()
+
+
+with open(os.path.join(ROOT, "tests", "golden", "engine_args.json")) as f:
+    ARGS = json.load(f)
+
+
+def test_the_argument_digests_cover_every_plan_case():
+    assert sorted(ARGS) == sorted(n for n in GOLDEN if n.startswith("plan/")) == sorted(TOOL.PLAN_CASES)
+
+
+@pytest.mark.parametrize("name", sorted(ARGS))
+def test_recorded_plan_arguments_match_the_recorded_ones(name):
+    """per plan of the case (the tail plan of a split engine second): every field of every launch's argument struct, pointers as
+    (allocation, byte offset), prefetch fields included (tools/forward_trace.py args_digest), against the digest taken before Ctx got
+    one recorder and shared argument packers; the rest of the case is what it is without the digest"""
+    got = json.loads(json.dumps(TOOL.cases()[name](args=True)))
+    assert got.pop("args") == ARGS[name]
+    assert got == GOLDEN[name]

@@ -59,3 +59,25 @@ def test_parameter_and_processor_names_match_the_recorded_ones(name):
     for k in ("state_dict", "attn_processors", "attn2_modules"):
         assert got[k] == GOLDEN[name][k], k
     assert got == GOLDEN[name]
+
+
+# ------------------------------------------------------------------------------------------------------------------ the exact arguments
+with open(os.path.join(ROOT, "tests", "golden", "forward_args.json")) as f:
+    ARGS = json.load(f)
+
+
+def test_the_argument_digests_cover_every_forward_and_45_direct_calls():
+    names = sorted(TOOL.args_cases())
+    assert names == sorted(ARGS)
+    assert sorted(n for n in names if not n.startswith("direct/")) == sorted(n for n in GOLDEN if not n.startswith("model/"))
+    assert len([n for n in names if n.startswith("direct/")]) == len(TOOL.DIRECT) == 45
+    assert ARGS["unet/1x128x128"][0] == 745
+
+
+@pytest.mark.parametrize("name", sorted(ARGS))
+def test_recorded_arguments_match_the_recorded_ones(name):
+    """every field of every launch's argument struct, pointers as (allocation, byte offset), prefetch fields included
+    (tools/forward_trace.py args_digest), against the digest taken before Ctx got one recorder and shared argument packers"""
+    got = TOOL.args_cases()[name]()
+    assert got[0] == ARGS[name][0], "another launch count"
+    assert got == ARGS[name], "the same launch count, but a scalar argument, a byte offset or a prefetch field differs"

@@ -64,6 +64,32 @@ def test_argument_errors_are_status_codes_not_crashes():
     assert l.imh_gemm_workspace_bytes(100, 200, 4) == 100 * 200 * 4 * 4
 
 
+def test_op_table_names_an_exported_entry_and_a_plan_kind_per_row():
+    """lib.OPS, the table Ctx._emit launches and records by: every kind's eager entry is exported and takes the table's struct (two of
+    them for the pair, the op code first for the element-wise entry); imh_plan_add (host only, it never launches) takes a zeroed struct
+    of that type under that kind and refuses the kinds the table leaves out"""
+    from imagharmony_amd import lib
+    C = lib.C
+    l = lib.load()
+    bound = {n: args for n, _, args in lib.SYMBOLS + lib.REGIONS_SYMBOLS}
+    assert sorted(lib.OPS) == sorted(getattr(lib, n) for n in dir(lib) if n.startswith("OP_")) == [*range(12), 13, 15, 17]
+    p = l.imh_plan_create()
+    for i, (kind, (struct, entry, call)) in enumerate(sorted(lib.OPS.items())):
+        want = {lib._launch: [C.POINTER(struct), C.c_void_p], lib._launch_op: [C.c_int, C.POINTER(struct), C.c_void_p],
+                lib._launch_pair: [C.POINTER(struct), C.POINTER(struct), C.c_void_p]}[call]
+        assert bound[entry] == want == list(getattr(l, entry).argtypes), entry
+        assert (call is lib._launch_pair) == (kind == lib.OP_GEMM_DUAL) and (call is lib._launch_op) == (kind == lib.OP_EW)
+        args = (struct * 2)() if call is lib._launch_pair else struct()
+        assert l.imh_plan_add(p, kind, C.byref(args), 0, 100 + kind) == i, entry
+        assert l.imh_plan_get_kind(p, i) == kind and l.imh_plan_get_tag(p, i) == 100 + kind
+        assert l.imh_plan_update(p, i, C.byref(args)) == 0
+    assert l.imh_plan_size(p) == len(lib.OPS)
+    for kind in (12, 14, 16, max(lib.OPS) + 1, -1):
+        assert l.imh_plan_add(p, kind, C.byref(lib.GemmArgs()), 0, 0) == -1 and f"unknown kind {kind}".encode() in l.imh_last_error()
+    assert l.imh_plan_size(p) == len(lib.OPS)
+    l.imh_plan_destroy(p)
+
+
 def test_product_path_has_no_cpu_fallback():
     from imagharmony_amd import lib
     from imagharmony_amd.ctx import Ctx

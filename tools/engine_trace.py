@@ -6,6 +6,10 @@ Every ``Ctx`` the engine makes is a dry recording one (the name ``Ctx`` of the `
 nothing captures and the XCD pick never runs).  ``tests/golden/engine_trace.json`` is this tool's output at the commit before the engine
 got one plan record and one step tail; ``tests/test_engine_trace_host.py`` compares case by case.
 
+``python tools/engine_trace.py --args [out.json]`` writes ``tests/golden/engine_args.json``: per plan case and plan (the tail plan of a
+``cfg_role`` engine second) the launch count and the SHA-1 over the exact arguments of every launch (tools/forward_trace.py
+args_digest), taken at the commit before Ctx got one recorder and shared argument packers.
+
 Per plan case: the launch count of the forward part and a SHA-1 over its (tag, kind, descr, shape, epilogue) list; in clear, every op
 from the first tail op on (``cfg.rescale`` or ``cfg+...``), of both plans of a ``cfg_role`` engine: kind, element-wise op code, descr,
 tag, i0..i5, f0..f3 and every pointer field resolved to the NAME of the engine buffer it points at (null: a null pointer, "?": none of
@@ -27,6 +31,8 @@ from unittest import mock
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from forward_trace import args_digest                                          # noqa: E402
 from imagharmony_amd import denoise as D                                       # noqa: E402
 from imagharmony_amd import lib as L                                           # noqa: E402
 from imagharmony_amd import schedulers as hs                                   # noqa: E402
@@ -159,7 +165,7 @@ def _forward(ctx, n):
     return dict(launches=n, sha1=hashlib.sha1(repr(rows).encode()).hexdigest())
 
 
-def plan_trace(eng):
+def plan_trace(eng, args=False):
     """records the plan of the engine's current schedule and describes it"""
     eng._record()
     split = eng.cfg_role is not None and eng.do_cfg
@@ -170,6 +176,8 @@ def plan_trace(eng):
     out = dict(forward=_forward(rec, n), tail=[_op(rec, j, names) for j in range(n, len(rec.tags))])
     if split:
         out["plan_tail"] = [_op(eng.plan_tail, j, names) for j in range(len(eng.plan_tail.tags))]
+    if args:
+        out["args"] = [list(args_digest(c)) for c in ctxs]
     out["key"] = list(eng._sched_key)
     out["state"] = dict(steps=eng.steps, t_start=eng.t_start, inpaint=eng.inpaint, general=eng.general, stochastic=eng.stochastic,
                         seeded=eng.seeded)
@@ -177,10 +185,10 @@ def plan_trace(eng):
 
 
 def plan_case(scheduler, steps=4, schedule=None, **engine_kw):
-    def run():
+    def run(args=False):
         eng = engine(**engine_kw)
         eng.set_schedule(scheduler(), steps, **(schedule or {}))
-        return plan_trace(eng)
+        return plan_trace(eng, args)
     return run
 
 
@@ -297,9 +305,9 @@ def fork_sequence():
 
 def dry(fn):
     """fn, run with every Ctx the engine makes a dry recording one"""
-    def run():
+    def run(*a, **kw):
         with mock.patch.object(D, "Ctx", DryCtx), torch.no_grad():
-            return fn()
+            return fn(*a, **kw)
     return run
 
 
@@ -315,7 +323,15 @@ def trace():
     return {name: run() for name, run in cases().items()}
 
 
+def args_trace():
+    """{plan case: per plan [launch count, SHA-1] of args_digest}: tests/golden/engine_args.json (python tools/engine_trace.py --args)"""
+    return {name: dry(fn)(args=True)["args"] for name, fn in PLAN_CASES.items()}
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--args"]:
+        del sys.argv[1]
+        trace = args_trace
     text = "{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v, sort_keys=True)}" for k, v in sorted(trace().items())) + "\n}\n"
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
