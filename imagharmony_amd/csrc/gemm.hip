@@ -19,6 +19,7 @@
 #include "imh_common.h"
 #include "imh_kernels.h"
 #include "imh_gemm_epilogue.h"
+#include "imh_gemm_core.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -43,7 +44,6 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int bid, co
     constexpr int XT_BYTES = BM * GEMM_ROW_BYTES;
     constexpr int WT_BYTES = BN * GEMM_ROW_BYTES;
     constexpr int STAGE = XT_BYTES + WT_BYTES;
-    typedef typename Vec<T>::v8 v8;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -61,10 +61,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int bid, co
     }
 
     // ---- split-K range ----
-    const int nkt = p.K / GEMM_BK;
-    const int per = (nkt + p.splits - 1) / p.splits;
-    const int kt0 = z * per;
-    const int kt1 = min(nkt, kt0 + per);
+    int kt0, kt1;
+    split_k_range(p, z, kt0, kt1);
 
     // ---- per-thread staging state ----
     const unsigned char* zero = g_zero_page;
@@ -151,10 +149,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int bid, co
     }
 
     f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
     constexpr int NS = LN == 1 ? FM : 1;
     float st_s[NS], st_q[NS];
 #pragma unroll
@@ -178,19 +173,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int bid, co
         for (int kt = kt0; kt < kt1; ++kt) {
             if (kt + 1 < kt1) stage(cur ^ 1, kt + 1);
             const unsigned char* xs = smem + cur * STAGE;
-            const unsigned char* ws = xs + XT_BYTES;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                v8 xf[FM], wf[FN];
-#pragma unroll
-                for (int i = 0; i < FM; ++i) xf[i] = *(const v8*)(xs + xoff[kk] + i * 16 * GEMM_ROW_BYTES);
-#pragma unroll
-                for (int j = 0; j < FN; ++j) wf[j] = *(const v8*)(ws + woff[kk] + j * 4 * GEMM_ROW_BYTES);
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(wf[j], xf[i], acc[i][j]);
-            }
+            mma_ktile<T>(xs, xs + XT_BYTES, xoff, woff, acc);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             cur ^= 1;
@@ -228,14 +211,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int bid, co
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[j * 4 + r] = acc[i][j][r];
         if (p.splits > 1) {
-            float* o = p.partial + ((size_t)z * p.M + m) * p.N + nb;
-            if (nb + 4 * FN <= p.N && (p.N & 3) == 0) {
-#pragma unroll
-                for (int q0 = 0; q0 < 4 * FN; q0 += 4) *(f32x4*)(o + q0) = f32x4{v[q0], v[q0 + 1], v[q0 + 2], v[q0 + 3]};
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4 * FN; ++q) if (nb + q < p.N) o[q] = v[q];
-            }
+            store_partial<4 * FN>(p, z, m, nb, v);
         } else {
             if constexpr (LN == 1) { ln.mean = st_s[i]; ln.rstd = st_q[i]; }     // fragment i's row (lane & 15) IS output row m
             epilogue_store_pre<T, FN>(p, v, m, nb, lnpre, have_pre, LN != 0 ? &ln : nullptr, nullptr, lane);
@@ -291,22 +267,11 @@ IMH_KERNEL __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
 
 template <typename T, int BM, int BN, bool CONV>
 static int launch_tile(const GemmParams& p, hipStream_t stream) {
-    GemmParams q = p;
-    int tiles;
-    xcd_partition(q, BM, BN, &tiles);
     const size_t smem = 2 * (size_t)(BM + BN) * GEMM_ROW_BYTES + (p.ln_stats ? (BM > BN ? BM : BN) * 8 : 0);
-    dim3 grid(tiles, p.splits, 1);
-    if (!CONV && (p.flags & GF_LN_ROW)) {             // (gemm_launch has checked that p.ln_stats is there)
-        static DynLdsOnce once;
-        once.ensure((const void*)gemm_kernel<T, BM, BN, false, 1>, (int)smem);
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, 1>), grid, dim3(256), smem, stream, q);
-    } else if (!CONV && (p.flags & GF_LN_COL)) {
-        static DynLdsOnce once;
-        once.ensure((const void*)gemm_kernel<T, BM, BN, false, 2>, (int)smem);
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, 2>), grid, dim3(256), smem, stream, q);
-    }
-    else hipLaunchKernelGGL((gemm_kernel<T, BM, BN, CONV, 0>), grid, dim3(256), smem, stream, q);
-    return check_launch("gemm_kernel");
+    if (!CONV && (p.flags & GF_LN_ROW))               // (gemm_launch has checked that p.ln_stats is there)
+        return launch_gemm<gemm_kernel<T, BM, BN, false, 1>>(p, BM, BN, 256, smem, true, "gemm_kernel", stream);
+    if (!CONV && (p.flags & GF_LN_COL)) return launch_gemm<gemm_kernel<T, BM, BN, false, 2>>(p, BM, BN, 256, smem, true, "gemm_kernel", stream);
+    return launch_gemm<gemm_kernel<T, BM, BN, CONV, 0>>(p, BM, BN, 256, smem, false, "gemm_kernel", stream);
 }
 
 int gemm_ring_launch(const GemmParams& p, int dtype, int conv, int bm, int bn, hipStream_t stream);
@@ -314,18 +279,20 @@ int gemm_ws_dual_launch(const GemmParams& a, const GemmParams& b, int dtype, hip
 int conv_halo_launch(const GemmParams& p, int dtype, int bm, int bn, hipStream_t stream);       // conv_halo.hip: variant codes 7128 / 7564 x 320 / 160
 int gemm_pp_launch(const GemmParams& p, int dtype, int conv, int bm, hipStream_t stream);      // gemm_pp.hip: variant codes 8256 x 256, 9128 x 320
 
+template <typename T> constexpr int dtype_of() { return std::is_same<T, bf16_t>::value ? IMH_DT_BF16 : IMH_DT_F16; }
+
 template <typename T>
 static int launch_typed(const GemmParams& p, int conv, int bm, int bn, hipStream_t stream) {
     int rc;
     if (bm == 7128 || bm == 7564 || bm == 7328 || bm == 7428 || bm == 7256 || bm == 7356) {
         if (!conv) { set_error("gemm: variant 7128 is the halo conv3x3 kernel"); return IMH_ERR_ARG; }
-        rc = conv_halo_launch(p, sizeof(T) == 2 && std::is_same<T, bf16_t>::value ? IMH_DT_BF16 : IMH_DT_F16, bm, bn, stream);
+        rc = conv_halo_launch(p, dtype_of<T>(), bm, bn, stream);
     } else
     if (bm == 8256 || bm == 9128 || bm == 9256) {
-        rc = gemm_pp_launch(p, sizeof(T) == 2 && std::is_same<T, bf16_t>::value ? IMH_DT_BF16 : IMH_DT_F16, conv, bm, stream);
+        rc = gemm_pp_launch(p, dtype_of<T>(), conv, bm, stream);
     } else
     if (bm >= 256) {
-        rc = gemm_ring_launch(p, sizeof(T) == 2 && std::is_same<T, bf16_t>::value ? IMH_DT_BF16 : IMH_DT_F16, conv, bm, bn, stream);
+        rc = gemm_ring_launch(p, dtype_of<T>(), conv, bm, bn, stream);
     } else
     if (conv) {
         if (bm == 128 && bn == 128) rc = launch_tile<T, 128, 128, true>(p, stream);
@@ -352,18 +319,9 @@ static int launch_typed(const GemmParams& p, int conv, int bm, int bn, hipStream
 
 template <typename T, int BM, int BN>
 static int launch_dual_tile(const GemmParams& a, const GemmParams& b, hipStream_t stream) {
-    GemmParams qa = a, qb = b;
-    int ga, gb;
-    xcd_partition(qa, BM, BN, &ga);
-    xcd_partition(qb, BM, BN, &gb);
     const size_t smem = 2 * (size_t)(BM + BN) * GEMM_ROW_BYTES + (a.ln_stats ? (BM > BN ? BM : BN) * 8 : 0);
-    if (a.flags & GF_LN_ROW) {
-        static DynLdsOnce once;
-        once.ensure((const void*)gemm_dual_kernel<T, BM, BN, true>, (int)smem);
-        hipLaunchKernelGGL((gemm_dual_kernel<T, BM, BN, true>), dim3(ga + gb), dim3(256), smem, stream, qa, qb, ga);
-    }
-    else hipLaunchKernelGGL((gemm_dual_kernel<T, BM, BN, false>), dim3(ga + gb), dim3(256), smem, stream, qa, qb, ga);
-    return check_launch("gemm_dual_kernel");
+    if (a.flags & GF_LN_ROW) return launch_gemm_pair<gemm_dual_kernel<T, BM, BN, true>>(a, BM, BN, b, BM, BN, 256, smem, true, "gemm_dual_kernel", stream);
+    return launch_gemm_pair<gemm_dual_kernel<T, BM, BN, false>>(a, BM, BN, b, BM, BN, 256, smem, false, "gemm_dual_kernel", stream);
 }
 
 template <typename T>
@@ -437,15 +395,14 @@ void gemm_pick_config(int M, int N, int K, int* bm, int* bn, int* splits) {
 // statistics epilogue (imh_lnstats.h): a wave's four 16-lane groups own one slot of consecutive columns
 int gemm_stats_slot_width(int bm, int bn) {
     if ((bm == 64 || bm == 128) && (bn == 64 || bn == 128)) return bn / 2;          // plain tiles: 2 x 2 waves
-    if ((bm == 1464 || bm == 2464 || bm == 24128 || bm == 23256 || bm == 22128) && bn == 160) return 80;   // wave-specialised, CN = 2
+    if (variant_is_ws(bm) && bn == 160) return 80;   // wave-specialised, CN = 2
     if ((bm == 24128 || bm == 23256) && bn == 128) return 64;
     return 0;
 }
 
 // GroupNorm epilogue (imh_lnstats.h gn_emit): pixels per partial block = one wave's rows; needs lane runs of 20 / 40 channels
 int gemm_gn_block_rows(int bm, int bn) {
-    if ((bm == 1464 || bm == 2464) && bn == 160) return 32;
-    if ((bm == 24128 || bm == 23256 || bm == 22128) && bn == 160) return 64;
+    if (variant_is_ws(bm) && bn == 160) return (bm == 1464 || bm == 2464) ? 32 : 64;
     if (bm == 7128 || bm == 7328 || bm == 7428) return 32;
     if (bm == 7564) return 16;
     if (bm == 7256 || bm == 7356) return 64;
@@ -483,7 +440,7 @@ int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t s
                   "wrote the rows, or IMH_EW_ROW_STATS); there is no in-loop E[x^2] - mean^2 form");
         return IMH_ERR_ARG;
     }
-    if ((p.flags & (GF_LN_ROW | GF_LN_COL)) && (p.splits > 1 || (bm >= 256 && !((bm == 1464 || bm == 2464 || bm == 24128 || bm == 23256 || bm == 22128 || bm == 26256) && (p.flags & GF_LN_ROW))) || conv)) {
+    if ((p.flags & (GF_LN_ROW | GF_LN_COL)) && (p.splits > 1 || (bm >= 256 && !((variant_is_ws(bm) || bm == 26256) && (p.flags & GF_LN_ROW))) || conv)) {
         set_error("gemm: folded LayerNorm needs a plain 64/128 tile or a wave-specialised variant (row form), splits == 1, no conv (bm=%d splits=%d conv=%d)", bm, p.splits, conv);
         return IMH_ERR_ARG;
     }
@@ -499,7 +456,7 @@ int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t s
     }
     if (p.gn_out) {
         const int rows = gemm_gn_block_rows(bm, bn);
-        const bool halo = bm >= 7000 && bm < 8000;
+        const bool halo = variant_is_halo(bm);
         const int cout = p.phase ? p.pN : p.N;              // (phase form: one block per (rows low-res pixels, phase), 4 gn_hw / rows per sample)
         if (rows == 0 || cout % 10 || cout % (halo ? bn : 80) || p.gn_hw <= 0 || p.gn_hw % rows || p.M % p.gn_hw || p.gn_nblk != (p.phase ? 4 : 1) * (p.gn_hw / rows) ||
             p.splits > 1 || (p.flags & (GF_GEGLU | GF_VT_PERM | GF_OUT_F32 | GF_LN_ROW | GF_LN_COL)) ||
@@ -510,8 +467,7 @@ int gemm_launch(GemmParams p, int dtype, int conv, int bm, int bn, hipStream_t s
         }
     }
     {
-        const bool halo = bm >= 7000 && bm < 8000;
-        const bool ws = bm == 1464 || bm == 2464 || bm == 24128 || bm == 23256 || bm == 22128;
+        const bool halo = variant_is_halo(bm), ws = variant_is_ws(bm);
         if ((p.gn_tab || p.gn_src.partial) && !(conv && halo)) {
             set_error("gemm: the fused GroupNorm front end (gn_tab / gn_part) is a form of the LDS-halo conv3x3 (variant %d)", bm);
             return IMH_ERR_ARG;

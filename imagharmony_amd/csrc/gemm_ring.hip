@@ -10,6 +10,7 @@
 #include "imh_common.h"
 #include "imh_kernels.h"
 #include "imh_gemm_epilogue.h"
+#include "imh_gemm_core.h"
 #include "imh_lnstats.h"
 #include <type_traits>
 
@@ -37,7 +38,6 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
     static_assert(FN == 4 || FN == 2 || FN == 10 || FN == 5, "lane owns 8, 16, 20 or 40 output columns");
     static_assert(BM % RPR == 0 && BN % RPR == 0, "staging rounds");
     static_assert((S - 2) * LP <= 63, "vmcnt range");
-    typedef typename Vec<T>::v8 v8;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -49,11 +49,9 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
     int m0, n0;
     if (!xcd_tile<BM, BN>(p, blockIdx.x, m0, n0)) return;     // the whole workgroup exits together
 
-    const int nkt = p.K / GEMM_BK;
     const int z = blockIdx.y;
-    const int per = (nkt + p.splits - 1) / p.splits;
-    const int kt0 = z * per;
-    const int kt1 = min(nkt, kt0 + per);
+    int kt0, kt1;
+    split_k_range(p, z, kt0, kt1);
     const int nt = max(0, kt1 - kt0);
     const int ph = (CONV && p.phase) ? n0 / p.pN : 0;        // phase form of the upsampler conv: the column tile's phase
 
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
         woff[kk] = tile_off(wr, kk * 4 + (lane >> 4), swz_w(wr, FN));
     }
 
-    f32x4 acc[FM][FN];
+    f32x4 acc[FM][FN];      // (cleared in place, not by acc_zero: behind the function the four-wave 256 x 320 ring spills differently)
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -160,19 +158,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(const GemmPa
             stage(ns, kt0 + t + S - 1);           // refill the slot tile t-1 used
         }
         const unsigned char* xs = smem + slot * STAGE;
-        const unsigned char* ws = xs + XT_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            v8 xf[FM], wf[FN];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) xf[i] = *(const v8*)(xs + xoff[kk] + i * 16 * GEMM_ROW_BYTES);
-#pragma unroll
-            for (int j = 0; j < FN; ++j) wf[j] = *(const v8*)(ws + woff[kk] + j * 4 * GEMM_ROW_BYTES);
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(wf[j], xf[i], acc[i][j]);
-        }
+        mma_ktile<T>(xs, xs + XT_BYTES, xoff, woff, acc);
         asm volatile("" ::: "memory");
         if (++slot == S) slot = 0;
     }
@@ -222,7 +208,6 @@ __global__ __launch_bounds__(512, 2) void gemm_kg2_kernel(const GemmParams p) {
     constexpr int GROUP_BYTES = 2 * STAGE;
     static_assert(FM % 2 == 0, "the two groups split the token fragments");
     static_assert((FM / 2) * FN * 4 * 256 * 4 <= GROUP_BYTES, "exchange buffer fits a group's stages");
-    typedef typename Vec<T>::v8 v8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -235,11 +220,9 @@ __global__ __launch_bounds__(512, 2) void gemm_kg2_kernel(const GemmParams p) {
 
     int m0, n0;
     if (!xcd_tile<BM, BN>(p, blockIdx.x, m0, n0)) return;     // the whole workgroup exits together
-    const int nkt = p.K / GEMM_BK;
     const int z = blockIdx.y;
-    const int per = (nkt + p.splits - 1) / p.splits;
-    const int kt0 = z * per;
-    const int kt1 = min(nkt, kt0 + per);
+    int kt0, kt1;
+    split_k_range(p, z, kt0, kt1);
     const int niter = (max(0, kt1 - kt0) + 1) / 2;    // lockstep iterations; group g takes kt0 + 2*i + g
 
     const unsigned char* zero = g_zero_page;
@@ -314,10 +297,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kg2_kernel(const GemmParams p) {
         woff[kk] = wfrag_off(lane, wn, BN, kk);
     }
     f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
 
     if (niter > 0) {
         if (kt0 + grp < kt1) stage(0, kt0 + grp);
@@ -329,19 +309,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kg2_kernel(const GemmParams p) {
             if (kt + 2 < kt1) stage(cur ^ 1, kt + 2);
             if (kt < kt1) {
                 const unsigned char* xs = gmem + cur * STAGE;
-                const unsigned char* ws = xs + XT_BYTES;
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    v8 xf[FM], wf[FN];
-#pragma unroll
-                    for (int i = 0; i < FM; ++i) xf[i] = *(const v8*)(xs + xoff[kk] + i * 16 * GEMM_ROW_BYTES);
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) wf[j] = *(const v8*)(ws + woff[kk] + j * 4 * GEMM_ROW_BYTES);
-#pragma unroll
-                    for (int i = 0; i < FM; ++i)
-#pragma unroll
-                        for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(wf[j], xf[i], acc[i][j]);
-                }
+                mma_ktile<T>(xs, xs + XT_BYTES, xoff, woff, acc);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -451,11 +419,9 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
 #endif
     int m0, n0;
     if (!xcd_tile<BM, BN>(p, bid, m0, n0)) return;     // the whole workgroup exits together
-    const int nkt = p.K / GEMM_BK;
     const int z = blockIdx.y;
-    const int per = (nkt + p.splits - 1) / p.splits;
-    const int kt0 = z * per;
-    const int kt1 = min(nkt, kt0 + per);
+    int kt0, kt1;
+    split_k_range(p, z, kt0, kt1);
     const int nt = max(0, kt1 - kt0);
     const int ph = (CONV && p.phase) ? n0 / p.pN : 0;        // phase form of the upsampler conv: the column tile's phase (0 otherwise)
 
@@ -573,10 +539,7 @@ __device__ __forceinline__ void gemm_ws_body(const GemmParams& p, const int bid,
         woff[kk] = XT_BYTES + tile_off(wr, kk * 4 + (lane >> 4), swz_w(wr, FN));
     }
     f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
     v8 xf[2][FM], wf[2][FN];                       // register set kk holds k step kk of the tile being consumed
     auto rd = [&](auto KK, int slot) {
         constexpr int kk = decltype(KK)::value;
@@ -947,16 +910,8 @@ __global__ __launch_bounds__(512, 1) void gemm_ws_dual_kernel(const GemmParams a
 
 template <typename T>
 static int launch_ws_dual(const GemmParams& a, const GemmParams& b, hipStream_t stream) {
-    GemmParams qa = a, qb = b;
-    int ga, gb;
-    xcd_partition(qa, 128, 160, &ga);
-    xcd_partition(qb, 128, 128, &gb);
     const size_t smem = 4 * (size_t)(128 + 160) * GEMM_ROW_BYTES + 128 * 8;
-    auto kern = gemm_ws_dual_kernel<T>;
-    static DynLdsOnce lds_once;
-    lds_once.ensure((const void*)kern, (int)smem);
-    hipLaunchKernelGGL(kern, dim3(ga + gb), dim3(512), smem, stream, qa, qb, ga);
-    return check_launch("gemm_ws_dual_kernel");
+    return launch_gemm_pair<gemm_ws_dual_kernel<T>>(a, 128, 160, b, 128, 128, 512, smem, true, "gemm_ws_dual_kernel", stream);
 }
 
 int gemm_ws_dual_launch(const GemmParams& a, const GemmParams& b, int dtype, hipStream_t stream) {
@@ -971,15 +926,8 @@ int gemm_ws_dual_launch(const GemmParams&, const GemmParams&, int, hipStream_t) 
 
 template <typename T, int BM, int BN, int CM, int CN, int S, int NP, bool CONV, int LN, int OCC = 1>
 static int launch_ws_ln(const GemmParams& p, hipStream_t stream) {
-    GemmParams q = p;
-    int tiles;
-    xcd_partition(q, BM, BN, &tiles);
     const size_t smem = (size_t)S * (BM + BN) * GEMM_ROW_BYTES + (LN == 1 ? BM * 8 : (LN == 2 ? BN * 8 : 0));
-    auto kern = gemm_ws_kernel<T, BM, BN, CM, CN, S, NP, CONV, LN, OCC>;
-    static DynLdsOnce lds_once;
-    lds_once.ensure((const void*)kern, (int)smem);
-    hipLaunchKernelGGL(kern, dim3(tiles, p.splits, 1), dim3(64 * (CM * CN + NP)), smem, stream, q);
-    return check_launch("gemm_ws_kernel");
+    return launch_gemm<gemm_ws_kernel<T, BM, BN, CM, CN, S, NP, CONV, LN, OCC>>(p, BM, BN, 64 * (CM * CN + NP), smem, true, "gemm_ws_kernel", stream);
 }
 
 template <typename T, int BM, int BN, int CM, int CN, int S, int NP, bool CONV, int OCC = 1>
@@ -992,28 +940,14 @@ static int launch_ws(const GemmParams& p, hipStream_t stream) {
 
 template <typename T, int BM, int BN, bool CONV>
 static int launch_kg2(const GemmParams& p, hipStream_t stream) {
-    GemmParams q = p;
-    int tiles;
-    xcd_partition(q, BM, BN, &tiles);
     const size_t smem = 2 * 2 * (size_t)(BM + BN) * GEMM_ROW_BYTES;
-    auto kern = gemm_kg2_kernel<T, BM, BN, CONV>;
-    static DynLdsOnce lds_once;
-    lds_once.ensure((const void*)kern, (int)smem);
-    hipLaunchKernelGGL(kern, dim3(tiles, p.splits, 1), dim3(512), smem, stream, q);
-    return check_launch("gemm_kg2_kernel");
+    return launch_gemm<gemm_kg2_kernel<T, BM, BN, CONV>>(p, BM, BN, 512, smem, true, "gemm_kg2_kernel", stream);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int S, bool CONV>
 static int launch_ring(const GemmParams& p, hipStream_t stream) {
-    GemmParams q = p;
-    int tiles;
-    xcd_partition(q, BM, BN, &tiles);
     const size_t smem = (size_t)S * (BM + BN) * GEMM_ROW_BYTES;
-    auto kern = gemm_ring_kernel<T, BM, BN, WM, WN, S, CONV>;
-    static DynLdsOnce lds_once;
-    lds_once.ensure((const void*)kern, (int)smem);
-    hipLaunchKernelGGL(kern, dim3(tiles, p.splits, 1), dim3(64 * WM * WN), smem, stream, q);
-    return check_launch("gemm_ring_kernel");
+    return launch_gemm<gemm_ring_kernel<T, BM, BN, WM, WN, S, CONV>>(p, BM, BN, 64 * WM * WN, smem, true, "gemm_ring_kernel", stream);
 }
 
 // variant codes (bm field of the config): 256 -> ring 256x{128,256}; 3128 / 3064 -> KG2 128x128 / 64x64.

@@ -61,6 +61,11 @@ struct GemmParams {
     int early_res;         // wave-specialised kernels: fetch the residual rows / bias BEFORE the K loop (set by the launcher; g_ws_early)
 };
 
+// variant codes (the bm field of a tile config) by kernel family: the wave-specialised kernels of gemm_ring.hip, and the code range of the
+// LDS-halo conv3x3 (conv_halo.hip)
+inline bool variant_is_ws(int bm) { return bm == 1464 || bm == 2464 || bm == 24128 || bm == 23256 || bm == 22128; }
+inline bool variant_is_halo(int bm) { return bm >= 7000 && bm < 8000; }
+
 void gemm_pick_config(int M, int N, int K, int* bm, int* bn, int* splits);
 size_t gemm_workspace_bytes(int M, int N, int splits);
 int gemm_stats_slot_width(int bm, int bn);       // channels per ln_stats_out slot of a tile variant, 0 = no statistics epilogue

@@ -6,9 +6,10 @@ and the one rounding to T has one right result.  A dropped K element in one ragg
 add, a stale ring slot: each changes some element, and equality sees it -- where the k * EPS * max|ref| bound of test_gpu_ops.assert_close
 passes all three.  out_f32 is the bit-exact proof of every variant's accumulator.
 
-Variants: dispatch_matrix.gemm_variants(built(BIG_VARIANTS)) -- the plain tiles at splits 1 / 2 / 4, every ring / KG2 / ping-pong variant, the
-wave-specialised set, the sixteen-wave tile.  A cell runs on a variant iff cell.variant_ok(cfg) (Ctx's own gate); a refusal of an approved cell
-is a failure.  The sixteen-wave tile (26256 x 320) serves folded-LayerNorm launches only, whose arithmetic is inexact by nature: Ctx approves
+Variants: dispatch_matrix.gemm_variants(built(BIG_VARIANTS + SPLIT_K)) -- the plain tiles at splits 1 / 2 / 4, every ring / KG2 / ping-pong
+variant, the wave-specialised set, the sixteen-wave tile, and split-K off the plain tiles: BIG_VARIANTS holds the wave-specialised
+(2464, 160, 2), SPLIT_K adds one ring and one KG2 variant at splits = 2 (the split-K range and the fp32 slab store inside those three
+pipelines: 512 x 640 x 128 gives one K tile per split, 300 x 200 x 192 a 2 + 1 split with ragged edges).  A cell runs on a variant iff cell.variant_ok(cfg) (Ctx's own gate); a refusal of an approved cell is a failure.  The sixteen-wave tile (26256 x 320) serves folded-LayerNorm launches only, whose arithmetic is inexact by nature: Ctx approves
 none of the exact features for it, the test asserts exactly that, and its accumulator stays under test_gemm_sixteen_wave_256x320_tile.
 
 Shapes (exact_operands.GEMM_SHAPES): whole tiles, ragged M and N, fewer rows than one MFMA with one K tile, and K_DEEP = 576: nine K tiles, more
@@ -28,7 +29,9 @@ from test_gpu_ops import BIG_VARIANTS, DTYPES, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GEMM_V = dm.gemm_variants(built(BIG_VARIANTS))
+SPLIT_K = [(5064, 64, 2), (3064, 64, 2)]                            # ring, KG2 at splits = 2 (the wave-specialised (2464, 160, 2) is in BIG_VARIANTS)
+assert (2464, 160, 2) in BIG_VARIANTS
+GEMM_V = dm.gemm_variants(built(BIG_VARIANTS + SPLIT_K))
 NO_EXACT_FORM = [v for v in GEMM_V if v[0] in dm.Ctx._W16]          # folded-LayerNorm launches only
 RAN = collections.Counter()                                          # cfg -> (feature, shape, dtype) cells run
 CANCEL_SHAPES = [s for s in exo.GEMM_SHAPES if s[2] >= 128]
