@@ -133,13 +133,17 @@ __device__ __forceinline__ float to_f32(bf16_t x) { return (float)x; }
 __device__ __forceinline__ float to_f32(f16_t x) { return (float)x; }
 template <typename T> __device__ __forceinline__ T from_f32(float x) { return (T)x; }
 
-// x * sigmoid(x) as 1 mul + v_exp + add + v_rcp + mul (an IEEE divide here costs ~10 more instructions; the result is rounded to
-// bf16 / fp16 anyway); exp2 overflow for x << 0 gives rcp(inf) = 0 -> -0, the limit
+// x * sigmoid(x) as 1 fma + v_exp + add + v_rcp + 2 mul (an IEEE divide here costs ~10 more instructions; the result is rounded to
+// bf16 / fp16 anyway).  The denominator is carried as (1 + 2^t) / 4 (the -2 rides in the exponent's fma, the 1/4 goes back on in one
+// multiply): v_rcp_f32 flushes a denormal RESULT, so rcp(1 + 2^t) was 0 from t = 126 on -- x = -87.5 came out as -0 where
+// silu(x) = -8.7e-37 is a normal bf16 value (tests/test_gpu_pointwise_values.py).  Scaled, the flush starts at t = 128 (x = -88.7),
+// where |silu(x)| <= 2.6e-37 is below every value the tests distinguish from the limit -0; v_mul_f32 keeps the denormal 1 / (1 + 2^t)
 __device__ __forceinline__ float silu_f(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+    return x * (0.25f * __builtin_amdgcn_rcpf(0.25f + __builtin_amdgcn_exp2f(__builtin_fmaf(x, -1.4426950408889634f, -2.0f))));
 }
-// quick-GELU x * sigmoid(1.702 x) (transformers QuickGELUActivation, CLIP-L's hidden_act), the same five instructions with the
-// factor folded into the exponent's constant: 1.702 * log2(e)
+// quick-GELU x * sigmoid(1.702 x) (transformers QuickGELUActivation, CLIP-L's hidden_act), mul + v_exp + add + v_rcp + mul with the
+// factor folded into the exponent's constant: 1.702 * log2(e).  (Unscaled: where rcp's result would be denormal, t >= 126, |qgelu(x)|
+// is below 6.1e-37 already.)
 __device__ __forceinline__ float qgelu_f(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -2.4554669595930157f));
 }
