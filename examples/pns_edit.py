@@ -8,12 +8,14 @@ whole path (PIL in -> CLIP-shaped embeddings -> HarmonyAttention + ImageProjMode
                                 [--scheduler euler-a --step-noise seed]
                                 [--init-image in.png --strength 0.6] [--clip-backend hip --judge-preprocess hip]
                                 [--preview-vae taesdxl.safetensors | --preview-vae random]
+                                [--freeu 0.6 0.4 1.1 1.2]
 
 With --init-image the candidates are image-to-image EDITS of that image (IPAdapterXL.generate_pns(image=, strength=)): every seed fixes its
 posterior and add-noise draws, the previews are decoded and scored by the CLIP judge when a tower is attached (--clip-backend), and
 --judge-preprocess hip takes the decoded previews to the HIP tower's patch rows in one launch.  --preview-vae lets the judge see the
 previews through AutoencoderTiny (diffusers' TAESDXL decoder, 35 small launches per decode) instead of the full VAE; the winner's image
-still comes from the full VAE.
+still comes from the full VAE.  --freeu S1 S2 B1 B2 switches FreeU on (pipe.enable_freeu, diffusers' argument order; SDXL's published
+values are 0.6 0.4 1.1 1.2): previews and finals alike run the UNet with the re-weighted skip concats of its first two up blocks.
 
 Launch under torch.distributed.run with N ranks to shard the seeds over N GPUs (one process per GPU, RCCL).
 """
@@ -69,6 +71,8 @@ def main():
     ap.add_argument("--preview-vae", nargs="?", const="random", default=None, metavar="PATH",
                     help="with --init-image and a CLIP tower: decode the judge's previews with AutoencoderTiny -- PATH = a diffusers taesdxl "
                          "safetensors file; no value or `random` = seeded random weights")
+    ap.add_argument("--freeu", type=float, nargs=4, metavar=("S1", "S2", "B1", "B2"), default=None,
+                    help="FreeU: skip scales s1, s2 and backbone scales b1, b2 of up blocks 0 and 1 (SDXL: 0.6 0.4 1.1 1.2)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -91,6 +95,8 @@ def main():
     pipe_cls = StableDiffusionXLImg2ImgCustomPipeline if a.init_image else StableDiffusionXLCustomPipeline
     pipe = pipe_cls(unet, scheduler=SCHEDULERS[a.scheduler](), device=dev, dtype=dtype, vae=vae)
     pipe.enable_vae_tiling()                                              # test.py:73
+    if a.freeu:
+        pipe.enable_freeu(*a.freeu)
     ha = HarmonyAttention(image_hidden_size=1280, text_context_dim=2048, inter_dim=2560, cross_heads=8, reshape_blocks=8,
                           cross_value_dim=64, scale=1.0, fusion_method="cross_attention")     # test.py:82-91
     ip = IPAdapterXL(pipe, None, a.ip_ckpt, dev, num_tokens=4, inference=True, number_class_crossattention=ha, dtype=dtype)

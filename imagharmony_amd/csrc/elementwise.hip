@@ -92,6 +92,165 @@ __global__ void concat_kernel(const EwParams p) {
     }
 }
 
+// EW_CONCAT, the FreeU form (imh.h; i2 = H > 0, i3 = W): diffusers' apply_freeu at the up blocks' torch.cat([hidden, skip], 1),
+//   y[pix, c]      = round_T(a[pix, c] * f0)            c <  i4        (the backbone scale b on the leading hidden channels)
+//   y[pix, c]      = a[pix, c]                          i4 <= c < C1
+//   y[pix, C1 + c] = round_T(x + (f1 - 1) * low(x))     x = b[pix, c]  (fourier_filter(threshold = 1, scale = s = f1) of the skip)
+// With threshold 1 the mask keeps the frequency pairs {-1, 0} x {-1, 0}, so per (sample, channel) plane, with t = 2 pi y / H and
+// u = 2 pi x / W, low is the real part of four Fourier components and needs seven plane sums:
+//   HW * low(y, x) = S + (Ac cos t + As sin t) + (Bc cos u + Bs sin u) + (Dc cos(t + u) + Ds sin(t + u)),
+//   S = sum x, (Ac, As) = sum x (cos t, sin t), (Bc, Bs) = sum x (cos u, sin u), (Dc, Ds) = sum x (cos, sin)(t + u).
+// One workgroup owns FREEU_LANES channel quads (32 bytes per pixel) of every pixel of one sample: four lanes per pixel, 256 pixels per
+// sweep (8-byte loads, eight sweeps in flight).  Pass 1 sweeps the slab and keeps the 7 x 4 sums per lane; they are merged by a fixed butterfly inside the wave and in wave
+// order across the workgroup through LDS (no atomics, no workspace: the bits depend on nothing but the operands).  Pass 2 reads the
+// slab again -- from the XCD's L2, which the same CU has just filled; a slab is 32 B x HW, 32 to 512 KiB at the SDXL shapes -- and
+// stores the filtered values.  cos / sin of t and u come from per-workgroup tables in LDS (H + W sincospi calls instead of two per
+// pixel), cos / sin of t + u from the angle-sum identity.  The hidden channels are a scaled copy by the workgroups behind the slab
+// owners.
+// Sums, tables and the evaluation of low are float64, and the result is rounded to T once (through fp32 rounded to odd).  fp32 would
+// not do: where x and (s - 1) * low cancel -- one element in 10^5 lands 2^-15 below |x| -- an ulp of the RESULT is 2^-23 |x| in bf16,
+// the size of ONE fp32 rounding of the plane sums, and the launch is held to 1 ulp of the float64 statement
+// (tests/test_gpu_freeu.py; an fp32 FFT is 89 ulp off at such an element).  At 14 fp64 multiply-adds per element the arithmetic
+// stays below the launch's memory time.  LDS: 2 (H + W) + 1904 doubles (16.9 KiB at 64 x 64).
+constexpr int FREEU_THREADS = 1024, FREEU_LANES = 4, FREEU_SUMS = 7;
+constexpr int FREEU_COEF = FREEU_LANES * FREEU_SUMS * 4;                             // merged sums of a slab
+constexpr int FREEU_RED = (FREEU_THREADS / 64 + 1) * FREEU_COEF;                     // per-wave partials, then the merged coefficients
+
+static inline size_t freeu_lds_bytes(int H, int W) { return ((size_t)2 * (H + W) + FREEU_RED) * sizeof(double); }
+
+// float64 -> T with ONE rounding: to fp32 rounded to odd (the inexact bit survives in the last place), then the usual nearest-even
+template <typename T>
+__device__ __forceinline__ T from_f64(double d) {
+    const double ad = fabs(d);
+    float af = (float)ad;
+    if ((double)af != ad && !(__float_as_uint(af) & 1u)) af = __uint_as_float(__float_as_uint(af) + ((double)af < ad ? 1u : 0xffffffffu));
+    return from_f32<T>(copysignf(af, (float)d));
+}
+
+template <typename T>
+__global__ __launch_bounds__(FREEU_THREADS) void freeu_concat_kernel(const EwParams p, int slabs_per_sample, int nslab) {
+    typedef typename Vec<T>::v8 v8;
+    typedef typename Vec<T>::v4 v4;
+    extern __shared__ double fl[];
+    const int c1 = p.i0 >> 3, ct = (p.i0 + p.i1) >> 3;
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= nslab) {
+        // the hidden half: channels [0, i4) scaled in fp32 and rounded once (torch's a[..., :i4] * b in T), the rest copied
+        // (four vectors in flight per thread: these workgroups run at the filter's register budget, one per CU)
+        const long long total = p.n * c1, nthr = (long long)(gridDim.x - nslab) * FREEU_THREADS;
+        for (long long i0 = (long long)(blockIdx.x - nslab) * FREEU_THREADS + tid; i0 < total; i0 += 4 * nthr) {
+            v8 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u * nthr < total) v[u] = ((const v8*)p.a)[i0 + u * nthr];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const long long i = i0 + u * nthr;
+                if (i >= total) break;
+                const long long pix = i / c1;
+                const int c = (int)(i - pix * c1) * 8;
+                if (c < p.i4) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (c + e < p.i4) v[u][e] = from_f32<T>(to_f32(v[u][e]) * p.f0);
+                }
+                ((v8*)p.y)[pix * ct + (c >> 3)] = v[u];
+            }
+        }
+        return;
+    }
+    const int H = p.i2, W = p.i3, HW = H * W;
+    const int q2 = p.i1 >> 2, qt = (p.i0 + p.i1) >> 2;       // channel quads of the skip and of y
+    double* cy = fl;
+    double* sy = cy + H;
+    double* cx = sy + H;
+    double* sx = cx + W;
+    double* red = sx + W;
+    double* coef = red + (FREEU_THREADS / 64) * FREEU_COEF;
+    for (int i = tid; i < H; i += FREEU_THREADS) sincospi(2.0 * (double)i / (double)H, sy + i, cy + i);
+    for (int i = tid; i < W; i += FREEU_THREADS) sincospi(2.0 * (double)i / (double)W, sx + i, cx + i);
+    __syncthreads();
+    // slab order: workgroups that share an XCD (blockIdx % 8, as the dispatcher is observed to deal them; speed only) take neighbouring
+    // slabs, so that the four slabs of a 128-byte line are fetched into one L2
+    const int xcd = blockIdx.x & 7, chunk = nslab >> 3, rem = nslab & 7;
+    const int slab = xcd * chunk + (xcd < rem ? xcd : rem) + (blockIdx.x >> 3);
+    const int smp = slab / slabs_per_sample;
+    const int q = tid & (FREEU_LANES - 1), quad = (slab - smp * slabs_per_sample) * FREEU_LANES + q;
+    const bool live = quad < q2;                    // (the last slab of a sample may be narrower)
+    const v4* src = (const v4*)p.b + (long long)smp * HW * q2 + quad;
+    constexpr int PR = FREEU_THREADS / FREEU_LANES; // pixels per sweep
+    double acc[FREEU_SUMS][4];
+#pragma unroll
+    for (int k = 0; k < FREEU_SUMS; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[k][e] = 0.0;
+    if (live) {
+#pragma unroll 8
+        for (int px = tid / FREEU_LANES; px < HW; px += PR) {
+            const v4 v = src[(long long)px * q2];
+            const int yy = px / W, xx = px - yy * W;
+            const double ct_ = cy[yy], st_ = sy[yy], cu = cx[xx], su = sx[xx];
+            const double cd = ct_ * cu - st_ * su, sd = st_ * cu + ct_ * su;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double f = (double)to_f32(v[e]);
+                acc[0][e] += f;
+                acc[1][e] = fma(f, ct_, acc[1][e]);
+                acc[2][e] = fma(f, st_, acc[2][e]);
+                acc[3][e] = fma(f, cu, acc[3][e]);
+                acc[4][e] = fma(f, su, acc[4][e]);
+                acc[5][e] = fma(f, cd, acc[5][e]);
+                acc[6][e] = fma(f, sd, acc[6][e]);
+            }
+        }
+    }
+    // lanes q, q + 4, .. of a wave hold the same channels: butterfly over the sixteen, then the waves in order
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < FREEU_SUMS; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            double v = acc[k][e];
+#pragma unroll
+            for (int o = FREEU_LANES; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+            acc[k][e] = v;
+        }
+    if (lane < FREEU_LANES) {
+#pragma unroll
+        for (int k = 0; k < FREEU_SUMS; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) red[((wave * FREEU_LANES + lane) * FREEU_SUMS + k) * 4 + e] = acc[k][e];
+    }
+    __syncthreads();
+    if (tid < FREEU_COEF) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < FREEU_THREADS / 64; ++w) s += red[w * FREEU_COEF + tid];
+        coef[tid] = s * (((double)p.f1 - 1.0) / (double)HW);
+    }
+    __syncthreads();
+    if (!live) return;
+#pragma unroll
+    for (int k = 0; k < FREEU_SUMS; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[k][e] = coef[(q * FREEU_SUMS + k) * 4 + e];
+    v4* dst = (v4*)p.y + (long long)smp * HW * qt + (p.i0 >> 2) + quad;
+#pragma unroll 4
+    for (int px = tid / FREEU_LANES; px < HW; px += PR) {
+        const v4 v = src[(long long)px * q2];
+        const int yy = px / W, xx = px - yy * W;
+        const double ct_ = cy[yy], st_ = sy[yy], cu = cx[xx], su = sx[xx];
+        const double cd = ct_ * cu - st_ * su, sd = st_ * cu + ct_ * su;
+        v4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double low = acc[0][e] + (acc[1][e] * ct_ + acc[2][e] * st_) + (acc[3][e] * cu + acc[4][e] * su) + (acc[5][e] * cd + acc[6][e] * sd);
+            o[e] = from_f64<T>((double)to_f32(v[e]) + low);
+        }
+        dst[(long long)px * qt] = o;
+    }
+}
+
 // conv_in: a = latents fp32 NCHW [S, 4, H, W]; w = weights T [C0][CIN][3][3]; bias T [C0];
 // y = NHWC T [Bout, H, W, C0] with Bout = i4 (batch b reads latent b % S: CFG duplication).
 // i0 = S, i1 = H, i2 = W, i3 = C0, f0 = input scale.  Eight threads per pixel, each 8 channels at a time.
@@ -490,6 +649,25 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
             break;
         case EW_CONCAT:
             if ((p.i0 & 7) || (p.i1 & 7)) { set_error("concat: channel counts must be multiples of 8"); return IMH_ERR_SHAPE; }
+            if (p.i2 > 0) {         // the FreeU form (imh.h): i2 = H, i3 = W, i4 = scaled hidden channels, f0 = b, f1 = s
+                const long long hw = (long long)p.i2 * p.i3;
+                if (p.i0 < 0 || p.i1 < 0 || p.i4 < 0 || p.i4 > p.i0) {
+                    set_error("concat: FreeU scales i4 = %d leading channels of the %d hidden ones (0 <= i4 <= i0)", p.i4, p.i0); return IMH_ERR_SHAPE;
+                }
+                if (p.i2 < 2 || p.i3 < 2 || p.n < 0 || p.n % hw) {
+                    set_error("concat: FreeU planes are H = %d x W = %d (both >= 2) and tile the n = %lld pixels", p.i2, p.i3, p.n); return IMH_ERR_SHAPE;
+                }
+                const size_t lds = freeu_lds_bytes(p.i2, p.i3);
+                const int spb = ((p.i1 >> 2) + FREEU_LANES - 1) / FREEU_LANES;
+                const long long nslab = p.n / hw * spb;
+                if (hw > 0x7fffffffLL || lds > 64 * 1024 || nslab > 0x3fffffffLL) {
+                    set_error("concat: FreeU planes of %d x %d over %lld pixels are beyond the launch (H + W <= 3000, H * W < 2^31)", p.i2, p.i3, p.n); return IMH_ERR_SHAPE;
+                }
+                if ((p.i0 && !p.a) || (p.i1 && !p.b)) { set_error("concat: null source"); return IMH_ERR_ARG; }
+                const int ncopy = p.i0 ? std::min(grid_for((p.n * (p.i0 >> 3) + 3) / 4, FREEU_THREADS), 768) : 0;
+                hipLaunchKernelGGL((freeu_concat_kernel<T>), dim3(std::max((int)nslab + ncopy, 1)), dim3(FREEU_THREADS), lds, stream, p, std::max(spb, 1), (int)nslab);
+                break;
+            }
             hipLaunchKernelGGL((concat_kernel<T>), dim3(grid_for(p.n * ((p.i0 + p.i1) >> 3), 256)), dim3(256), 0, stream, p);
             break;
         case EW_CONV_IN: {

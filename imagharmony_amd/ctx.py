@@ -1228,12 +1228,26 @@ class Ctx:
         out = self.new(*x.shape)
         return self.ew(L.EW_SILU, out, a=x, n=x.numel(), descr=descr, nbytes=2.0 * x.numel() * x.element_size())
 
-    def concat(self, a, b, descr="concat"):
-        """NHWC channel concat: a [..., C1], b [..., C2] -> [..., C1 + C2]."""
+    def concat(self, a, b, descr="concat", freeu=None):
+        """NHWC channel concat: a [..., C1], b [..., C2] -> [..., C1 + C2].
+        freeu = (scaled, b, s): the FreeU form of the launch (imh.h IMH_EW_CONCAT with i2 > 0; freeu.py states it) on a [B, H, W, C1],
+        b [B, H, W, C2] -- the first `scaled` channels of a times b, b through fourier_filter(threshold 1, scale s), then the concat.
+        None: the launch as it always was."""
         c1, c2 = a.shape[-1], b.shape[-1]
         pix = a.numel() // c1
+        hw = (0, 0, 0)
+        if freeu is not None:
+            scaled, fb, fs = freeu
+            if a.dim() != 4 or b.dim() != 4 or tuple(a.shape[:3]) != tuple(b.shape[:3]) or not (a.is_contiguous() and b.is_contiguous()):
+                raise L.ImhError(f"{descr}: the FreeU concat takes dense NHWC [B, H, W, C] pairs of one grid, got {tuple(a.shape)} and {tuple(b.shape)}")
+            self._chk(a, f"{descr}.a"); self._chk(b, f"{descr}.b")
+            if not 0 <= int(scaled) <= c1 or a.shape[1] < 2 or a.shape[2] < 2 or c1 % 8 or c2 % 8:
+                raise L.ImhError(f"{descr}: FreeU over {tuple(a.shape)} | {tuple(b.shape)} with {scaled} scaled channels "
+                                 f"(H, W >= 2; channels multiples of 8; 0 <= scaled <= {c1})")
+            hw = (int(a.shape[1]), int(a.shape[2]), int(scaled))
         out = self.new(*a.shape[:-1], c1 + c2)
-        return self.ew(L.EW_CONCAT, out, a=a, b=b, n=pix, i=(c1, c2, 0, 0, 0, 0), descr=descr,
+        return self.ew(L.EW_CONCAT, out, a=a, b=b, n=pix, i=(c1, c2) + hw + (0,), descr=descr,
+                       f=(float(freeu[1]), float(freeu[2]), 0.0, 0.0) if freeu is not None else (0.0, 0.0, 0.0, 0.0),
                        nbytes=2.0 * out.numel() * out.element_size())
 
     # ------------------------------------------------------------------ weight prefetch

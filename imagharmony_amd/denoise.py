@@ -54,15 +54,27 @@ _PLAN_ENGINE = ("steps", "init_noise_sigma", "plan", "noise_pred", "plan_tail", 
 _KEY_FIELDS = ("scheduler num_train_timesteps num_inference_steps control_guidance_start control_guidance_end "
                "denoising_end ip_scale steps tables controlnet inpaint adapter seeded")
 PlanKeyRegions = collections.namedtuple("PlanKeyRegions", _KEY_FIELDS + " regions")
+#   freeu (the UNet's (s1, s2, b1, b2), unet.enable_freeu) -- the same way: a trailing field that exists only on the key of a plan recorded
+#   with FreeU enabled, behind regions where both are set; a key without it is the tuple it always was and ``.freeu`` reads None
+PlanKeyFreeU = collections.namedtuple("PlanKeyFreeU", _KEY_FIELDS + " freeu")
+PlanKeyFreeU.regions = None
+PlanKeyRegions.freeu = None
+PlanKeyRegionsFreeU = collections.namedtuple("PlanKeyRegionsFreeU", _KEY_FIELDS + " regions freeu")
 
 
 class PlanKey(collections.namedtuple("PlanKey", _KEY_FIELDS)):
     __slots__ = ()
     regions = None
+    freeu = None
 
-    def __new__(cls, *args, regions=None, **kw):
+    def __new__(cls, *args, regions=None, freeu=None, **kw):
         if len(args) == len(cls._fields) + 1:
             args, regions = args[:-1], args[-1]
+        if freeu is not None:
+            freeu = tuple(float(v) for v in freeu)
+            if regions is not None:
+                return PlanKeyRegionsFreeU(*args, **kw, regions=regions, freeu=freeu)
+            return PlanKeyFreeU(*args, **kw, freeu=freeu)
         if regions is None:
             return super().__new__(cls, *args, **kw)
         return PlanKeyRegions(*args, **kw, regions=regions)
@@ -427,7 +439,7 @@ class DenoiseEngine:
         key = PlanKey(type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps),
                       float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(),
                       controlnet=cn_key, inpaint=mode, adapter=ad_key, seeded=seeded,
-                      regions=self.regions.digest() if self.regions is not None else None)
+                      regions=self.regions.digest() if self.regions is not None else None, freeu=getattr(self.unet, "freeu", None))
         self.t_start = t_start
         self.inpaint = mode
         self.general = general

@@ -203,6 +203,14 @@ class StableDiffusionXLCustomPipeline(LoRAPipelineMixin):
         if self.vae is not None:
             self.vae.enable_tiling(False)
 
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' pipe.enable_freeu: delegates to the UNet (unet.UNet2DConditionModel.enable_freeu); the next call records -- or
+        picks from the engine's cache -- the plan of that setting.  SDXL's published values: s1 = 0.6, s2 = 0.4, b1 = 1.1, b2 = 1.2."""
+        self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
+
     def set_scale(self, scale):                                           # custom_pipelines.py:17-20
         for p in self.unet.attn_processors.values():
             if isinstance(p, IPAttnProcessor):

@@ -838,6 +838,24 @@ class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
         for blk in self.up_blocks:
             yield from blk.resnets
 
+    # ---- FreeU (diffusers enable_freeu / disable_freeu; freeu.py states the arithmetic) ----
+    freeu = None             # (s1, s2, b1, b2) or None: part of what a recorded plan is (denoise.PlanKey)
+
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' UNet2DConditionModel.enable_freeu: in every ResNet of up block 0 the first half of the hidden channels is scaled
+        by b1 and the skip tensor goes through fourier_filter(threshold = 1, scale = s1) before torch.cat([hidden, skip], 1); up block
+        1 the same with (b2, s2); later up blocks are untouched.  SDXL's published values: s1 = 0.6, s2 = 0.4, b1 = 1.1, b2 = 1.2.
+        Takes effect at the next recording (DenoiseEngine.set_schedule sees the change) and in the eager forward."""
+        self.freeu = tuple(float(v) for v in (s1, s2, b1, b2))
+
+    def disable_freeu(self):
+        self.freeu = None
+
+    def _freeu_of(self, bi):
+        """(b, s) of up block bi under the current setting, or None (diffusers apply_freeu: resolution_idx 0 and 1 only)"""
+        from .freeu import unet_settings
+        return unet_settings(self.freeu, bi)
+
     # ---- the forward, as emitted ops ----
     def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None, adapter=None):
         """Records one UNet forward.  Reads st.latents (fp32 NCHW [S,4,Hl,Wl]); batch B = 2S when
@@ -887,7 +905,17 @@ class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
         for bi, blk in enumerate(self.up_blocks):
             for i, r in enumerate(blk.resnets):
                 ctx.tag = 40 + bi
-                h = r.emit(ctx, h, st, skip=skips.pop())      # torch.cat([hidden, skip], 1) is read from its two producers
+                fu = self._freeu_of(bi)
+                if fu is not None:
+                    # FreeU acts at the concat, so here it is an op of its own: one launch scales half of the hidden channels, filters
+                    # the skip and writes the concatenated tensor, which the ResNet then takes as a single input (its norm1 statistics
+                    # from one statistics pass; conv1 and the shortcut read the materialised tensor)
+                    sk = skips.pop()
+                    cat = Feat(ctx.concat(h.t, sk.t, descr="freeu.concat", freeu=(h.t.shape[-1] // 2, fu[0], fu[1])))
+                    h.free(ctx); sk.free(ctx)
+                    h = r.emit(ctx, cat, st)
+                else:
+                    h = r.emit(ctx, h, st, skip=skips.pop())      # torch.cat([hidden, skip], 1) is read from its two producers
                 if blk.has_attn:
                     ctx.tag = 50 + bi
                     h = blk.attentions[i].emit(ctx, h, self._kv_of(st, blk.attentions[i]), st)

@@ -429,7 +429,20 @@ int imh_layernorm(const imh_norm_args* a, void* stream);
 enum imh_ew_op {
     IMH_EW_TIMESTEP = 0,  /* diffusers Timesteps() sinusoid */
     IMH_EW_SILU = 1,
-    IMH_EW_CONCAT = 2,    /* NHWC channel concat (up-block skips) */
+    IMH_EW_CONCAT = 2,    /* NHWC channel concat (up-block skips): y[pix, 0:i0] = a[pix], y[pix, i0:i0+i1] = b[pix], n pixels; i0, i1 multiples of 8.
+                           * Additive, ABI unchanged -- the FreeU form, selected by i2 > 0 (i2 == 0: the op as it was, same kernel): diffusers'
+                           * apply_freeu at that concat.  i2 = H, i3 = W (both >= 2, any value; n % (H * W) == 0: n / (H * W) samples),
+                           * i4 = leading channels of `a` that are scaled (0 <= i4 <= i0, any value), f0 = backbone scale b, f1 = skip scale s:
+                           *   y[pix, c] = round_T(float(a[pix, c]) * f0) for c < i4 (torch's a[..., :i4] * b in T, bit for bit), a[pix, c] for i4 <= c < i0;
+                           *   y[pix, i0 + c] = round_T(x + (f1 - 1) * low), x = b[pix, c]: fourier_filter(x, threshold = 1, scale = s) per (sample,
+                           *   channel) plane, whose mask keeps the frequency pairs {-1, 0} x {-1, 0} (asymmetric, as upstream: a real cosine of
+                           *   frequency 1 keeps weight 1 / 2),
+                           *     low(y, x) = Re((1 / HW) * sum over (u, v) in {-1, 0}^2 of X[u, v] * exp(2 pi i (u y / H + v x / W))),
+                           *   evaluated in float64 from float64 plane sums taken in a fixed order (no atomics, no workspace: the same bits on
+                           *   every call, eager or from a plan), one rounding at the end -- where x and (s - 1) * low cancel, an ulp of the
+                           *   result is smaller than one fp32 rounding of the sums.  imagharmony_amd/freeu.py restates it in numpy float64.
+                           * Refused without a launch (the text names `concat`): i0 / i1 no multiples of 8, i4 outside [0, i0], H or W < 2,
+                           * H * W not dividing n, H + W beyond the tables' LDS (about 3000). */
     IMH_EW_CONV_IN = 3,   /* conv_in + CFG duplication (custom_pipelines.py:332) + scale_model_input (:334).  ABI 11: i5 = input channels, 0 | 4 (the
                            * latents alone) or 9 (the SDXL inpainting UNet): channels 4-8 = [mask | masked-image latents] come unscaled from `x2`,
                            * fp32 NCHW [i0, 5, H, W], the same at every step; w is then [C0][9][3][3] */
@@ -491,7 +504,8 @@ typedef struct imh_ew_args {
  * IMH_EW_STEP_ROW reads row *step of `a` only; `tab` / `blend_tab` are read at row *step only; IMH_EW_GATHER_ROWS reads idx[0, n), columns
  * [0, C) of the table rows idx names and of add's rows [0, min(n, P)), and writes columns [0, C) of y's rows [0, n).  IMH_EW_CFG_MSTEP reads
  * its six-column `tab` and the noise bank `bias` at row *step only (6 floats and i0 * 4 * i1 floats), and reads and writes exactly the
- * i0 * 4 * i1 elements of y and of the history buffer `b`. */
+ * i0 * 4 * i1 elements of y and of the history buffer `b`.  IMH_EW_CONCAT, both forms, reads the n * i0 elements of `a` and the n * i1 of `b`,
+ * writes the n * (i0 + i1) elements of y and touches nothing else (the FreeU form reads `b` twice and keeps its sums on chip). */
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 
 /* ---- seeded step noise: the noise of the stochastic samplers as a pure function of (seed, lane, table row, element) --------------
