@@ -9,6 +9,7 @@ whole path (PIL in -> CLIP-shaped embeddings -> HarmonyAttention + ImageProjMode
                                 [--init-image in.png --strength 0.6] [--clip-backend hip --judge-preprocess hip]
                                 [--preview-vae taesdxl.safetensors | --preview-vae random]
                                 [--freeu 0.6 0.4 1.1 1.2]
+                                [--seeds 0 --pag-scale 3.0 --pag-layers mid]
 
 With --init-image the candidates are image-to-image EDITS of that image (IPAdapterXL.generate_pns(image=, strength=)): every seed fixes its
 posterior and add-noise draws, the previews are decoded and scored by the CLIP judge when a tower is attached (--clip-backend), and
@@ -16,6 +17,9 @@ posterior and add-noise draws, the previews are decoded and scored by the CLIP j
 previews through AutoencoderTiny (diffusers' TAESDXL decoder, 35 small launches per decode) instead of the full VAE; the winner's image
 still comes from the full VAE.  --freeu S1 S2 B1 B2 switches FreeU on (pipe.enable_freeu, diffusers' argument order; SDXL's published
 values are 0.6 0.4 1.1 1.2): previews and finals alike run the UNet with the re-weighted skip concats of its first two up blocks.
+--pag-scale S (with ONE seed) adds perturbed-attention guidance: pipe.set_pag_applied_layers(--pag-layers, default "mid") and the pipe's
+own call with pag_scale=S through IPAdapterXL.generate -- one more UNet batch member per step whose self-attention maps in the chosen
+layers are the identity.  Noise selection over several seeds is not built with PAG: the script says so and stops.
 
 Launch under torch.distributed.run with N ranks to shard the seeds over N GPUs (one process per GPU, RCCL).
 """
@@ -73,7 +77,12 @@ def main():
                          "safetensors file; no value or `random` = seeded random weights")
     ap.add_argument("--freeu", type=float, nargs=4, metavar=("S1", "S2", "B1", "B2"), default=None,
                     help="FreeU: skip scales s1, s2 and backbone scales b1, b2 of up blocks 0 and 1 (SDXL: 0.6 0.4 1.1 1.2)")
+    ap.add_argument("--pag-scale", type=float, default=0.0, help="perturbed-attention guidance scale (0 = off); single seed only")
+    ap.add_argument("--pag-layers", nargs="+", default=["mid"], metavar="REGEX",
+                    help='with --pag-scale: the self-attention layers that get the identity map, as diffusers\' pag_applied_layers ("mid", "down_blocks.2", ...)')
     a = ap.parse_args()
+    if a.pag_scale > 0 and len(a.seeds) > 1:
+        ap.error("--pag-scale runs a single seed: noise selection over several seeds (generate_pns) is not built with PAG")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -128,6 +137,23 @@ def main():
     prompt = (torch.randn(1, 77, 2048, generator=g), torch.randn(1, 77, 2048, generator=g),
               torch.randn(1, 1280, generator=g), torch.randn(1, 1280, generator=g))
     extra = torch.randn(1, 77, 2048, generator=g)
+    if a.pag_scale > 0:
+        # one seed, no selection: the pipe's own call (text-to-image, or the image-to-image edit of --init-image) with PAG
+        pipe.set_pag_applied_layers(a.pag_layers)
+        kw = {}
+        if a.init_image:
+            from PIL import Image
+            kw = dict(image=Image.open(a.init_image).convert("RGB").resize((a.size, a.size)), strength=a.strength)
+        else:
+            kw = dict(height=a.size, width=a.size)
+        images = ip.generate(clip_image_embeds=clip_embeds, prompt_embeds=prompt, extra_prompt_embeds=extra, scale=a.scale, num_samples=1,
+                             seed=a.seeds[0], num_inference_steps=a.steps, guidance_scale=a.guidance, pag_scale=a.pag_scale, **kw)
+        if int(os.environ.get("RANK", "0")) == 0:
+            images[0].save(a.out)
+            print(f"seed {a.seeds[0]} with PAG {a.pag_scale} in {len(unet.pag_layer_names())} layers {a.pag_layers}; wrote {a.out} {images[0].size}")
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     if a.init_image:
         from PIL import Image
         ip.image_encoder = enc                                            # the judge's tower (None: the latent-statistic scorer)

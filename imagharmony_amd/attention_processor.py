@@ -133,8 +133,12 @@ class AttnProcessor2_0(nn.Module):
         super().__init__()
 
     # -- recorded / fused path ------------------------------------------------------------
-    def emit(self, ctx, attn, x, B, L_, residual=None, kv=None, step=None, lk=None, ln=None, ln_stats=None, want_stats=False):
+    def emit(self, ctx, attn, x, B, L_, residual=None, kv=None, step=None, lk=None, ln=None, ln_stats=None, want_stats=False, pag=0):
         """x: [B*L, C].  Returns to_out(attention(x)) (+ residual).
+        pag = k > 0 (perturbed-attention guidance, diffusers PAGIdentitySelfAttnProcessor2_0): the attention map of the LAST k samples is
+        the identity, out = to_out(to_v(x)).  The projections and to_out stay whole-batch launches; the attention launch runs over the
+        first B - k samples of the same buffers, and the last k get V itself, un-transposed out of V^T by one copy launch
+        (Ctx.identity_rows).  Their Q and K projections are computed and never read.
         ln = norm module: x is the UN-normalised residual stream and that LayerNorm is folded into the projections;
         ln_stats = (tensor, slots): the rows' statistics as left by the GEMM that wrote x (csrc/imh_lnstats.h), None -> taken
         supplied by a row-statistics launch (Ctx.gemm_dual).  Without ln, x is already layer-normed.
@@ -142,8 +146,10 @@ class AttnProcessor2_0(nn.Module):
         lk < L_: only the first lk rows of every batch are real keys (zero-padded sequence)."""
         C_ = x.shape[1]
         H = attn.heads
+        if not 0 <= pag < B or (pag and lk is not None):
+            raise L.ImhError(f"self-attention: {pag} perturbed samples of a batch of {B} (0 <= pag < B; not with a key count lk)")
         if L_ % 64 and lk is None:
-            return self._emit_ragged(ctx, attn, x, B, L_, residual, ln)
+            return self._emit_ragged(ctx, attn, x, B, L_, residual, ln, pag)
         if ln is None:
             wqk, wv = _packed_qk(attn, ctx), _w(attn.to_v, ctx)
             g1, g2 = dict(x=x, w=wqk), dict(x=wv, w=x, flags=L.GF_VT_PERM)
@@ -170,18 +176,21 @@ class AttnProcessor2_0(nn.Module):
             ws = ln is not None and ln_stats is not None and DUAL_WS and L.experimental() and (B * L_) % 128 == 0 and C_ % 160 == 0      # the wave-specialised two-problem launch is an -DIMH_EXPERIMENTAL kernel: fall back to (128, 64) on the default library
             qk, vt = ctx.gemm_dual(g1, g2, cfg=(24128, 160) if ws else (128, 64), descr="self.to_qk+v^T")
         ao = ctx.new(B * L_, C_)
-        ctx.attention(qk[:, :C_], qk[:, C_:], vt, ao, B, H, L_, lk or L_, L_, 2 * C_, 2 * C_, B * L_, C_,
+        ctx.attention(qk[:, :C_], qk[:, C_:], vt, ao, B - pag, H, L_, lk or L_, L_, 2 * C_, 2 * C_, B * L_, C_,
                       HEAD_DIM ** -0.5, descr="self.attn")
+        if pag:
+            ctx.identity_rows(vt, ao[(B - pag) * L_:], pag * L_, (B - pag) * L_, descr="self.pag_rows")
         out = ctx.gemm(ao, _w(attn.to_out[0], ctx), bias=_b(attn.to_out[0], ctx), residual=residual,
                        descr="self.to_out", stats_out=want_stats)
         ctx.free(qk); ctx.free(vt); ctx.free(ao)
         return out
 
-    def _emit_ragged(self, ctx, attn, x, B, L_, residual, ln):
+    def _emit_ragged(self, ctx, attn, x, B, L_, residual, ln, pag=0):
         """Token counts that are not a multiple of the 64-key tile (1152x896 -> 36x28 = 1008 tokens, 832x1216 -> 26x38 = 988 at the
         deepest level): the rows of every batch are copied into its own Lp-row slab of a zero-initialised buffer (the padded rows are
         never written, so they stay zero), [Q|K] and V^T are projected over all B*Lp rows -- the V^T store permutes keys in groups of
-        16 and only ever sees whole groups; the padded keys are exact zeros -- and the kernel masks the keys at or past L_."""
+        16 and only ever sees whole groups; the padded keys are exact zeros -- and the kernel masks the keys at or past L_.
+        pag (emit): the copy takes the last pag samples' whole Lp-row slabs (the padded rows of V are zeros; to_out never reads them)."""
         if ln is not None:
             raise L.ImhError("ragged token counts are not supported together with the folded-LayerNorm path")
         C_ = x.shape[1]
@@ -194,8 +203,10 @@ class AttnProcessor2_0(nn.Module):
                    descr="self.pad_rows", nbytes=2.0 * L_ * C_ * x.element_size())
         qk, vt = ctx.gemm_dual(dict(x=xp, w=wqk), dict(x=wv, w=xp, flags=L.GF_VT_PERM), cfg=(128, 64), descr="self.to_qk+v^T")
         ao = ctx.new(B * Lp, C_)
-        ctx.attention(qk[:, :C_], qk[:, C_:], vt, ao, B, H, Lp, L_, Lp, 2 * C_, 2 * C_, B * Lp, C_,
+        ctx.attention(qk[:, :C_], qk[:, C_:], vt, ao, B - pag, H, Lp, L_, Lp, 2 * C_, 2 * C_, B * Lp, C_,
                       HEAD_DIM ** -0.5, descr="self.attn")
+        if pag:
+            ctx.identity_rows(vt, ao[(B - pag) * Lp:], pag * Lp, (B - pag) * Lp, descr="self.pag_rows")
         ctx.free(qk); ctx.free(vt)
         out = ctx.new(B * L_, C_)
         for b in range(B):

@@ -1,7 +1,8 @@
 // Small memory-/latency-bound kernels around the UNet forward and the denoise loop, gfx950.
 //   EW_TIMESTEP   diffusers Timesteps(dim, flip_sin_to_cos=True, shift 0)      
 //   EW_SILU       SiLU on the time embedding before time_emb_proj               (App. A ResnetBlock2D)
-//   EW_CONCAT     channel concat of NHWC tensors (up-block skip connections)    (App. A.6)
+//   EW_CONCAT     channel concat of NHWC tensors (up-block skip connections)    (App. A.6); its FreeU form (the concat behind
+//                 diffusers' apply_freeu) and its identity-attention form (perturbed-attention guidance: V rows out of V^T)
 //   EW_CONV_IN    conv_in 3x3 (4 | 9 -> C0) reading NCHW fp32 latents, fusing CFG duplication
 //                 (custom_pipelines.py:332) and scale_model_input (:334); writes NHWC; with 9 channels (the SDXL inpainting
 //                 UNet) the last five, [mask | masked-image latents], come from a second, step-invariant buffer
@@ -14,6 +15,7 @@
 //                 z the step's row of a host-filled noise bank -- or, in the seeded form (imh_step_seeded), generated in the launch by
 //                 Philox4x32-10 from the sample's seed row, the table row and the element index (imh_philox.h): no bank, no host draw
 //   randn_seeded  the generator's rows by themselves (imh_randn_seeded): normals or raw words, for tests and oracle comparisons
+//                 -- all three step forms optionally with the third, perturbed block of perturbed-attention guidance (i2 = 1)
 //   EW_CFG_RESCALE per-sample factor of rescale_noise_cfg (custom_pipelines.py:351-354; arXiv 2305.08891 3.4):
 //                 phi * std(eps_text) / std(eps_cfg) + (1 - phi), consumed by EW_CFG_STEP through `w`
 //   EW_SOFTMAX    row softmax of fp32 scores -> T probabilities (the VAE mid-block attention: one head of width
@@ -251,6 +253,62 @@ __global__ __launch_bounds__(FREEU_THREADS) void freeu_concat_kernel(const EwPar
     }
 }
 
+// EW_CONCAT, the identity-attention form (imh.h; i5 = ldvt > 0, empty first part): the self-attention output of samples whose attention
+// map is the identity (perturbed-attention guidance) is V itself, and V exists only transposed -- b = Vt [C = i1, ldvt], keys permuted
+// inside every 16-group by vt_perm16 (imh_layout.h: runs 1 and 2 of 4 swapped).  So this is a transposing copy,
+//   y[r, c] = Vt[c, col0 + 16 * (r / 16) + vt_perm16(r % 16)]      0 <= r < n, 0 <= c < C      (col0 = i4, y rows i3 elements apart)
+// One workgroup moves a 64-key x 64-channel tile through LDS: 16-byte loads along the key axis (eight lanes cover a channel's 128
+// bytes), each split into its two runs of four keys, which go to their LOGICAL place as 8-byte LDS writes (the un-permutation costs
+// nothing: it is where the two halves are put); then every lane gathers the eight channels of one key as 16-bit LDS reads and stores
+// 16 bytes along the channel axis (eight lanes cover a row's 128 bytes).  The tile is [channel][16 slots of four keys], 128-byte rows,
+// slot s of channel c at s ^ (c >> 3) ^ ((c & 1) << 1) (idr_slot), which leaves neither side a bank conflict by the rules of the LDS
+// (bank = dword mod 32 for the writes and for the 16-bit reads):
+//   writes  a 16-lane group holds chunks j = 0..7 of channels c, c + 1 (c even, one c >> 3): per half its eight slots 4 (j >> 1) + (j & 1)
+//           [+ 2] are distinct, the odd channel's are those XOR 2 -- a disjoint set -- so 16 lanes x 2 dwords fill the 32 banks once;
+//   reads   a 32-lane group holds four keys of one slot x eight channel octets cc, and for element e reads channel 8 cc + e: slot
+//           (r >> 2) ^ cc ^ ((e & 1) << 1), eight distinct slots = 16 distinct dwords, each read by the two lanes whose keys share it.
+// Both dtypes are 16 bits wide and the launch never looks inside an element: one kernel.  Partial tiles (C % 64, n % 64) are guarded per
+// 16-byte chunk on both sides (C % 8 == 0 and n % 16 == 0: a chunk is inside or outside as a whole).  8 KiB of LDS, no scratch.
+constexpr int IDR_TILE = 64, IDR_THREADS = 256;
+
+__device__ __forceinline__ int idr_slot(int c, int s) { return s ^ (c >> 3) ^ ((c & 1) << 1); }
+
+__global__ __launch_bounds__(IDR_THREADS) void identity_rows_kernel(const EwParams p) {
+    __shared__ uint2 tile[IDR_TILE][IDR_TILE / 4];
+    const int C = p.i1, ldy = p.i3, col0 = p.i4, ldvt = p.i5, n = (int)p.n;
+    const int k0 = blockIdx.x * IDR_TILE, c0 = blockIdx.y * IDR_TILE;
+    const int tid = threadIdx.x, lo = tid & 7, hi = tid >> 3;
+    const unsigned short* vt = (const unsigned short*)p.b;
+    unsigned short* y = (unsigned short*)p.y;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int c = hi + it * 32;                         // lo = 16-byte chunk of the channel's 64 keys
+        if (c0 + c < C && k0 + 8 * lo < n) {
+            const uint4 v = *(const uint4*)(vt + (size_t)(c0 + c) * ldvt + col0 + k0 + 8 * lo);
+            // stored runs (0, 1 | 2, 3) of a 16-group are the logical runs (0, 2 | 1, 3)
+            const int s = 4 * (lo >> 1) + (lo & 1);
+            tile[c][idr_slot(c, s)] = make_uint2(v.x, v.y);
+            tile[c][idr_slot(c, s + 2)] = make_uint2(v.z, v.w);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int r = hi + it * 32;                         // lo = channel octet of the key's 64 channels
+        if (k0 + r < n && c0 + 8 * lo < C) {
+            unsigned int w[4];
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                const int ca = 8 * lo + e, cb = ca + 1;
+                const unsigned int a = ((const unsigned short*)&tile[ca][idr_slot(ca, r >> 2)])[r & 3];
+                const unsigned int b = ((const unsigned short*)&tile[cb][idr_slot(cb, r >> 2)])[r & 3];
+                w[e >> 1] = a | (b << 16);
+            }
+            *(uint4*)(y + (size_t)(k0 + r) * ldy + c0 + 8 * lo) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+}
+
 // conv_in: a = latents fp32 NCHW [S, 4, H, W]; w = weights T [C0][CIN][3][3]; bias T [C0];
 // y = NHWC T [Bout, H, W, C0] with Bout = i4 (batch b reads latent b % S: CFG duplication).
 // i0 = S, i1 = H, i2 = W, i3 = C0, f0 = input scale.  Eight threads per pixel, each 8 channels at a time.
@@ -330,11 +388,20 @@ __global__ __launch_bounds__(CIN > 4 ? 512 : 256) void conv_in_kernel(const EwPa
     }
 }
 
+// The guided noise prediction of the step kernels below, np_ = the UNet's output NHWC [blocks * S, HW, 4]:
+//   i3 = 1: [uncond | cond (| perturbed)],  eps = u + f2 * (c - u)            i3 = 0: [cond (| perturbed)],  eps = c
+// PAG (imh.h: i2 = 1, the scale s in f3 -- IMH_EW_CFG_RESCALE: f0): perturbed-attention guidance, diffusers
+// PAGMixin._apply_perturbed_attention_guidance -- a further block p, the conditional prediction with identity self-attention maps,
+//   eps = (u + f2 * (c - u)) + s * (c - p)      |      eps = c + s * (c - p)
+// The two-term part is the expression it always was and the third term is added to its result, so a perturbed block equal to the
+// conditional one gives the bits of the launch without it; the PAG = false instantiations are the kernels as they were, instruction
+// for instruction.
+
 // BLEND (imh.h IMH_EW_CFG_STEP with `mask`): after the update, the masked blend of diffusers StableDiffusionXLInpaintPipeline.__call__
 // (num_channels_unet == 4): latents = (1 - m) * add_noise(z, n, timesteps[i + 1]) + m * latents, with add_noise's pair read from
 // blend_tab[*step] ((1, 0) in the last row that runs: the image latents themselves).  Same pass, same launch; a == NULL: the blend alone.
 // The plain instantiation is the kernel as it was.
-template <typename T, bool BLEND>
+template <typename T, bool BLEND, bool PAG = false>
 __global__ void cfg_step_kernel(const EwParams p) {
     const int S = p.i0, HW = p.i1;
     const long long total = (long long)S * HW * 4;
@@ -354,8 +421,10 @@ __global__ void cfg_step_kernel(const EwParams p) {
                 const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + ch]);
                 const float c = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + ch]);
                 eps = u + p.f2 * (c - u);
+                if constexpr (PAG) eps = eps + p.f3 * (c - to_f32(np_[((size_t)(2 * S + s) * HW + pix) * 4 + ch]));
             } else {
                 eps = to_f32(np_[((size_t)s * HW + pix) * 4 + ch]);
+                if constexpr (PAG) eps = eps + p.f3 * (eps - to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + ch]));
             }
             if (p.w) eps *= ((const float*)p.w)[s];        // guidance_rescale factor of this sample (EW_CFG_RESCALE)
             if (p.b) ((float*)p.b)[i] = eps;
@@ -382,7 +451,7 @@ __global__ void cfg_step_kernel(const EwParams p) {
 // when HW % 4 != 0).  The update is the expression of the bank form, term for term, so that fed the same z the bits are the same; a row
 // with cn == 0 (every row of a deterministic sampler, the last row of Euler ancestral) generates nothing.  The SEEDED = false
 // instantiations are the kernels as they were.
-template <typename T, bool BLEND, bool SEEDED = false>
+template <typename T, bool BLEND, bool SEEDED = false, bool PAG = false>
 __global__ void cfg_mstep_kernel(const EwParams p) {
     const int S = p.i0, HW = p.i1;
     const long long total = (long long)S * HW * 4;
@@ -412,8 +481,10 @@ __global__ void cfg_mstep_kernel(const EwParams p) {
                     const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
                     const float cnd = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + chn]);
                     eps = u + p.f2 * (cnd - u);
+                    if constexpr (PAG) eps = eps + p.f3 * (cnd - to_f32(np_[((size_t)(2 * S + s) * HW + pix) * 4 + chn]));
                 } else {
                     eps = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
+                    if constexpr (PAG) eps = eps + p.f3 * (eps - to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + chn]));
                 }
                 if (p.w) eps *= ((const float*)p.w)[s];
                 const float x = lat[i];
@@ -442,8 +513,10 @@ __global__ void cfg_mstep_kernel(const EwParams p) {
             const float u = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
             const float cnd = to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + chn]);
             eps = u + p.f2 * (cnd - u);
+            if constexpr (PAG) eps = eps + p.f3 * (cnd - to_f32(np_[((size_t)(2 * S + s) * HW + pix) * 4 + chn]));
         } else {
             eps = to_f32(np_[((size_t)s * HW + pix) * 4 + chn]);
+            if constexpr (PAG) eps = eps + p.f3 * (eps - to_f32(np_[((size_t)(S + s) * HW + pix) * 4 + chn]));
         }
         if (p.w) eps *= ((const float*)p.w)[s];            // guidance_rescale factor of this sample (EW_CFG_RESCALE)
         const float x = lat[i];
@@ -488,7 +561,8 @@ __global__ void randn_seeded_kernel(const RandnParams p) {
 // One workgroup per sample: unbiased std over (C, H, W) of the text-conditioned prediction and of the CFG
 // combination (torch.std semantics, as diffusers' rescale_noise_cfg), double accumulation, fixed-order tree.
 // a = noise prediction NHWC T [2S, HW, 4] ([uncond | cond]); y = fp32 [S]; f2 = guidance scale, f3 = guidance_rescale.
-template <typename T>
+// PAG (i2 = 1, f0 = the PAG scale): a is [3S, HW, 4] ([uncond | cond | perturbed]) and the combination is the three-term one of guided_eps.
+template <typename T, bool PAG = false>
 __global__ __launch_bounds__(256) void cfg_rescale_kernel(const EwParams p) {
     __shared__ double red[4][256];
     const int S = p.i0, HW = p.i1, s = blockIdx.x;
@@ -498,7 +572,8 @@ __global__ __launch_bounds__(256) void cfg_rescale_kernel(const EwParams p) {
     double st = 0, st2 = 0, sc = 0, sc2 = 0;
     for (long long i = threadIdx.x; i < n; i += 256) {
         const float uu = to_f32(u[i]), cc = to_f32(c[i]);
-        const float g = uu + p.f2 * (cc - uu);
+        float g = uu + p.f2 * (cc - uu);
+        if constexpr (PAG) g = g + p.f0 * (cc - to_f32(c[(size_t)S * n + i]));
         st += cc; st2 += (double)cc * cc; sc += g; sc2 += (double)g * g;
     }
     red[0][threadIdx.x] = st; red[1][threadIdx.x] = st2; red[2][threadIdx.x] = sc; red[3][threadIdx.x] = sc2;
@@ -648,6 +723,18 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
             hipLaunchKernelGGL((add_kernel<T>), dim3(grid_for(p.n >> 3, 256)), dim3(256), 0, stream, p);
             break;
         case EW_CONCAT:
+            if (p.i5 > 0) {         // the identity-attention form (imh.h): b = Vt [C = i1, ldvt = i5], y[r, c] = Vt[c, col0 + unpermuted r], i3 = ld of y, i4 = col0
+                if (p.i0 != 0 || p.i2 != 0) { set_error("concat: the identity-rows form (i5 = ldvt = %d > 0) has an empty first part and no FreeU planes (i0 = %d, i2 = %d)", p.i5, p.i0, p.i2); return IMH_ERR_ARG; }
+                if (p.n <= 0 || (p.n & 15) || p.n > 0x7fffffc0LL || p.i4 < 0 || (p.i4 & 15) || p.i1 <= 0 || (p.i1 & 7)) {
+                    set_error("concat: identity rows n = %lld, col0 = %d (positive / non-negative multiples of 16), C = %d (a positive multiple of 8)", p.n, p.i4, p.i1); return IMH_ERR_ARG;
+                }
+                if ((p.i5 & 7) || p.i5 < p.i4 + p.n || (p.i3 & 7) || p.i3 < p.i1) {
+                    set_error("concat: identity rows ldvt = %d (a multiple of 8, >= col0 + n = %lld), ld of y = %d (a multiple of 8, >= C = %d)", p.i5, p.i4 + p.n, p.i3, p.i1); return IMH_ERR_ARG;
+                }
+                if (!p.b || (((uintptr_t)p.b | (uintptr_t)p.y) & 15)) { set_error("concat: identity rows need Vt in b, and b and y 16-byte aligned"); return IMH_ERR_ARG; }
+                hipLaunchKernelGGL(identity_rows_kernel, dim3((unsigned)((p.n + IDR_TILE - 1) / IDR_TILE), (unsigned)((p.i1 + IDR_TILE - 1) / IDR_TILE)), dim3(IDR_THREADS), 0, stream, p);
+                break;
+            }
             if ((p.i0 & 7) || (p.i1 & 7)) { set_error("concat: channel counts must be multiples of 8"); return IMH_ERR_SHAPE; }
             if (p.i2 > 0) {         // the FreeU form (imh.h): i2 = H, i3 = W, i4 = scaled hidden channels, f0 = b, f1 = s
                 const long long hw = (long long)p.i2 * p.i3;
@@ -691,37 +778,52 @@ static int ew_typed(int op, const EwParams& p, hipStream_t stream) {
             break;
         }
         case EW_CFG_STEP:
+            if (p.i2 != 0 && (p.i2 != 1 || !p.a)) { set_error("cfg_step: i2 = %d selects the three-term (PAG) form with 1 and needs the noise prediction", p.i2); return IMH_ERR_ARG; }
             if (p.mask) {
                 if (!p.x2 || !p.noise || !p.blend_tab || !p.step || p.i4 < 1) {
                     set_error("cfg_step: the masked blend needs x2 (image latents), noise, blend_tab, step and i4 = mask batch >= 1");
                     return IMH_ERR_ARG;
                 }
-                hipLaunchKernelGGL((cfg_step_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+                if (p.i2) hipLaunchKernelGGL((cfg_step_kernel<T, true, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+                else hipLaunchKernelGGL((cfg_step_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
                 break;
             }
             if (!p.a) { set_error("cfg_step: null noise prediction"); return IMH_ERR_ARG; }
-            hipLaunchKernelGGL((cfg_step_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+            if (p.i2) hipLaunchKernelGGL((cfg_step_kernel<T, false, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((cfg_step_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
             break;
         case EW_CFG_MSTEP:
             if (!p.a || !p.tab || !p.step || p.i0 <= 0 || p.i1 <= 0) {
                 set_error("cfg_mstep: needs the noise prediction, the six-column table, step and S, HW > 0");
                 return IMH_ERR_ARG;
             }
-            if (p.mask) {
-                if (!p.x2 || !p.noise || !p.blend_tab || p.i4 < 1) {
-                    set_error("cfg_mstep: the masked blend needs x2 (image latents), noise, blend_tab and i4 = mask batch >= 1");
-                    return IMH_ERR_ARG;
+            if (p.i2 != 0 && p.i2 != 1) { set_error("cfg_mstep: i2 = %d selects the three-term (PAG) form with 1", p.i2); return IMH_ERR_ARG; }
+            {
+                const dim3 gq(grid_for((long long)p.i0 * p.i1, 256)), ge(grid_for((long long)p.i0 * p.i1 * 4, 256));
+                if (p.mask) {
+                    if (!p.x2 || !p.noise || !p.blend_tab || p.i4 < 1) {
+                        set_error("cfg_mstep: the masked blend needs x2 (image latents), noise, blend_tab and i4 = mask batch >= 1");
+                        return IMH_ERR_ARG;
+                    }
+                    if (p.i2) {
+                        if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, true, true, true>), gq, dim3(256), 0, stream, p);
+                        else hipLaunchKernelGGL((cfg_mstep_kernel<T, true, false, true>), ge, dim3(256), 0, stream, p);
+                    } else if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, true, true>), gq, dim3(256), 0, stream, p);
+                    else hipLaunchKernelGGL((cfg_mstep_kernel<T, true>), ge, dim3(256), 0, stream, p);
+                    break;
                 }
-                if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, true, true>), dim3(grid_for((long long)p.i0 * p.i1, 256)), dim3(256), 0, stream, p);
-                else hipLaunchKernelGGL((cfg_mstep_kernel<T, true>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
-                break;
+                if (p.i2) {
+                    if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, false, true, true>), gq, dim3(256), 0, stream, p);
+                    else hipLaunchKernelGGL((cfg_mstep_kernel<T, false, false, true>), ge, dim3(256), 0, stream, p);
+                } else if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, false, true>), gq, dim3(256), 0, stream, p);
+                else hipLaunchKernelGGL((cfg_mstep_kernel<T, false>), ge, dim3(256), 0, stream, p);
             }
-            if (p.seeds) hipLaunchKernelGGL((cfg_mstep_kernel<T, false, true>), dim3(grid_for((long long)p.i0 * p.i1, 256)), dim3(256), 0, stream, p);
-            else hipLaunchKernelGGL((cfg_mstep_kernel<T, false>), dim3(grid_for((long long)p.i0 * p.i1 * 4, 256)), dim3(256), 0, stream, p);
             break;
         case EW_CFG_RESCALE:
             if (p.i0 <= 0 || p.i1 <= 0) { set_error("cfg_rescale: empty problem"); return IMH_ERR_SHAPE; }
-            hipLaunchKernelGGL((cfg_rescale_kernel<T>), dim3(p.i0), dim3(256), 0, stream, p);
+            if (p.i2 != 0 && p.i2 != 1) { set_error("cfg_rescale: i2 = %d selects the three-term (PAG) form with 1", p.i2); return IMH_ERR_ARG; }
+            if (p.i2) hipLaunchKernelGGL((cfg_rescale_kernel<T, true>), dim3(p.i0), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((cfg_rescale_kernel<T>), dim3(p.i0), dim3(256), 0, stream, p);
             break;
         case EW_SOFTMAX:
             if (p.i0 <= 0 || p.i1 <= 0 || (p.i1 & 3) || (p.i2 & 3) || (p.i3 & 3) || p.f0 <= 0.f) {

@@ -1021,6 +1021,10 @@ class Ctx:
                 raise L.ImhError(f"{descr}: hist / bank belong to EW_CFG_MSTEP and take the place of b / bias")
             self._chk_dense_f32(descr, hist=hist, bank=bank)
             b, bias = hist, bank
+        if op == L.EW_CONCAT and int(i[5]) > 0:
+            self._chk_identity_rows(descr, y, b, int(n), i)
+        if op in (L.EW_CFG_STEP, L.EW_CFG_MSTEP, L.EW_CFG_RESCALE) and int(i[2]) != 0 and (int(i[2]) != 1 or a is None):
+            raise L.ImhError(f"{descr}: i2 = {int(i[2])} selects the three-term (PAG) form with 1 and needs the noise prediction")
         e = L.EwArgs()
         e.a, e.b, e.y, e.w, e.bias = self._p(a), self._p(b), y.data_ptr(), self._p(w), self._p(bias)
         e.tab, e.step = self._p(tab), self._p(step)
@@ -1037,6 +1041,30 @@ class Ctx:
             return y
         self._emit(L.OP_EW, e, ew_op=op, descr=descr, nbytes=nbytes, keep=(a, b, y, w, bias, tab, step, x2, noise, mask, blend_tab))
         return y
+
+    def _chk_identity_rows(self, descr, y, vt, n, i):
+        """the identity-attention form of EW_CONCAT (imh.h: i5 = ldvt > 0) is refused here for what the library refuses it for"""
+        i0, C_, i2, ldy, col0, ldvt = (int(v) for v in i)
+        if i0 != 0 or i2 != 0:
+            raise L.ImhError(f"{descr}: the identity-rows form has an empty first part and no FreeU planes (i0 = {i0}, i2 = {i2})")
+        if n <= 0 or n % 16 or col0 < 0 or col0 % 16 or C_ <= 0 or C_ % 8:
+            raise L.ImhError(f"{descr}: identity rows n = {n}, col0 = {col0} (multiples of 16), C = {C_} (a positive multiple of 8)")
+        if ldvt % 8 or ldvt < col0 + n or ldy % 8 or ldy < C_:
+            raise L.ImhError(f"{descr}: identity rows ldvt = {ldvt} (a multiple of 8, >= col0 + n = {col0 + n}), ld of y = {ldy} (a multiple of 8, >= C = {C_})")
+        if vt is None or vt.data_ptr() % 16 or y.data_ptr() % 16:
+            raise L.ImhError(f"{descr}: identity rows need Vt in b, and b and y 16-byte aligned")
+        self._chk(vt, f"{descr}.vt"); self._chk(y, f"{descr}.y")
+
+    def identity_rows(self, vt, out, n, col0, descr="identity_rows"):
+        """out[r, 0:C] = V[col0 + r, 0:C] for r < n, read from vt = V^T [C, ldvt] as the self-attention projections leave it (keys permuted
+        inside every 16-group, imh_layout.h vt_perm16): the attention output of samples whose attention map is the identity
+        (perturbed-attention guidance).  The identity-attention form of EW_CONCAT (imh.h: i5 = ldvt > 0), one launch; out: rows of a
+        row-major [*, ld] buffer, ld = out.stride(0)."""
+        if vt.dim() != 2 or out.dim() != 2 or vt.stride(1) != 1 or out.stride(1) != 1 or out.shape[1] != vt.shape[0] or out.shape[0] < n:
+            raise L.ImhError(f"{descr}: V^T {tuple(vt.shape)} and out {tuple(out.shape)} must be row-major [C, ldvt] and [>= n = {n}, C]")
+        C_ = int(vt.shape[0])
+        return self.ew(L.EW_CONCAT, out, b=vt, n=int(n), i=(0, C_, 0, int(out.stride(0)), int(col0), int(vt.stride(0))), descr=descr,
+                       nbytes=2.0 * n * C_ * out.element_size())
 
     def randn_seeded(self, seeds, HW, row=0, step=None, noise_stream=0, raw=False, out=None, descr="randn_seeded"):
         """the seeded generator's rows by themselves (imh_randn_seeded; imagharmony_amd/noise.py states what they are): fp32 [S, 4, HW]

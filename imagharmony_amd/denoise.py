@@ -53,31 +53,40 @@ _PLAN_ENGINE = ("steps", "init_noise_sigma", "plan", "noise_pred", "plan_tail", 
 #   hashes, slices and serialises as before, and PlanKey(...) equals PlanKey(..., regions=None)
 _KEY_FIELDS = ("scheduler num_train_timesteps num_inference_steps control_guidance_start control_guidance_end "
                "denoising_end ip_scale steps tables controlnet inpaint adapter seeded")
-PlanKeyRegions = collections.namedtuple("PlanKeyRegions", _KEY_FIELDS + " regions")
 #   freeu (the UNet's (s1, s2, b1, b2), unet.enable_freeu) -- the same way: a trailing field that exists only on the key of a plan recorded
 #   with FreeU enabled, behind regions where both are set; a key without it is the tuple it always was and ``.freeu`` reads None
-PlanKeyFreeU = collections.namedtuple("PlanKeyFreeU", _KEY_FIELDS + " freeu")
-PlanKeyFreeU.regions = None
-PlanKeyRegions.freeu = None
-PlanKeyRegionsFreeU = collections.namedtuple("PlanKeyRegionsFreeU", _KEY_FIELDS + " regions freeu")
+#   pag ((SHA-1 of the chosen attn1 layers' names, the PAG scale); unet.set_pag_applied_layers, set_conditioning(pag_scale=)) -- the same
+#   way again, the last of the trailing fields: it exists only on the key of a plan recorded with perturbed-attention guidance on
+_KEY_EXTRAS = ("regions", "freeu", "pag")
+
+
+@functools.lru_cache(maxsize=None)
+def _key_variant(extras):
+    """the key class that carries the trailing fields `extras` (a non-empty subset of _KEY_EXTRAS, in that order); the others read None"""
+    cls = collections.namedtuple("PlanKey" + "".join(n.capitalize() for n in extras), _KEY_FIELDS + " " + " ".join(extras))
+    for n in _KEY_EXTRAS:
+        if n not in extras:
+            setattr(cls, n, None)
+    return cls
 
 
 class PlanKey(collections.namedtuple("PlanKey", _KEY_FIELDS)):
     __slots__ = ()
     regions = None
     freeu = None
+    pag = None
 
-    def __new__(cls, *args, regions=None, freeu=None, **kw):
+    def __new__(cls, *args, regions=None, freeu=None, pag=None, **kw):
         if len(args) == len(cls._fields) + 1:
             args, regions = args[:-1], args[-1]
         if freeu is not None:
             freeu = tuple(float(v) for v in freeu)
-            if regions is not None:
-                return PlanKeyRegionsFreeU(*args, **kw, regions=regions, freeu=freeu)
-            return PlanKeyFreeU(*args, **kw, freeu=freeu)
-        if regions is None:
+        if pag is not None:
+            pag = (str(pag[0]), float(pag[1]))
+        extras = {n: v for n, v in (("regions", regions), ("freeu", freeu), ("pag", pag)) if v is not None}
+        if not extras:
             return super().__new__(cls, *args, **kw)
-        return PlanKeyRegions(*args, **kw, regions=regions)
+        return _key_variant(tuple(extras))(*args, **kw, **extras)
 
 
 def _move(names, src, dst):
@@ -96,6 +105,24 @@ class PlanRecord:
     def restore(self, eng):
         _move(PLAN_STATE, self, eng.st)
         _move(_PLAN_ENGINE, self, eng)
+
+
+# What a conditioning is, for the one case in which an engine keeps two: switching perturbed-attention guidance on or off changes the
+# UNet batch, so the other mode's caches and recorded plans cannot serve -- but they are still right for their own mode, and a call that
+# switches back with the same inputs picks them up again instead of projecting and recording anew
+_COND_STATE = ("st", "_cond_ctx", "_cond_in", "_cond_fp", "_plans", "S", "H", "W", "T_total", "do_cfg", "guidance", "guidance_rescale",
+               "cfg_role", "pag", "pag_scale")
+
+
+class _CondRecord:
+    __slots__ = _COND_STATE
+
+    def __init__(self, eng):
+        _move(_COND_STATE, eng, self)
+
+    def restore(self, eng):
+        _move(_COND_STATE, self, eng)
+        eng.plan, eng._sched_key = None, None          # set_schedule picks the plan out of the restored cache
 
 
 class DenoiseEngine:
@@ -133,6 +160,11 @@ class DenoiseEngine:
     ad_gate_tab = None       # fp32 [steps] 1 / 0 per step of the current schedule (set_schedule(adapter_conditioning_factor=))
     # regional image prompts (regions.py; an engine without them records, launches and returns what it always did)
     regions = None           # an IPRegions: the cross-attention layers with an image-prompt branch record csrc/xattn_regions.hip's launch (set_ip_regions)
+    # perturbed-attention guidance (set_conditioning(pag_scale=) with unet.set_pag_applied_layers; off: the engine is what it always was)
+    pag = False              # the conditioning carries one more block of S rows, [uncond | cond | perturbed] / [cond | perturbed]
+    pag_scale = 0.0          # ... and the step adds pag_scale * (cond - perturbed)
+    _cond_fp = None          # fingerprint of what the current conditioning was computed from (None: not taken) ...
+    _cond_stash = None       # ... and the conditioning of the other PAG mode, kept across a switch with its caches and plans (_CondRecord)
 
     def __init__(self, unet, device, dtype=torch.bfloat16, use_graph=True):
         """Touches no device: the eager context is made on first use, so the "no CPU path" ImhError of a non-ROCm device surfaces at the
@@ -300,8 +332,16 @@ class DenoiseEngine:
     @torch.no_grad()
     def set_conditioning(self, prompt_embeds, negative_prompt_embeds, pooled, negative_pooled, height, width,
                          guidance_scale=5.0, guidance_rescale=0.0, original_size=None, crops_coords_top_left=(0, 0),
-                         target_size=None, cfg_role=None):
+                         target_size=None, cfg_role=None, pag_scale=0.0):
         """prompt_embeds: [S, 77+T, 2048] (IP tokens already concatenated, ip_adapter.py:321-322).
+        pag_scale > 0 with layers chosen on the UNet (unet.set_pag_applied_layers): perturbed-attention guidance (diffusers PAGMixin).
+        Every conditioning row set -- the prompt embeddings behind every cross-attention layer's K / V cache, image tokens included,
+        text_embeds, time_ids, so also aug_emb and the time-embedding rows -- gets one more block, the positive rows again:
+        [neg | pos | pos], or [pos | pos] without CFG; the UNet runs that block with identity self-attention maps in the chosen layers
+        and the step adds pag_scale * (cond - perturbed).  pag_scale = 0, or no layers chosen: the call as it always was.  Refused
+        (NotImplementedError): together with cfg_role, a ControlNet, a T2I-Adapter, regional image prompts.
+        Switching the mode keeps the other mode's conditioning aside with its plans; the next call that switches back with the same
+        inputs, guidance and weights gets it back and records nothing.
         original_size / crops_coords_top_left / target_size: SDXL micro-conditioning (custom_pipelines.py:277-293),
         default (height, width), (0, 0), (height, width).
         cfg_role = 0 / 1: this engine computes only the unconditional / the conditional half of the CFG pair (UNet batch S
@@ -315,7 +355,31 @@ class DenoiseEngine:
         self._regions_alone("a ControlNet", self.controlnet is not None)
         self._regions_alone("a T2I-Adapter", self.adapter is not None)
         self._sync_regions()
-        self._plans, self.plan = {}, None         # every recorded plan points into the previous conditioning's caches
+        pag = float(pag_scale) > 0.0 and bool(getattr(self.unet, "pag_layers", None))
+        if pag:
+            for what, other in (("cfg_role (the CFG split)", cfg_role), ("a ControlNet", self.controlnet), ("a T2I-Adapter", self.adapter),
+                                ("regional image prompts", self.regions)):
+                if other is not None:
+                    raise NotImplementedError(f"perturbed-attention guidance together with {what} is not built")
+        if pag or self.pag or self._cond_stash is not None or getattr(self.unet, "pag_layers", None):
+            # PAG is in play (layers chosen, or a mode to switch from): the conditionings are fingerprinted, and the one of the other mode
+            # is kept across the switch.  An engine that never meets PAG skips all of this and carries none of its state
+            fp = self._cond_fingerprint((prompt_embeds, negative_prompt_embeds, pooled, negative_pooled),
+                                        (height, width, float(guidance_scale), float(guidance_rescale), original_size,
+                                         tuple(crops_coords_top_left), target_size, cfg_role, float(pag_scale) if pag else 0.0))
+            cur = _CondRecord(self) if self.st is not None and self._cond_fp is not None else None
+            stash, self._cond_stash = self._cond_stash, None
+            if cur is not None and cur.pag != pag:
+                self._cond_stash = cur            # the other mode's conditioning outlives the switch
+            elif stash is not None and stash.pag != pag:
+                self._cond_stash = stash
+            if stash is not None and fp is not None and stash.pag == pag and stash._cond_fp == fp:
+                stash.restore(self)               # (its StepState comes back with it: the latents, the counter and the tables its plans point at)
+                return self.st
+            self.pag, self.pag_scale, self._cond_fp = pag, float(pag_scale) if pag else 0.0, fp
+        elif self._cond_fp is not None:
+            self._cond_fp = None                  # (a fingerprint taken while PAG was in play does not describe this conditioning)
+        self._plans, self.plan = {}, None        # every recorded plan points into the previous conditioning's caches
         self.cfg_role = cfg_role
         self.do_cfg = guidance_scale > 1.0                                   # custom_pipelines.py:223
         self.guidance = float(guidance_scale)
@@ -323,7 +387,12 @@ class DenoiseEngine:
         S = prompt_embeds.shape[0]
         osz, tsz = tuple(original_size or (height, width)), tuple(target_size or (height, width))
         ids = torch.tensor([list(osz) + list(crops_coords_top_left) + list(tsz)], dtype=torch.float32).repeat(S, 1)   # :277-293
-        if self.do_cfg and cfg_role is None:                                 # :295-298 -- order [uncond | cond]
+        if pag:                                                              # diffusers PAGMixin._prepare_perturbed_attention_guidance
+            neg = [negative_prompt_embeds] if self.do_cfg else []
+            ehs = torch.cat(neg + [prompt_embeds, prompt_embeds], 0)
+            text = torch.cat(([negative_pooled] if self.do_cfg else []) + [pooled, pooled], 0)
+            ids = torch.cat([ids] * (len(neg) + 2), 0)
+        elif self.do_cfg and cfg_role is None:                               # :295-298 -- order [uncond | cond]
             ehs = torch.cat([negative_prompt_embeds, prompt_embeds], 0)
             text = torch.cat([negative_pooled, pooled], 0)
             ids = torch.cat([ids, ids], 0)
@@ -354,6 +423,27 @@ class DenoiseEngine:
         if self.ad is not None and not self._image_fits(self.ad["image"], S, height, width):
             self.ad = None                        # the previous call's control image does not fit this size or batch: set_adapter_image sets this call's
         return st
+
+    def _cond_fingerprint(self, tensors, scalars):
+        """SHA-1 of everything a conditioning is computed from, for the switch of PAG modes (set_conditioning); None where the engine
+        carries state the fingerprint does not cover (a ControlNet, an adapter, regions) or a tensor is missing"""
+        if self.controlnet is not None or self.adapter is not None or self.regions is not None or any(not torch.is_tensor(t) for t in tensors):
+            return None
+        fp = hashlib.sha1(repr((scalars, getattr(self.unet, "lora_epoch", 0), str(self.dtype))).encode())
+        for t in tensors:
+            t = t.detach().to("cpu").contiguous()
+            fp.update(repr((tuple(t.shape), str(t.dtype))).encode())
+            fp.update(t.view(torch.uint8).numpy().tobytes())
+        return fp.hexdigest()
+
+    def _pag_key(self):
+        """the PAG field of the plan key: (digest of the chosen layers' names, the scale), or None with PAG off"""
+        if not self.pag:
+            return None
+        names = self.unet.pag_layer_names()
+        if not names:
+            raise L.ImhError("the conditioning carries the perturbed block but the UNet's PAG layers were cleared: set_pag_applied_layers, or set_conditioning again")
+        return hashlib.sha1("\n".join(names).encode()).hexdigest(), self.pag_scale
 
     # -- schedule tables --
     def set_schedule(self, scheduler, num_inference_steps, control_guidance_start=0.0, control_guidance_end=1.0,
@@ -439,7 +529,8 @@ class DenoiseEngine:
         key = PlanKey(type(scheduler).__name__, int(getattr(scheduler, "num_train_timesteps", 1000)), int(num_inference_steps),
                       float(control_guidance_start), float(control_guidance_end), denoising_end, float(base), n, fp.hexdigest(),
                       controlnet=cn_key, inpaint=mode, adapter=ad_key, seeded=seeded,
-                      regions=self.regions.digest() if self.regions is not None else None, freeu=getattr(self.unet, "freeu", None))
+                      regions=self.regions.digest() if self.regions is not None else None, freeu=getattr(self.unet, "freeu", None),
+                      pag=self._pag_key())
         self.t_start = t_start
         self.inpaint = mode
         self.general = general
@@ -494,6 +585,8 @@ class DenoiseEngine:
         e._is_fork = True                        # never tunes: it may record while its parent is running on another stream
         _move(("do_cfg", "guidance", "guidance_rescale", "S", "H", "W", "T_total", "steps", "init_noise_sigma", "_cond_ctx", "cfg_role",
                "xcd_candidates", "xcd_cells", "t_start", "inpaint", "general", "stochastic", "seeded"), self, e)
+        if self.pag:
+            _move(("pag", "pag_scale"), self, e)
         # shared, read-only during denoising: the ControlNet's hint, caches and table, the adapter's features and gate table
         _move(("controlnet", "cn", "cn_scale_tab", "adapter", "ad", "ad_gate_tab", "regions"), self, e)
         st = StepState()
@@ -550,7 +643,7 @@ class DenoiseEngine:
             self.controlnet.precompute_temb(self._temb_ctx, cst, st.t_table)
             self._cn_temb = cst.temb_table
         if not split and self.use_graph and len(self.xcd_candidates) > 1 and self.xcd_cells is None:
-            pk = (self.device.index or 0, self.S, self.H, self.W, str(self.dtype), bool(self.do_cfg))
+            pk = (self.device.index or 0, self.S, self.H, self.W, str(self.dtype), bool(self.do_cfg)) + ((True,) if self.pag else ())
             if pk not in _XCD_PICK and not self._is_fork:
                 _XCD_PICK[pk] = self._pick_xcd_cells()
             self.xcd_cells = _XCD_PICK[pk][0] if pk in _XCD_PICK else 0
@@ -573,6 +666,10 @@ class DenoiseEngine:
                 raise L.ImhError(f"adapter image {tuple(img.shape)}: one image or one per sample ({self.S}) at {8 * self.H} x {8 * self.W}")
             from .t2i_adapter import AdapterResiduals
             extra["adapter"] = AdapterResiduals(self.ad["feats"], scale=self.ad["scale"], tab=self.ad_gate_tab, step=st.step)
+        if self.pag:
+            if split or control is not None or self.adapter is not None:
+                raise NotImplementedError("perturbed-attention guidance runs on a whole engine without a ControlNet or a T2I-Adapter")
+            extra["pag"] = self.S             # [uncond | cond | perturbed]: the perturbed block reads the same S latents
         out = self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg and not split, **extra)
         if split:
             # this rank's half of the noise prediction ends the forward plan; the CFG combine + scheduler step + step counter are a
@@ -598,20 +695,22 @@ class DenoiseEngine:
         six-column row, the history slot and the step's noise row (a seeded schedule: no bank, the launch generates the row from the
         samples' seed rows, imh.h imh_step_seeded); upstream's masked blend rides in either (no extra launch, no extra pass over the
         latents) -- then step++.  pred: the noise prediction, [uncond | cond] under CFG -- the forward's output, or on a cfg_role engine
-        the buffer of both ranks' halves (such an engine always combines and never blends)."""
+        the buffer of both ranks' halves (such an engine always combines and never blends).  Under perturbed-attention guidance pred
+        ends in the perturbed block and both launches run their three-term form (imh.h: i2 = 1, the PAG scale in f3 / f0)."""
         st, S, HW = self.st, self.S, self.H * self.W
         fac = None
+        pag, ps = int(self.pag), self.pag_scale if self.pag else 0.0
         if self.do_cfg and self.guidance_rescale > 0.0:
             fac = ctx.new(S, dtype=torch.float32)
-            ctx.ew(L.EW_CFG_RESCALE, fac, a=pred, i=(S, HW, 0, 0, 0, 0), f=(0.0, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
+            ctx.ew(L.EW_CFG_RESCALE, fac, a=pred, i=(S, HW, pag, 0, 0, 0), f=(ps, 0.0, self.guidance, self.guidance_rescale), descr="cfg.rescale")
         blend = dict(x2=st.inp_z, noise=st.inp_noise, mask=st.inp_mask, blend_tab=st.blend_tab) if self.inpaint == "blend" else {}
         if self.general:
             op, tab, descr = L.EW_CFG_MSTEP, st.coef6_tab, "cfg+mstep+seeded" if self.seeded else "cfg+mstep"
             more = dict(hist=st.hist, bank=st.noise_bank, seeds=st.seed_rows if self.seeded else None)
         else:
             op, tab, descr, more = L.EW_CFG_STEP, st.coef_tab, "cfg+step", {}
-        ctx.ew(op, st.latents, a=pred, w=fac, tab=tab, step=st.step, i=(S, HW, 0, int(self.do_cfg), S if blend else 0, 0),
-               f=(0.0, 0.0, self.guidance, 0.0), descr=descr + ("+blend" if blend else ""), **more, **blend)
+        ctx.ew(op, st.latents, a=pred, w=fac, tab=tab, step=st.step, i=(S, HW, pag, int(self.do_cfg), S if blend else 0, 0),
+               f=(0.0, 0.0, self.guidance, ps), descr=descr + ("+pag" if pag else "") + ("+blend" if blend else ""), **more, **blend)
         ctx.ew(L.EW_STEP_SET, st.step, i=(0, 0, 0, 0, 0, 0), descr="step++")
 
     def _remember_plan(self):
@@ -632,7 +731,7 @@ class DenoiseEngine:
         for cells in self.xcd_candidates:
             rec = Ctx(self.device, self.dtype, record=True)
             rec.xcd_cells = cells
-            self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg)
+            self.unet.emit_forward(rec, st, self.S, self.H, self.W, cfg_dup=self.do_cfg, **({"pag": self.S} if self.pag else {}))
             rec.capture()
             ts = []
             for i in range(11):

@@ -359,6 +359,8 @@ class IPAdapterXL(IPAdapter):
         from .pipeline import (StableDiffusionXLImg2ImgCustomPipeline, StableDiffusionXLInpaintCustomPipeline, _ControlNetPipe,
                                check_controlnet_args, decode_output, edit_moments, prepare_control_image)
         seeds = list(seeds)                       # consumed more than once below: a generator passed as `seeds` must survive that
+        if schedule_kw.get("pag_scale") or schedule_kw.get("pag_adaptive_scale"):
+            raise NotImplementedError("perturbed-attention guidance (pag_scale=) is not built for generate_pns: use generate")
         if judge_preprocess not in ("torch", "hip"):
             raise ValueError(f"judge_preprocess={judge_preprocess!r}: 'torch' or 'hip'")
         if judge_preprocess == "hip" and not hasattr(self.image_encoder, "embed_decoded"):

@@ -106,9 +106,11 @@ class _Call(types.SimpleNamespace):
         return {}
 
     def condition(self, pipe, eng):
+        pag = pipe.pag_scale_of(self)           # (0.0: the call as it always was)
         eng.set_conditioning(self.prompt_embeds, self.negative_prompt_embeds, self.pooled_prompt_embeds, self.negative_pooled_prompt_embeds,
                              self.height, self.width, self.guidance_scale, guidance_rescale=self.guidance_rescale,
-                             original_size=self.original_size, crops_coords_top_left=self.crops_coords_top_left, target_size=self.target_size)
+                             original_size=self.original_size, crops_coords_top_left=self.crops_coords_top_left, target_size=self.target_size,
+                             **({"pag_scale": pag} if pag else {}))
 
     def start(self, pipe, eng, S):
         if self.latents is not None:
@@ -211,6 +213,29 @@ class StableDiffusionXLCustomPipeline(LoRAPipelineMixin):
     def disable_freeu(self):
         self.unet.disable_freeu()
 
+    def set_pag_applied_layers(self, layers):
+        """diffusers' PAGMixin.set_pag_applied_layers: delegates to the UNet (unet.UNet2DConditionModel.set_pag_applied_layers; None
+        switches it off).  The layers take effect in calls with ``pag_scale > 0``."""
+        self.unet.set_pag_applied_layers(layers)
+
+    def pag_scale_of(self, c):
+        """the PAG scale a call runs with: its pag_scale (a keyword of the classes that have none in their signature) where layers are
+        chosen on the UNet, else 0.0 -- the call as it always was.  Refuses what is not built, before any GPU work."""
+        kw = getattr(c, "kwargs", None) or {}
+        scale = float(getattr(c, "pag_scale", None) or kw.get("pag_scale") or 0.0)
+        adaptive = float(getattr(c, "pag_adaptive_scale", None) or kw.get("pag_adaptive_scale") or 0.0)
+        if adaptive != 0.0:
+            raise NotImplementedError("pag_adaptive_scale != 0 (the PAG scale decaying with the timestep) is not built")
+        if scale < 0.0:
+            raise ValueError(f"pag_scale must be >= 0, got {scale}")
+        if scale == 0.0 or not getattr(self.unet, "pag_layers", None):
+            return 0.0
+        for what, other in (("a ControlNet", getattr(self, "controlnet", None)), ("a T2I-Adapter", getattr(self, "adapter", None)),
+                            ("regional image prompts (ip_region_masks=)", kw.get("ip_region_masks"))):
+            if other is not None:
+                raise NotImplementedError(f"perturbed-attention guidance (pag_scale > 0) together with {what} is not built")
+        return scale
+
     def set_scale(self, scale):                                           # custom_pipelines.py:17-20
         for p in self.unet.attn_processors.values():
             if isinstance(p, IPAttnProcessor):
@@ -232,8 +257,14 @@ class StableDiffusionXLCustomPipeline(LoRAPipelineMixin):
                  negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator", **kwargs):
-        """``output_type`` defaults to "pil" as the reference does (custom_pipelines.py:42), so ``test.py:43``'s
+                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
+        """``pag_scale`` > 0 with layers chosen (set_pag_applied_layers): perturbed-attention guidance, diffusers'
+        StableDiffusionXLPAGPipeline -- per sample one more UNet batch member, conditioned like the conditional one and with identity
+        self-attention maps in the chosen layers; eps = u + g (c - u) + pag_scale (c - p), or c + pag_scale (c - p) at
+        guidance_scale <= 1; guidance_rescale applies to that sum.  pag_scale = 0 or no layers: the call as it always was.
+        ``pag_adaptive_scale`` != 0 is refused (NotImplementedError).
+        ``output_type`` defaults to "pil" as the reference does (custom_pipelines.py:42), so ``test.py:43``'s
         ``images[0].save(...)`` works; that needs a VAE (``vae=`` / ``vae_decode=``) -- without one the call fails
         BEFORE denoising with a clear error (pass output_type="latent" for latents).  The default scheduler is
         DDIM (BASELINE.json's metric; IP-Adapter convention) -- stock SDXL ships EulerDiscrete: pass
@@ -248,6 +279,7 @@ class StableDiffusionXLCustomPipeline(LoRAPipelineMixin):
         """The call sequence of every pipeline class, once; c: the __call__'s arguments and hooks.  Refusals of arguments that only one
         __call__ has come before, in that __call__."""
         self._refuse(c.output_type, c.eta, c.kwargs)
+        self.pag_scale_of(c)
         self.step_seed_table(c.step_noise, c.generator, None)
         masks, weights = c.kwargs.get("ip_region_masks"), c.kwargs.get("ip_region_weights")
         if masks is None and weights is not None:
@@ -346,8 +378,10 @@ class StableDiffusionXLImg2ImgCustomPipeline(StableDiffusionXLCustomPipeline):
                  negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
         """aesthetic_score / negative_aesthetic_score are accepted and unused: SDXL base has requires_aesthetics_score=False.
+        pag_scale / pag_adaptive_scale: as the text-to-image call.
         step_noise: as the text-to-image call ("seeded": the step noise of a stochastic scheduler from the generators' seeds; the rows
         read are the schedule's rows t_start .. -- the device step counter, not the count of steps that ran).
         Refused: denoising_start (refiner hand-off), a 4-channel latent ``image``, ``latents=``, eta != 0 (NotImplementedError);
@@ -388,8 +422,11 @@ class StableDiffusionXLInpaintCustomPipeline(StableDiffusionXLCustomPipeline):
                  negative_pooled_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
         """height / width default to the preprocessed image's size (anything else is refused: resize the image first).
+        pag_scale / pag_adaptive_scale: as the text-to-image call; the perturbed member runs under the 4-channel blend and through the
+        9-channel conv_in like the other two.
         aesthetic_score / negative_aesthetic_score are accepted and unused, as for image-to-image; step_noise as there.
         Refused before any GPU work -- NotImplementedError: padding_mask_crop, masked_image_latents=, a 4-channel latent ``image``,
         latents=, denoising_start, eta != 0; ValueError: no image, no mask_image, a mask that cannot be brought to the image's size and
@@ -511,8 +548,11 @@ class StableDiffusionXLControlNetCustomPipeline(_ControlNetPipe, StableDiffusion
                  controlnet_guidance_start: float = 0.0, controlnet_guidance_end: float = 1.0,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator", **kwargs):
-        """image: the control image -- PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1] -- resized to (height, width),
+                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
+        """pag_scale / pag_adaptive_scale: the base call's arguments; perturbed-attention guidance next to this conditioner is not built
+        and refused where it would be on (NotImplementedError).
+        image: the control image -- PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1] -- resized to (height, width),
         not normalised; one image serves every sample.  Everything else as StableDiffusionXLCustomPipeline.__call__.
         Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no image, a window outside 0 <= start <= end <= 1
         (ValueError)."""
@@ -541,8 +581,11 @@ class StableDiffusionXLControlNetImg2ImgCustomPipeline(_ControlNetPipe, StableDi
                  controlnet_guidance_start: float = 0.0, controlnet_guidance_end: float = 1.0,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
-        """control_image: PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1], brought to the init image's height and
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
+        """pag_scale / pag_adaptive_scale: the parent call's arguments; perturbed-attention guidance under a ControlNet is not built and
+        refused where it would be on (NotImplementedError).
+        control_image: PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1], brought to the init image's height and
         width, not normalised; one image serves every sample.  Everything else as StableDiffusionXLImg2ImgCustomPipeline.__call__.
         Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no control_image, a window outside
         0 <= start <= end <= 1 (ValueError); and what the image-to-image call refuses."""
@@ -576,8 +619,11 @@ class StableDiffusionXLControlNetInpaintCustomPipeline(_ControlNetPipe, StableDi
                  controlnet_guidance_start: float = 0.0, controlnet_guidance_end: float = 1.0,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator", **kwargs):
-        """control_image: as for StableDiffusionXLControlNetImg2ImgCustomPipeline, at the init image's height and width.  Everything else
+                 target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
+        """pag_scale / pag_adaptive_scale: the parent call's arguments; perturbed-attention guidance under a ControlNet is not built and
+        refused where it would be on (NotImplementedError).
+        control_image: as for StableDiffusionXLControlNetImg2ImgCustomPipeline, at the init image's height and width.  Everything else
         as StableDiffusionXLInpaintCustomPipeline.__call__, defaults included.
         Refused before any GPU work: guess_mode, a list of scales (NotImplementedError); no control_image, a window outside
         0 <= start <= end <= 1 (ValueError); and what the inpainting call refuses."""
@@ -682,8 +728,11 @@ class StableDiffusionXLAdapterCustomPipeline(StableDiffusionXLCustomPipeline):
                  adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
                  callback=None, callback_steps: int = 1, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator", **kwargs):
-        """image: the control image -- PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1] --, not normalised and not
+                 target_size=None, denoising_end: Optional[float] = None, step_noise: str = "generator",
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, **kwargs):
+        """pag_scale / pag_adaptive_scale: the base call's arguments; perturbed-attention guidance next to this conditioner is not built
+        and refused where it would be on (NotImplementedError).
+        image: the control image -- PIL, a list of PIL images or a float tensor [1 | S, 3, H, W] in [0, 1] --, not normalised and not
         resized: its sides are multiples of 2 x the adapter's downscale factor (32) and equal height / width (which default to the
         image's); one image serves every sample.  Everything else as StableDiffusionXLCustomPipeline.__call__.
         Refused before any GPU work: a list of scales (NotImplementedError); no image, an image of another size, a factor outside

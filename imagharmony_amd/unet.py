@@ -339,10 +339,14 @@ class BasicTransformerBlock(nn.Module):
                              "imagharmony_amd.attention_processor processors")
         ip2 = isinstance(p2, IPAttnProcessor2_0)
         rk = dict(grid=grid) if ip2 and getattr(p2, "regions", None) is not None else {}      # (without regions: the call as it always was)
+        # perturbed-attention guidance: in a chosen layer (set_pag_applied_layers) the last st.pag samples' self-attention map is the identity
+        pk = dict(pag=st.pag) if getattr(st, "pag", 0) and getattr(self.attn1, "pag_identity", False) else {}
+        if pk and not isinstance(p1, AttnProcessor2_0):
+            raise L.ImhError(f"perturbed-attention guidance needs the HIP self-attention processor on attn1, not {type(p1).__name__}")
         if self.fused(L_):
             # LayerNorm never materialises: every consumer GEMM reads the residual stream itself, and takes the rows' statistics
             # from the epilogue of the GEMM that wrote it
-            h1, s1 = p1.emit(ctx, self.attn1, h, B, L_, residual=h, ln=self.norm1, ln_stats=stats, want_stats=True)
+            h1, s1 = p1.emit(ctx, self.attn1, h, B, L_, residual=h, ln=self.norm1, ln_stats=stats, want_stats=True, **pk)
             _free_rows(ctx, h, stats)
             h2, s2 = p2.emit(ctx, self.attn2, h1, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab, ln=self.norm2,
                              ln_stats=s1, want_stats=True, **rk)
@@ -353,7 +357,7 @@ class BasicTransformerBlock(nn.Module):
         if stats is not None:
             ctx.free(stats[0])
         n = _ln(ctx, self.norm1, h, "norm1")
-        h1 = p1.emit(ctx, self.attn1, n, B, L_, residual=h)
+        h1 = p1.emit(ctx, self.attn1, n, B, L_, residual=h, **pk)
         ctx.free(n); ctx.free(h)
         n = _ln(ctx, self.norm2, h1, "norm2")
         h2 = p2.emit(ctx, self.attn2, n, B, L_, residual=h1, kv=kv, step=st.step, scale_tab=st.ip_scale_tab, **rk) \
@@ -515,6 +519,7 @@ class TimestepEmbedding(nn.Module):
 
 class StepState:
     """Device-resident per-image / per-step state the recorded forward reads."""
+    pag = 0        # trailing samples of the forward's batch whose chosen self-attention layers run the identity map: set by emit_forward(pag=)
 
     def __init__(self):
         self.latents = None        # fp32 [S, 4, H, W] (NCHW) -- scheduler state
@@ -856,8 +861,39 @@ class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
         from .freeu import unet_settings
         return unet_settings(self.freeu, bi)
 
+    # ---- perturbed-attention guidance (diffusers PAGMixin.set_pag_applied_layers; the guidance itself is the engine's: denoise.py) ----
+    pag_layers = None        # the patterns as given (a tuple), or None: part of what a recorded plan is (denoise.PlanKey)
+
+    def set_pag_applied_layers(self, layers):
+        """layers: a regular expression or a list of them, each re.search-ed in the dotted names of the attn1 (self-attention) modules as
+        diffusers >= 0.30 does -- "mid" (the mid block's ten layers at SDXL), "down_blocks.2", "up_blocks.0.attentions.1", "." (all) --;
+        the layers any of them matches replace the attention map of the perturbed samples by the identity (out = to_out(to_v(x))).  An
+        entry that matches no attn1 raises ValueError and changes nothing.  None (the default state): off.  Takes effect at the next
+        recording (DenoiseEngine sees the change) and in the eager forward(..., pag=k)."""
+        import re
+        attn1 = [(name, mod) for name, mod in self._attentions() if name.endswith("attn1")]
+        if layers is None:
+            pats = ()
+        else:
+            pats = (layers,) if isinstance(layers, str) else tuple(layers)
+            if not pats or not all(isinstance(p, str) for p in pats):
+                raise ValueError(f"pag_applied_layers takes a regular expression or a non-empty list of them, got {layers!r}")
+        hit = set()
+        for pat in pats:
+            m = {name for name, _ in attn1 if re.search(pat, name) is not None}
+            if not m:
+                raise ValueError(f"pag_applied_layers: {pat!r} matches no self-attention layer (attn1) of this UNet")
+            hit |= m
+        for name, mod in attn1:
+            mod.pag_identity = name in hit
+        self.pag_layers = pats or None
+
+    def pag_layer_names(self):
+        """the dotted names of the attn1 modules the current setting chooses, in module order"""
+        return [name for name, mod in self._attentions() if name.endswith("attn1") and getattr(mod, "pag_identity", False)]
+
     # ---- the forward, as emitted ops ----
-    def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None, adapter=None):
+    def emit_forward(self, ctx, st, S, Hl, Wl, cfg_dup=True, control=None, adapter=None, pag=0, batch=None):
         """Records one UNet forward.  Reads st.latents (fp32 NCHW [S,4,Hl,Wl]); batch B = 2S when
         cfg_dup (CFG halves share the latent, custom_pipelines.py:332).  Returns the noise prediction
         as NHWC [B, Hl*Wl, 4] in the compute dtype.
@@ -866,11 +902,27 @@ class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
         take the place of the superseded tensor's); the down path and the mid block have read the unmodified tensors, as upstream.
         The residuals are consumed.  None: the launch list is what it is without the argument.
         adapter: a t2i_adapter.AdapterResiduals (diffusers down_intrablock_additional_residuals): four gated adds inside the down path and
-        behind the mid block (_emit_encoder); the features are per-image state and are not consumed.  Not together with control."""
+        behind the mid block (_emit_encoder); the features are per-image state and are not consumed.  Not together with control.
+        pag = k > 0 (perturbed-attention guidance): k further samples BEHIND the (CFG-duplicated) batch, B = 2S + k | S + k -- batch member
+        b reads latent b % S, so k = S gives [uncond | cond | perturbed] -- conditioned by the rows of st the caller put there; in the
+        layers set_pag_applied_layers chose, their self-attention map is the identity.  Without chosen layers, or with a ControlNet or a
+        T2I-Adapter (their branches would need the further batch member), refused.  batch: the whole batch where it is not the sum above
+        (the eager forward: the last k of the samples it was given)."""
         if adapter is not None and control is not None:
             raise NotImplementedError("a T2I-Adapter together with a ControlNet is not built")
         cfg = self.config
-        B = self._latent_batch(S, Hl, Wl, cfg_dup)
+        B = self._latent_batch(S, Hl, Wl, cfg_dup) + int(pag)
+        if batch is not None:
+            B = int(batch)
+        if pag:
+            if control is not None or adapter is not None:
+                raise NotImplementedError("perturbed-attention guidance under a ControlNet or a T2I-Adapter is not built")
+            if not self.pag_layers:
+                raise L.ImhError("perturbed samples without chosen layers: set_pag_applied_layers first")
+            if not 0 < int(pag) < B:
+                raise L.ImhError(f"{pag} perturbed samples of a batch of {B}")
+        if pag or getattr(st, "pag", 0):
+            st.pag = int(pag)
         # -- time embedding (SURVEY.md Appendix A.1) --
         ctx.tag = 1
         self._emit_time_embedding(ctx, st, B)
@@ -945,6 +997,9 @@ class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, cross_attention_kwargs=None,
                 return_dict=False, **kw):
+        """pag = k (keyword; default 0): the last k samples of the batch are perturbed ones -- in the layers set_pag_applied_layers chose
+        their self-attention map is the identity (what diffusers' PAG processors do to the trailing chunk of the batch)"""
+        pag = int(kw.pop("pag", 0))
         intra = kw.pop("down_intrablock_additional_residuals", None)
         if intra is not None:                    # a T2I-Adapter's features: four NCHW tensors, already scaled (diffusers T2IAdapter.forward's outputs)
             if kw.get("down_block_additional_residuals") is not None or kw.get("mid_block_additional_residual") is not None:
@@ -967,6 +1022,7 @@ class UNet2DConditionModel(LoRAMixin, UNetEncoderModel):
         if down_res is not None:                 # NCHW, already scaled (diffusers ControlNetModel.forward's outputs)
             from .controlnet import ControlResiduals
             control = ControlResiduals([nhwc(t) for t in down_res], nhwc(mid_res))
-        out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, control=control, **({"adapter": adapter} if adapter is not None else {}))
+        out = self.emit_forward(ctx, st, B, Hl, Wl, cfg_dup=False, control=control, **({"adapter": adapter} if adapter is not None else {}),
+                                **({"pag": pag, "batch": B} if pag else {}))
         y = out.view(B, Hl, Wl, -1).permute(0, 3, 1, 2).to(sample.dtype)
         return (y,)

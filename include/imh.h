@@ -442,7 +442,17 @@ enum imh_ew_op {
                            *   every call, eager or from a plan), one rounding at the end -- where x and (s - 1) * low cancel, an ulp of the
                            *   result is smaller than one fp32 rounding of the sums.  imagharmony_amd/freeu.py restates it in numpy float64.
                            * Refused without a launch (the text names `concat`): i0 / i1 no multiples of 8, i4 outside [0, i0], H or W < 2,
-                           * H * W not dividing n, H + W beyond the tables' LDS (about 3000). */
+                           * H * W not dividing n, H + W beyond the tables' LDS (about 3000).
+                           * Additive, ABI unchanged -- the identity-attention form, selected by i5 > 0 (0 in every other call): the self-attention
+                           * output of samples whose attention map is the identity (perturbed-attention guidance: softmax(QK^T) := I, so the
+                           * output is V) read out of V^T as the self-attention projections leave it.  b = Vt (T) [C = i1, ldvt = i5], the keys of
+                           * every 16-group stored in the order [0-3, 8-11, 4-7, 12-15] (imh_attention's V^T layout; perm16 swaps runs 1 and 2 of
+                           * 4 and is its own inverse); the first part is empty (i0 = 0, `a` unused), i2 = 0, i3 = row stride of y, i4 = col0:
+                           *   y[r, c] = Vt[c, col0 + 16 * (r / 16) + perm16(r % 16)]      0 <= r < n,  0 <= c < C
+                           * -- a transposing copy, bit for bit, through one 64 x 64 LDS tile per workgroup; no atomics, no workspace.
+                           * Refused without a launch, IMH_ERR_ARG (the text names `concat`): n or col0 no multiple of 16 (n > 0, col0 >= 0), C
+                           * no positive multiple of 8, ldvt or i3 no multiple of 8, ldvt < col0 + n, i3 < C, i0 != 0 or i2 != 0, b NULL, b or y
+                           * not 16-byte aligned. */
     IMH_EW_CONV_IN = 3,   /* conv_in + CFG duplication (custom_pipelines.py:332) + scale_model_input (:334).  ABI 11: i5 = input channels, 0 | 4 (the
                            * latents alone) or 9 (the SDXL inpainting UNet): channels 4-8 = [mask | masked-image latents] come unscaled from `x2`,
                            * fp32 NCHW [i0, 5, H, W], the same at every step; w is then [C0][9][3][3] */
@@ -450,12 +460,21 @@ enum imh_ew_op {
                            * blend of diffusers StableDiffusionXLInpaintPipeline (4-channel UNet),
                            *   y = (1 - m) * (ba * x2 + bb * noise) + m * y,   (ba, bb) = blend_tab[2 * *step + {0, 1}]  (step REQUIRED),
                            * all fp32: x2 = the image latents z [i0, 4, i1], noise = the add-noise noise [i0, 4, i1], mask = the latent mask
-                           * [i4, i1] (1 = repaint; sample s reads mask s % i4, i4 >= 1); a == NULL: the blend alone (no CFG / scheduler update) */
+                           * [i4, i1] (1 = repaint; sample s reads mask s % i4, i4 >= 1); a == NULL: the blend alone (no CFG / scheduler update).
+                           * Additive, ABI unchanged -- the three-term form, selected by i2 = 1 (0: the op as it was, same kernel):
+                           * perturbed-attention guidance (diffusers PAGMixin._apply_perturbed_attention_guidance), f3 = the PAG scale s.  `a`
+                           * carries one more block of i0 samples, the conditional prediction under identity self-attention maps, p:
+                           *   i3 = 1: a = [uncond | cond | perturbed] = [3 i0, i1, 4],  eps = (u + f2 * (c - u)) + s * (c - p);
+                           *   i3 = 0: a = [cond | perturbed] = [2 i0, i1, 4],           eps = c + s * (c - p);
+                           * everything behind eps (w, the update, the blend) is what it is without.  i2 outside {0, 1}, or i2 = 1 with
+                           * a == NULL: IMH_ERR_ARG. */
     IMH_EW_CAST_F32 = 5,
     IMH_EW_ADD = 6,
     IMH_EW_STEP_SET = 7,  /* *y(int32) = i1 ? i0 : *y + 1 : the device-side step counter */
     IMH_EW_CFG_RESCALE = 8, /* y[s] = f3 * std(eps_text_s) / std(eps_cfg_s) + 1 - f3 (rescale_noise_cfg, custom_pipelines.py:351-354);
-                             * a = noise prediction NHWC [2 i0, i1, 4], f2 = guidance scale; IMH_EW_CFG_STEP reads y through `w` */
+                             * a = noise prediction NHWC [2 i0, i1, 4], f2 = guidance scale; IMH_EW_CFG_STEP reads y through `w`.
+                             * i2 = 1 (additive; 0: the op as it was): the three-term form of IMH_EW_CFG_STEP -- a = [3 i0, i1, 4], f0 = the PAG
+                             * scale s, eps_cfg = (u + f2 * (c - u)) + s * (c - p) */
     IMH_EW_SOFTMAX = 9,     /* y[r,:] (T) = softmax(f0 * a[r,:]) with a fp32 (VAE mid-block attention); i0 rows, i1 cols, i2 / i3 leading dims */
     IMH_EW_ROW_STATS = 10,  /* y[r] (fp32 pair) = (sum, M2) of a[r, 0:i0] (row stride i1), n rows: LayerNorm statistics in the ln_stats format, one slot */
     IMH_EW_STEP_ROW = 11,   /* y[0:n] = a[*step * n + 0:n] (T; n % 8 == 0): row `step` of a per-schedule table (time embeddings of all denoise steps) */
@@ -477,7 +496,9 @@ enum imh_ew_op {
                              * h = `b`, a fp32 history buffer [i0, 4, i1] that the launch READS AND WRITES in place (each element by one
                              * thread), z = row *step of the fp32 noise bank `bias` [n, i0, 4, i1].  b == NULL / bias == NULL: that term is
                              * absent (and h is not written).  With `mask` set the masked blend of IMH_EW_CFG_STEP follows in the same pass, same
-                             * fields, same blend_tab -- except that `a` is REQUIRED here: there is no blend-alone form (a == NULL is an error).  With ch = cn = 0 and neither h nor bank the result equals IMH_EW_CFG_STEP's bit for bit. */
+                             * fields, same blend_tab -- except that `a` is REQUIRED here: there is no blend-alone form (a == NULL is an error).  With ch = cn = 0 and neither h nor bank the result equals IMH_EW_CFG_STEP's bit for bit.
+                             * i2 = 1, f3 = the PAG scale: the three-term eps of IMH_EW_CFG_STEP, same layout of `a`, in every form of this op
+                             * (bank, imh_step_seeded, with and without the blend). */
 };
 
 typedef struct imh_ew_args {
@@ -504,8 +525,11 @@ typedef struct imh_ew_args {
  * IMH_EW_STEP_ROW reads row *step of `a` only; `tab` / `blend_tab` are read at row *step only; IMH_EW_GATHER_ROWS reads idx[0, n), columns
  * [0, C) of the table rows idx names and of add's rows [0, min(n, P)), and writes columns [0, C) of y's rows [0, n).  IMH_EW_CFG_MSTEP reads
  * its six-column `tab` and the noise bank `bias` at row *step only (6 floats and i0 * 4 * i1 floats), and reads and writes exactly the
- * i0 * 4 * i1 elements of y and of the history buffer `b`.  IMH_EW_CONCAT, both forms, reads the n * i0 elements of `a` and the n * i1 of `b`,
- * writes the n * (i0 + i1) elements of y and touches nothing else (the FreeU form reads `b` twice and keeps its sums on chip). */
+ * i0 * 4 * i1 elements of y and of the history buffer `b`.  IMH_EW_CONCAT, plain and FreeU form, reads the n * i0 elements of `a` and the n * i1 of `b`,
+ * writes the n * (i0 + i1) elements of y and touches nothing else (the FreeU form reads `b` twice and keeps its sums on chip); its
+ * identity-attention form (i5 > 0) reads columns [i4, i4 + n) of the i1 rows of `b` (row stride i5) and writes columns [0, i1) of y's rows
+ * [0, n) (row stride i3): the slack columns of either side are neither read nor written.  The three-term forms (i2 = 1) of
+ * IMH_EW_CFG_STEP / IMH_EW_CFG_MSTEP / IMH_EW_CFG_RESCALE read one more block of i0 * i1 * 4 elements of `a` and nothing else besides. */
 int imh_elementwise(int op, const imh_ew_args* a, void* stream);
 
 /* ---- seeded step noise: the noise of the stochastic samplers as a pure function of (seed, lane, table row, element) --------------
